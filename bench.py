@@ -5,8 +5,14 @@ Workload = Groth16 prove of the synthetic iterated-cubic R1CS wit
 the witness already resident in HBM.  A STEP = `--proofs-per-step` (16) consecutive proofs of the pipelined prover
 (`--inflight` proofs in flight, one HIP stream each; the pipeline is NOT drained between steps).
 N = 1: n = 2^20 constraints (BASELINE.json configs[2]: the largest configuration the metric names for ONE GPU) is the headline
-`value`; the same run then times the other single-GPU configurations (2^16 = configs[1], 2^18, 2^22 = config 4's size on one
+`value`; with `--full` the same run then times the other single-GPU configurations (2^16 = configs[1], 2^18, 2^22 = config 4's size on one
 GPU, and Pinocchio 2^18 = config 5) and reports them under `other_workloads`, each with its own parity check.
+
+PLAIN RUN (no `--full`): the headline only -- set-up, warm-up, the `--steps` timed steps, `--dump-outputs`, the line.  The key's Lagrange form
+comes straight from the keygen (the same pools, byte for byte, that `--full` derives on the device from the tau-power key in ~30 s at 2^20),
+so the timed proofs are the same ones.  `--full` adds everything else: the key as uploaded and its on-device derivation, the parity gate,
+single-proof latency, the per-kernel pass and the rooflines, the CPU baselines, the other workloads (and config 4 at N = 8).
+`--dump-outputs DIR`: the proofs of the LAST timed step (the bytes of a | b | c as a caller receives them) as DIR/proof_{a,b,c}.npy, float32.
 N > 1 (`python bench.py --gpus N` starts its own N ranks; under torch.distributed.run it is one of them): the SAME proof of
 2^log_n constraints, its three multi-scalar products sharded by base points over the ranks (one process per GPU) -- total work
 fixed => "strong" scaling; `--weak` makes it 2^log_n constraints PER GPU instead (BASELINE config 4 = --gpus 8 --log-n 19 --weak).
@@ -14,7 +20,7 @@ Proofs go in rounds: rank j runs the Fr stage of the proofs it owns, one all-to-
 its slice of every proof's scalars, the 768-byte partial sums of a round travel in one all-gather (EC addition is not an RCCL
 reduction operator) and are added on the GPU.
 
-PARITY GATE: after every timed region the proof of the LAST timed (r, s) is compared with the oracle's trapdoor
+PARITY GATE (`--full`): after every timed region the proof of the LAST timed (r, s) is compared with the oracle's trapdoor
 evaluation (exact at any n; CPU, outside the timed region).  A mismatch aborts the run: no throughput is printed for
 wrong proofs.
 
@@ -300,7 +306,9 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
     rng = seeded(0x5EED0002)
     toxic = [rng() for _ in range(5)]
     it = iter(toxic)
-    pk, _vk = Groth16.keygen(lambda: next(it), cs, lagrange=lagrange)
+    # plain run: the Lagrange-form pools the derivation would yield come from the keygen (same tau, same bytes) and are uploaded as they are
+    keygen_lagrange = (not args.full and derive_upto is not None and log_n <= derive_upto and world == 1 and not lagrange)
+    pk, _vk = Groth16.keygen(lambda: next(it), cs, lagrange=lagrange or keygen_lagrange)
     # N > 1 with the derivation enabled for this total size: every rank uploads the key WHOLE, the ranks SHARE the derivation of its Lagrange form
     # (one of the three independent sets per rank, broadcast) and each keeps its shard (cut for equal work, zk_groth16_shard_range).  Otherwise (--derive-lagrange-upto -1, or a total size
     # beyond it) the key is sharded at upload and stays in tau-power form.
@@ -316,7 +324,7 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
         # vector) -- replicated, every rank would run a (2^log_n x world)-constraint Fr stage per proof beside an MSM slice that does
         # not grow with the world size; --replicated-fr keeps the simpler scheme
     else:
-        prover = Groth16(cs, pk, rank, world, lagrange=lagrange)
+        prover = Groth16(cs, pk, rank, world, lagrange=lagrange or keygen_lagrange)
     prover.set_witness(w)
     w_host = RC.fr_bytes(w) if args.host_witness else None          # --host-witness: every proof gets the witness as a HOST buffer (one PCIe copy per proof)
     pps = args.proofs_per_step
@@ -342,32 +350,43 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
         group = GroupProver(prover)
     setup_s = time.perf_counter() - t_setup
 
-    def run(first, count):
+    def run(first, count, keep=None):
         """count proofs; proof i uses rs[(first + i) % len(rs)].  One GPU: `depth` of them in flight, proof i on slot i % depth.
         N > 1: rounds of `group.batch` (distributed Fr stage), each rank finishing the proofs it owns.
+        keep (a list): receives, in order, the proofs of the last `pps` indices (the last step) that this rank holds.
         Returns (last proof this rank holds, index into rs of that proof)."""
+        tail = max(0, count - pps)
         if group is not None:
             got = group.prove_many([rs[(first + i) % len(rs)] for i in range(count)], combine_all=False)
+            if keep is not None:
+                keep.extend(g for g in got[tail:] if g is not None)
             mine = [(g, (first + i) % len(rs)) for i, g in enumerate(got) if g is not None]
             return mine[-1] if mine else (None, None)
         last = None
         for i in range(count):
             if depth == 1:
                 last = prover.prove_rs(w_host, *rs[(first + i) % len(rs)])
+                if keep is not None and i >= tail:
+                    keep.append(last)
                 continue
             if i >= depth:
-                last = prover.prove_wait(i % depth)
+                last = prover.prove_wait(i % depth)          # proof i - depth
+                if keep is not None and i - depth >= tail:
+                    keep.append(last)
             prover.prove_async(w_host, *rs[(first + i) % len(rs)], i % depth)
         if depth > 1:
             for i in range(max(0, count - depth), count):
                 last = prover.prove_wait(i % depth)
+                if keep is not None and i >= tail:
+                    keep.append(last)
         return last, (first + count - 1) % len(rs)
 
     last_idx = [None]
     counters = [None]
+    last_step = []          # the proofs of the last timed step (--dump-outputs)
 
     def measure(with_families):
-        """warm-up + settle, the timed region, single-proof latency (and, with_families, the un-overlapped per-family pass), the parity gate"""
+        """warm-up + settle, the timed region; --full: single-proof latency (and, with_families, the un-overlapped per-family pass), the parity gate"""
         run(0, max(nwarm, 1))
         sync()
         # A box that has been idle starts in a low-power state and needs seconds of load before its clocks
@@ -387,8 +406,9 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
         # (level 1: two recycled event records per launch; nothing synchronises)
         _lib.check(L.zk_profile_reset())
         _lib.check(L.zk_profile_enable(1 if events else 0))
+        del last_step[:]
         t0 = time.perf_counter()
-        proof, proof_idx = run(nwarm, nproofs)
+        proof, proof_idx = run(nwarm, nproofs, last_step)
         last_idx[0] = proof_idx
         sync()
         dt = time.perf_counter() - t0
@@ -404,7 +424,7 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
         n_alone = 4 if log_n <= 20 else 2
         lat = None
         fam_alone = {}
-        if world == 1:
+        if world == 1 and args.full:
             _lib.check(L.zk_profile_reset())
             prover.prove_rs(None, *rs[0])
             t1 = time.perf_counter()
@@ -422,7 +442,7 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
 
         # ---- PARITY GATE (CPU oracle, outside every timed region): the last timed proof this rank holds
         parity = None
-        if proof is not None and not args.no_parity_gate:
+        if proof is not None and args.full and not args.no_parity_gate:
             O = oracle()
             frs = lambda xs: bytes(RC.fr_bytes(xs))
             csr = [O.CSR(M.ptr, M.col, M.val) for M in (cs.L, cs.R, cs.O)]
@@ -437,8 +457,8 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
     # A key in the reference's format (tau powers) can be turned into its Lagrange form ON THE DEVICE, once per key, without tau
     # (zk_groth16_pk_derive_lagrange): the per-proof basis conversion disappears, the proofs do not change.  When asked to, the run measures
     # the key as uploaded first, then derives (untimed, reported as derive_lagrange_s) and measures again: `value` is the second figure,
-    # `tau_power_form` keeps the first.
-    derive = derive_upto is not None and log_n <= derive_upto and world == 1 and not lagrange
+    # `tau_power_form` keeps the first.  A plain run (keygen_lagrange) uploaded those pools from the keygen and measures once.
+    derive = derive_upto is not None and log_n <= derive_upto and world == 1 and not lagrange and not keygen_lagrange
     if derive and not args.derived_only and args.time_budget > 0:
         est = 31.0 * n / (1 << 20) * (1.08 if log_n > 20 else 1.0) + 12.0 * n / (1 << 22)          # derivation + the second measurement and its parity check
         spent = time.perf_counter() - T_START
@@ -472,7 +492,7 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
     # convolutions over the Lagrange-form pools this key now holds), all threads of this process's CPU share, one proof, untimed w.r.t. `value`;
     # its bytes must equal the GPU's last timed proof
     cpu_fast = None
-    if world == 1 and (derive or lagrange) and log_n <= args.cpu_fast_upto and proof is not None and not args.no_cpu_baseline:
+    if args.full and world == 1 and (derive or lagrange) and log_n <= args.cpu_fast_upto and proof is not None and not args.no_cpu_baseline:
         O = oracle()
         frs = lambda xs: bytes(RC.fr_bytes(xs))
         csr = [O.CSR(M.ptr, M.col, M.val) for M in (cs.L, cs.R, cs.O)]
@@ -503,7 +523,7 @@ def bench_groth16(args, L, _lib, log_n, steps, warmup, inflight, settle, rank, w
            "fam_timed": fam_timed, "fam_alone": fam_alone, "n_alone": n_alone, "nproofs": nproofs, "counters": counters[0],
            "kernel_ms_per_proof": {k: round(v["ms_per_proof"], 4) for k, v in sorted(fam_alone.items())},
            "proof_compressed_hex": proof.to_compressed().hex() if proof is not None else None,
-           "group_batch": group.batch if group is not None else None}
+           "group_batch": group.batch if group is not None else None, "keygen_lagrange": keygen_lagrange, "last_step": list(last_step)}
     if group is not None:
         # exchange volume per proof and rank (device to device over xGMI): three scalar vectors, 32 B per element
         res["exchange"] = {"all_to_all_bytes_per_proof_sent_by_owner": 32 * ((min(group.nzA, group.p1) if group.clipA else group.p1) + group.p1 + group.p2),      # A: clipped to its non-zero prefix only when no rank's slice gets empty
@@ -672,8 +692,8 @@ def compact_line(full):
     cfg = full.get("config") or {}
     tpf = cfg.get("tau_power_form") or {}
     out = {k: full.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
-    key_form = "lagrange_extension_uploaded" if "LAGRANGE-FORM KEY EXTENSION" in (cfg.get("workload") or "") else (
-        "tau_powers_uploaded_lagrange_derived_on_device" if cfg.get("derive_lagrange_s") is not None else "tau_powers_as_uploaded")
+    key_form = cfg.get("key_form") or ("lagrange_extension_uploaded" if "LAGRANGE-FORM KEY EXTENSION" in (cfg.get("workload") or "") else (
+        "tau_powers_uploaded_lagrange_derived_on_device" if cfg.get("derive_lagrange_s") is not None else "tau_powers_as_uploaded"))
     log_n = (int(cfg.get("constraints") or 1) - 1).bit_length()
     out["config"] = {"workload": "groth16_prove 2^%d, iterated-cubic R1CS, BLS12-381, %s" % (log_n, "key+circuit resident, witness handed over per proof (PCIe-inclusive)"
                                  if "PCIe-inclusive" in (cfg.get("workload") or "") else "key+circuit+witness resident in HBM"),
@@ -681,7 +701,8 @@ def compact_line(full):
                      "derive_lagrange_s": cfg.get("derive_lagrange_s"), "break_even_proofs": tpf.get("break_even_proofs"),
                      "proofs_in_flight": cfg.get("proofs_in_flight"), "proofs_per_step": cfg.get("proofs_per_step"),
                      "sharding": (cfg.get("sharding") or "")[:160], "fr_stage": (cfg.get("fr_stage") or None) and cfg["fr_stage"][:120], "rehearsal_ranks_share_gpus": cfg.get("rehearsal_ranks_share_gpus"), "device_list": cfg.get("device_list"),
-                     "prove_algorithmic_bytes_per_constraint": cfg.get("prove_algorithmic_bytes_per_constraint"), "prove_hbm_frac": cfg.get("prove_hbm_frac")}
+                     "prove_algorithmic_bytes_per_constraint": cfg.get("prove_algorithmic_bytes_per_constraint"), "prove_hbm_frac": cfg.get("prove_hbm_frac"),
+                     "run": cfg.get("run")}
     out["ms_per_proof"] = full.get("ms_per_proof")
     out["single_proof_latency_ms"] = full.get("single_proof_latency_ms")
     roof = full.get("roofline")
@@ -725,6 +746,16 @@ def compact_line(full):
     raise SystemExit("bench.py: the result line does not fit %d bytes even without its optional blocks" % LINE_BUDGET)
 
 
+def dump_outputs(dirname, proofs):
+    """--dump-outputs: the proofs of the last timed step as a caller receives them (uncompressed G1 a | G2 b | G1 c, 96 | 192 | 96 bytes), one row
+    per proof in the order the step made them, each byte as a float32 (exact) -- DIR/proof_a.npy, proof_b.npy, proof_c.npy.  16 proofs are 24 KB."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, width in (("a", 96), ("b", 192), ("c", 96)):
+        rows = [np.frombuffer(getattr(p, name), dtype=np.uint8) for p in proofs]
+        arr = np.stack(rows).astype(np.float32) if rows else np.zeros((0, width), dtype=np.float32)
+        np.save(os.path.join(dirname, "proof_%s.npy" % name), arr)
+
+
 def emit(full):
     """detail -> bench_detail.json + stderr; the compact line -> stdout (the LAST line of stdout)"""
     detail = json.dumps(full)
@@ -754,7 +785,7 @@ def main():
     ap.add_argument("--config4-world", type=int, default=8, help="N at which the run ALSO measures BASELINE config 4 (2^config4-log-n constraints per rank, weak) into other_workloads")
     ap.add_argument("--config4-log-n", type=int, default=19)
     ap.add_argument("--dense-rows", type=int, default=20, help="one GPU: log2 size of the dense_rows workload (random R1CS, 8 entries per row; other_workloads only), -1 = skip")
-    ap.add_argument("--no-pinocchio", action="store_true", help="skip the Pinocchio 2^18 workload (config 5) of the default run")
+    ap.add_argument("--no-pinocchio", action="store_true", help="skip the Pinocchio 2^18 workload (config 5) of the --full run")
     ap.add_argument("--headline-only", action="store_true", help="only the headline workload (profiling runs): same as --sizes '' --no-pinocchio")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-budget", type=float, default=20.0, help="seconds of one host core the literal-algorithm ladder of cpu_baseline may take (n = 16, 64, 128, 256, 1024 while the fitted O(m n) law says the next size fits; "
@@ -767,9 +798,10 @@ def main():
                     "not the reference's key format -- the default and the headline use the tau-power key)")
     ap.add_argument("--derive-lagrange-upto", type=int, default=22, help="one GPU: for workloads of at most 2^K constraints, measure the reference-format key as uploaded, "
                     "then derive its Lagrange form on the device (zk_groth16_pk_derive_lagrange: once per key, untimed -- 2.7 s at 2^16, 6.7 s at 2^18, 31 s at 2^20, 147 s at 2^22) and "
-                    "measure again: `value` is the derived key's figure, `tau_power_form` the other one.  -1 = never derive")
+                    "measure again: `value` is the derived key's figure, `tau_power_form` the other one (--full; a plain run uploads the same Lagrange-form pools from the keygen "
+                    "and measures them only).  -1 = never derive")
     ap.add_argument("--time-budget", type=float, default=330.0, help="seconds of wall clock the whole run aims to stay within: a derivation whose estimate (31 s x n / 2^20, 8 %% more above 2^20) does not fit what is left "
-                    "is skipped and that workload reports its tau-power figure only (the default run is ~5 min with the 147 s derivation of the 2^22 key)")
+                    "is skipped and that workload reports its tau-power figure only (the --full run is ~5 min with the 147 s derivation of the 2^22 key)")
     ap.add_argument("--host-witness", action="store_true", help="one GPU: hand the witness over as a host buffer with every proof (the PCIe-inclusive rate of DESIGN.md 8) instead of "
                     "proving from the copy made resident by zk_groth16_set_witness; never the headline")
     ap.add_argument("--derived-only", action="store_true", help="profiling runs: derive the key's Lagrange form right after the upload and measure only that path "
@@ -782,6 +814,10 @@ def main():
                     "Not the driver's --gpus N contract (that is one process per GPU over RCCL); n_gpus in the line = distinct devices of the list")
     ap.add_argument("--settle", type=float, default=4.0, help="max seconds of untimed load before timing so the clocks leave the idle state (0 = off)")
     ap.add_argument("--inflight", type=int, default=14, help="proofs kept in flight on one GPU, one stream each (1 = strictly serial)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: the key as uploaded and its on-device derivation, the parity gate, latency, "
+                    "per-kernel pass and rooflines, CPU baselines, the other workloads (--sizes, --dense-rows, Pinocchio, config 4); without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the proofs of the last timed step (bytes of a | b | c, "
+                    "as float32) to DIR/proof_a.npy, proof_b.npy, proof_c.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -834,6 +870,7 @@ def main():
         import torch
         tiny = argparse.Namespace(**vars(args))
         tiny.weak = False
+        tiny.full = True          # the rehearsal decides the Fr path: it keeps its parity gate in a plain run too
         err = ""
         try:
             bench_groth16(tiny, L, _lib, min(args.log_n, 10), 1, 0, 2, 0.0, rank, world, dist, derive_upto=None, events=False)
@@ -853,11 +890,13 @@ def main():
     head = bench_groth16(args, L, _lib, args.log_n, args.steps, args.warmup, args.inflight, args.settle, rank, world, dist,
                          lagrange=args.lagrange_key, replicated_fr=replicated, events=not args.no_live_events,
                          derive_upto=args.derive_lagrange_upto if args.derive_lagrange_upto >= 0 else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["last_step"])
     # BASELINE config 4 (2^22 constraints, MSM point-sharded over 8 ranks) beside the N = 8 line of the scaling curve: the driver's SCALE command
     # measures the SAME 2^log_n proof on every N (strong scaling); config 4 is `--gpus 8 --weak --log-n 19`, so the 8-rank run adds it itself
     # (reference-format key sharded at upload, no derivation: a few proofs, parity-gated)
     config4 = None
-    if world > 1 and world == args.config4_world and not args.weak and not args.headline_only:
+    if args.full and world > 1 and world == args.config4_world and not args.weak and not args.headline_only:
         a4 = argparse.Namespace(**vars(args))
         a4.weak = True
         # never at the price of the headline: the N = 8 line above is already measured; if this extra leg raises (memory, a parity failure, a collective the
@@ -873,9 +912,13 @@ def main():
                        "value": r4["value"], "constraints": r4["constraints"], "ms_per_proof": r4["ms_per_proof"], "parity": r4["parity"], "tau_power_form": {"value": r4["value"]},
                        "derive_lagrange_s": None}
     peak = C.c_double()
-    _lib.check(L.zk_bench_field_mul(1 | 8, 2000, C.byref(peak)))   # the library's dependent-chain product benchmark on this chip, in this process: best of 2 / 4 / 6 / 8 waves per SIMD
-    traffic = pmc_traffic()
+    traffic = None
+    if args.full:
+        _lib.check(L.zk_bench_field_mul(1 | 8, 2000, C.byref(peak)))   # the library's dependent-chain product benchmark on this chip, in this process: best of 2 / 4 / 6 / 8 waves per SIMD
+        traffic = pmc_traffic()
     head_pub, roofs = summarize(head, world, peak.value, traffic, args.lagrange_key)
+    if not args.full:
+        roofs = {}          # the rooflines rest on the un-overlapped pass and the multiplier peak: --full
 
     others = [config4] if config4 else []
 
@@ -894,18 +937,19 @@ def main():
 
     # order: the short workloads, Pinocchio, the CPU ladder -- and the sizes above 2^20 LAST, so that the wall-clock guard of their (minutes-long)
     # derivation sees everything else already spent (--time-budget)
-    sizes = [int(t) for t in args.sizes.split(",") if t.strip() and int(t) != args.log_n] if world == 1 and rank == 0 and not args.headline_only else []
+    extra = args.full and world == 1 and rank == 0 and not args.headline_only
+    sizes = [int(t) for t in args.sizes.split(",") if t.strip() and int(t) != args.log_n] if extra else []
     for ln in [x for x in sizes if x <= 20]:
         other_size(ln)
-    if world == 1 and rank == 0 and not args.headline_only and args.dense_rows >= 0:
+    if extra and args.dense_rows >= 0:
         if time.perf_counter() - T_START + 60 < args.time_budget:          # ~25 s of host-side generation + keygen at 2^20
             other_size(args.dense_rows, "dense_rows")
         else:
             print("bench.py: the dense_rows workload does not fit --time-budget: skipped", file=sys.stderr)
-    if world == 1 and rank == 0 and not args.headline_only and not args.no_pinocchio:
+    if extra and not args.no_pinocchio:
         others.append(bench_pinocchio(args, L, _lib, 18, 48, 8, peak.value))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_baseline_budget)
     for ln in [x for x in sizes if x > 20]:
         other_size(ln)
@@ -942,7 +986,10 @@ def main():
             "data": "synthetic",
             "config": {"workload": "groth16_prove, iterated-cubic R1CS (u -> u^3+u+3), BLS12-381, " + ("key+circuit resident in HBM, witness handed over as a HOST buffer with every proof (PCIe-inclusive)" if args.host_witness else "key+circuit+witness resident in HBM")
                                    + (", LAGRANGE-FORM KEY EXTENSION (not the reference key format)" if args.lagrange_key else "")
-                                   + (", reference-format key (tau powers) uploaded, its Lagrange form DERIVED on the device once (zk_groth16_pk_derive_lagrange); tau_power_form = the same key before the derivation" if head.get("derive_lagrange_s") is not None else ""),
+                                   + (", reference-format key (tau powers) uploaded, its Lagrange form DERIVED on the device once (zk_groth16_pk_derive_lagrange); tau_power_form = the same key before the derivation" if head.get("derive_lagrange_s") is not None else "")
+                                   + (", the key's Lagrange form uploaded from the keygen: the pools --full derives on the device from the tau-power key, byte for byte" if head.get("keygen_lagrange") else ""),
+                       "key_form": "lagrange_form_from_keygen_same_pools_as_derived" if head.get("keygen_lagrange") else None,
+                       "run": "full" if args.full else "plain: headline only (--full adds the derivation, parity gate, latency, rooflines, CPU baselines, other workloads)",
                        "step": "%d consecutive proofs of the pipelined prover (pipeline not drained between steps)" % args.proofs_per_step,
                        "proofs_per_step": args.proofs_per_step, "timed_proofs": head["timed_proofs"], "timed_s": head["timed_s"],
                        "constraints": head["constraints"], "variables": head["variables"], "proofs_in_flight": head["proofs_in_flight"], "constraints_per_gpu": head["constraints"] // world,

@@ -8,7 +8,7 @@ for rep in 1 2; do
   i=0
   for e in "$@"; do
     i=$((i+1))
-    env $e timeout -k 10 400 python bench.py --headline-only --no-cpu-baseline --derive-lagrange-upto ${DERIVE:--1} $ARGS > $O/ab_${i}_$rep.json 2> $O/ab_${i}_$rep.err || { tail -5 $O/ab_${i}_$rep.err; exit 1; }
+    env $e timeout -k 10 400 python bench.py --full --headline-only --no-cpu-baseline --derive-lagrange-upto ${DERIVE:--1} $ARGS > $O/ab_${i}_$rep.json 2> $O/ab_${i}_$rep.err || { tail -5 $O/ab_${i}_$rep.err; exit 1; }
     cp bench_detail.json $O/ab_${i}_${rep}_detail.json
     python -c "
 import json

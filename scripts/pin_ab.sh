@@ -6,7 +6,7 @@ for rep in 1 2; do
   i=0
   for e in "$@"; do
     i=$((i+1))
-    env $e timeout -k 10 400 python bench.py --log-n 16 --sizes "" --no-cpu-baseline --derive-lagrange-upto 18 --cpu-fast-upto -1 --steps 4 > $O/p_${i}_$rep.json 2> $O/p_${i}_$rep.err || { tail -5 $O/p_${i}_$rep.err; exit 1; }
+    env $e timeout -k 10 400 python bench.py --full --log-n 16 --sizes "" --no-cpu-baseline --derive-lagrange-upto 18 --cpu-fast-upto -1 --steps 4 > $O/p_${i}_$rep.json 2> $O/p_${i}_$rep.err || { tail -5 $O/p_${i}_$rep.err; exit 1; }
     python -c "
 import json
 d=json.load(open('$O/p_${i}_$rep.json')); w=[x for x in d['other_workloads'] if 'pinocchio' in x['workload']][0]

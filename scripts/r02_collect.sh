@@ -5,11 +5,11 @@ set -o pipefail
 TAG=$1; shift
 O=gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-BARGS="--headline-only --no-cpu-baseline --no-parity-gate --derive-lagrange-upto ${DERIVE:--1} ${LOGN:+--log-n $LOGN}"      # LOGN=20 scripts/r02_collect.sh ... for the other sizes
+BARGS="--full --headline-only --no-cpu-baseline --no-parity-gate --derive-lagrange-upto ${DERIVE:--1} ${LOGN:+--log-n $LOGN}"      # LOGN=20 scripts/r02_collect.sh ... for the other sizes
 for st in "$@"; do
   case $st in
     tests) echo "== gpu tests"; timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1 || { tail -30 $O/pytest_gpu.log; exit 1; }; tail -3 $O/pytest_gpu.log;;
-    bench) echo "== bench"; timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }; cut -c1-600 $O/bench.json;;
+    bench) echo "== bench"; timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }; cut -c1-600 $O/bench.json;;
     stats) echo "== rocprofv3 stats"
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python bench.py $BARGS > $O/bench_under_rocprofv3.json 2> $O/stats.err || { tail -20 $O/stats.err; exit 1; }
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -o run -- python bench.py $BARGS --inflight 1 --steps 1 --proofs-per-step 10 --warmup 0 > $O/bench1_under_rocprofv3.json 2> $O/stats1.err || { tail -20 $O/stats1.err; exit 1; };;

@@ -8,7 +8,7 @@ TAG=$1; shift
 LN=${LOGN:-20}
 O=gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-BARGS="--headline-only --derived-only --no-cpu-baseline --no-parity-gate --cpu-fast-upto -1 --log-n $LN"
+BARGS="--full --headline-only --derived-only --no-cpu-baseline --no-parity-gate --cpu-fast-upto -1 --log-n $LN"
 ONE="--inflight 1 --steps 1 --proofs-per-step 6 --warmup 0 --settle 0"
 for st in "$@"; do
   case $st in

@@ -5,7 +5,7 @@ set -o pipefail
 TAG=$1; LN=$2; shift; shift
 O=gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-ARGS="--headline-only --no-cpu-baseline --no-parity-gate --cpu-fast-upto -1 --derive-lagrange-upto -1 --log-n $LN --inflight 1 --steps 1 --proofs-per-step 3 --warmup 0 --settle 0"
+ARGS="--full --headline-only --no-cpu-baseline --no-parity-gate --cpu-fast-upto -1 --derive-lagrange-upto -1 --log-n $LN --inflight 1 --steps 1 --proofs-per-step 3 --warmup 0 --settle 0"
 i=0
 for grp in "$@"; do
   i=$((i+1))

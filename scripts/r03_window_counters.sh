@@ -8,7 +8,7 @@ TAG=$1; shift
 WIDTHS=${@:-14 16 18 20}
 O=gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-BARGS="--headline-only --no-cpu-baseline --cpu-fast-upto -1 --derive-lagrange-upto -1 --log-n 20"
+BARGS="--full --headline-only --no-cpu-baseline --cpu-fast-upto -1 --derive-lagrange-upto -1 --log-n 20"
 ONE="--no-parity-gate --inflight 1 --steps 1 --proofs-per-step 4 --warmup 0 --settle 0"
 for c in $WIDTHS; do
   export ZK_MSM_WINDOW=$c

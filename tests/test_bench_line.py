@@ -89,3 +89,28 @@ def test_bench_parses_its_arguments_and_prints_its_help():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0 and "--gpus" in res.stdout and "--steps" in res.stdout and "--warmup" in res.stdout, res.stderr[-2000:]
+
+
+def test_dump_outputs_writes_the_last_step_proofs_as_exact_float32(tmp_path):
+    """--dump-outputs: one row per proof of the last timed step, every byte of a | b | c as a float32 (exact), in the order the step made them."""
+    import numpy as np
+    from zukelang_amd.groth16 import Proof
+    b = _bench()
+    rng = np.random.default_rng(7)
+    proofs = [Proof(*(bytes(rng.integers(0, 256, k, dtype=np.uint8)) for k in (96, 192, 96))) for _ in range(5)]
+    b.dump_outputs(str(tmp_path / "out"), proofs)
+    total = 0
+    for name, width in (("a", 96), ("b", 192), ("c", 96)):
+        path = tmp_path / "out" / ("proof_%s.npy" % name)
+        arr = np.load(path)
+        total += path.stat().st_size
+        assert arr.dtype == np.float32 and arr.shape == (5, width)
+        assert [bytes(row.astype(np.uint8)) for row in arr] == [getattr(p, name) for p in proofs]
+    assert total < 64 << 20
+
+
+def test_bench_help_names_the_full_and_dump_outputs_options():
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and "--full" in res.stdout and "--dump-outputs" in res.stdout, res.stderr[-2000:]

@@ -78,7 +78,7 @@ def test_bench_gpus_2_starts_its_own_two_ranks():
     the card and exchange over gloo (rehearsal); the line must say n_gpus 2, carry the parity gate's verdict and the proof of groth16.ml:123-161
     must not depend on N (the gate compares with the oracle's trapdoor evaluation, which knows nothing of ranks)."""
     import json
-    res = _bench(["--gpus", "2", "--log-n", "12", "--steps", "2", "--warmup", "1", "--settle", "0", "--config4-world", "2", "--config4-log-n", "10"])
+    res = _bench(["--full", "--gpus", "2", "--log-n", "12", "--steps", "2", "--warmup", "1", "--settle", "0", "--config4-world", "2", "--config4-log-n", "10"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -96,11 +96,11 @@ def test_bench_gpus_2_starts_its_own_two_ranks():
 
 @pytest.mark.gpu
 def test_bench_line_of_a_real_one_gpu_run_is_compact_and_complete():
-    """The N = 1 line as the driver reads it (round-3 verdict: `parsed` was null for a 24 KB line): one real run at 2^12 with every leg the default run has
+    """The N = 1 line as the driver reads it (round-3 verdict: `parsed` was null for a 24 KB line): one real --full run at 2^12 with every leg that run has
     (tau-power pass, derivation, derived pass, a second workload, Pinocchio off, the cpu_baseline ladder cut short) -- the LAST stdout line is < 4 KB of
     strict JSON carrying `roofline` and `cpu_baseline`, and bench_detail.json holds the long form."""
     import json
-    res = _bench(["--log-n", "12", "--steps", "2", "--warmup", "1", "--settle", "0", "--sizes", "10", "--dense-rows", "10", "--no-pinocchio", "--cpu-baseline-budget", "1"])
+    res = _bench(["--full", "--log-n", "12", "--steps", "2", "--warmup", "1", "--settle", "0", "--sizes", "10", "--dense-rows", "10", "--no-pinocchio", "--cpu-baseline-budget", "1"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     last = [ln for ln in res.stdout.splitlines() if ln.strip()][-1]
     assert len(last) < 4096
@@ -119,12 +119,40 @@ def test_bench_line_of_a_real_one_gpu_run_is_compact_and_complete():
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_only_and_dumps_the_proofs_full_checks(tmp_path):
+    """A plain run (no --full) times the headline and nothing else: the key's Lagrange form comes from the keygen, no parity gate, no other workload.
+    Its --dump-outputs are the proofs of the last timed step; the --full run of the same arguments derives that form on the device and holds its last
+    timed proof to the oracle -- the two dumps must be the same bytes."""
+    import json
+    import numpy as np
+    common = ["--log-n", "12", "--steps", "3", "--warmup", "1", "--settle", "0", "--proofs-per-step", "4", "--inflight", "3"]
+    plain = _bench(common + ["--dump-outputs", str(tmp_path / "plain")])
+    assert plain.returncode == 0, plain.stdout[-2000:] + plain.stderr[-4000:]
+    d = json.loads([ln for ln in plain.stdout.splitlines() if ln.strip()][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "constraints/s" and d["dtype"] == "u32"
+    assert abs(d["ms_per_step"] - 4 * d["ms_per_proof"]) / d["ms_per_step"] < 1e-3
+    assert d["config"]["key_form"] == "lagrange_form_from_keygen_same_pools_as_derived" and d["config"]["run"].startswith("plain")
+    assert d["parity"] == "skipped" and d["roofline"] is None and d["cpu_baseline"] is None and d["other_workloads"] == []
+    full = _bench(["--full"] + common + ["--headline-only", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert full.returncode == 0, full.stdout[-2000:] + full.stderr[-4000:]
+    f = json.loads([ln for ln in full.stdout.splitlines() if ln.strip()][-1])
+    assert f["parity"].startswith("passed") and f["config"]["key_form"] == "tau_powers_uploaded_lagrange_derived_on_device"
+    for name, width in (("a", 96), ("b", 192), ("c", 96)):
+        p, q = np.load(tmp_path / "plain" / ("proof_%s.npy" % name)), np.load(tmp_path / "full" / ("proof_%s.npy" % name))
+        assert p.dtype == np.float32 and p.shape == (4, width) and np.array_equal(p, q)
+    last = bytes(np.concatenate([np.load(tmp_path / "full" / ("proof_%s.npy" % x))[-1] for x in "abc"]).astype(np.uint8))
+    detail = json.load(open(os.path.join(ROOT, "bench_detail.json")))
+    from zukelang_amd.curve import G1, G2
+    assert G1.to_compressed_bytes(last[:96]) + G2.to_compressed_bytes(last[96:288]) + G1.to_compressed_bytes(last[288:]) == bytes.fromhex(detail["proof_compressed_hex"])
+
+
+@pytest.mark.gpu
 def test_bench_device_list_runs_the_one_process_multi_device_path():
     """`python bench.py --device-list 0,0`: ONE process, one key handle sharded over two entries of the device list (the path an OCaml host takes:
     zk_set_device_list, csrc/groth16_multi.hip) -- both entries are the one card of the test box, so the line must call itself a rehearsal; the parity
     gate compares the last timed proof with the oracle's trapdoor evaluation (groth16.ml:123-161: the bytes do not depend on how the sums are cut)."""
     import json
-    res = _bench(["--device-list", "0,0", "--log-n", "12", "--steps", "2", "--warmup", "1", "--settle", "0", "--headline-only", "--no-cpu-baseline"])
+    res = _bench(["--full", "--device-list", "0,0", "--log-n", "12", "--steps", "2", "--warmup", "1", "--settle", "0", "--headline-only", "--no-cpu-baseline"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][-1])
     assert d["n_gpus"] == 1 and d["config"]["device_list"] == [0, 0] and d["config"]["rehearsal_ranks_share_gpus"] is True
