@@ -20,7 +20,7 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rnd = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 12345)
 frb = P.fr_to_bytes
 t_end = time.time() + budget
-n_msm = n_g16 = n_pin = n_der = n_ba = n_multi = n_rns = n_sort = n_pin_multi = n_dec = 0
+n_msm = n_g16 = n_pin = n_der = n_ba = n_multi = n_rns = n_sort = n_pin_multi = n_pin_ba = n_dec = 0
 _lib.check(_lib.lib().zk_init(0))
 while time.time() < t_end:
     # ---- MSM with duplicates, negations, identity, tiny / huge / zero scalars
@@ -154,6 +154,10 @@ while time.time() < t_end:
         opts = {"ZK_PIN_COMPACT_H": "0" if n_pin % 3 == 1 else None, "ZK_PIN_SHARED_SORT": "0" if n_pin % 3 == 2 else None}
         for k_, v_ in opts.items():
             _lib.check(_lib.lib().zk_set_option(k_.encode(), None if v_ is None else v_.encode()))
+        # every second case (half of them derived): batch-affine rounds in the slots' workspaces (read when a slot is set up, i.e. at the first proof and again after the
+        # derivation), with the shared sorts on or off as above; set from the upload to the last proof of the case
+        pin_ba = str(rnd.choice([1, 2, 4])) if n_pin % 4 in (1, 2) else None
+        _lib.check(_lib.lib().zk_set_option(b"ZK_MSM_BA_ROUNDS", None if pin_ba is None else pin_ba.encode()))
         if n_pin % 5 == 4:
             os.environ["ZK_FR_RNS"] = "1"
         pin_devs = [0] * rnd.choice([2, 3, 4]) if n_pin % 4 == 3 else None          # round 5: every fourth case behind a device list (csrc/pinocchio.hip, PinGroup)
@@ -176,7 +180,7 @@ while time.time() < t_end:
         proof = prover.prove(lambda: next(it), w)
         csr = [O.CSR(M.ptr, M.col, M.val) for M in (cs.L, cs.R, cs.O)]
         exp = O.pinocchio_prove_trapdoor(cs.n, cs.m, *csr, cs.mid, b"".join(frb(x) for x in w), b"".join(frb(x) for x in tox[:8]), *(frb(x) for x in tox[8:]))
-        assert proof.to_bytes() == exp, ("Pinocchio mismatch", n)
+        assert proof.to_bytes() == exp, ("Pinocchio mismatch", n, pin_ba)
         if n_pin % 2 == 0:
             # round 2: the h pool rewritten on the device ([lambda_t(s)], zk_pinocchio_pk_derive_lagrange) proves the same bytes
             prover.derive_lagrange()
@@ -186,6 +190,9 @@ while time.time() < t_end:
         prover.close()
         if pin_devs:
             _lib.set_device_list([0])
+        if pin_ba:
+            _lib.check(_lib.lib().zk_set_option(b"ZK_MSM_BA_ROUNDS", None))
+            n_pin_ba += 1
         os.environ.pop("ZK_FR_RNS", None)          # set for every fifth case from the upload to the last proof (the switch is read per call under ZK_TEST_FORMS)
         n_pin += 1
     # ---- every eighth round: a list of compressed points (valid, the identity, sometimes one bad one) through the GPU decompression against the host function
@@ -216,5 +223,5 @@ while time.time() < t_end:
         n_dec += 1
     if (n_msm % 10) == 0:
         print("soak: %d MSM cases, %d Groth16 cases (%d multi-device, %d RNS), %d Pinocchio cases ok" % (n_msm, n_g16, n_multi, n_rns, n_pin), flush=True)
-print("SOAK-OK msm=%d groth16=%d (of them %d with the derived Lagrange form, %d with batch-affine rounds, %d behind a multi-device handle, %d through the residue number system, %d through the forced two-level sort in its plain / staged forms) pinocchio=%d (%d of them behind a device list) decompressed_lists=%d"
-      % (n_msm, n_g16, n_der, n_ba, n_multi, n_rns, n_sort, n_pin, n_pin_multi, n_dec))
+print("SOAK-OK msm=%d groth16=%d (of them %d with the derived Lagrange form, %d with batch-affine rounds, %d behind a multi-device handle, %d through the residue number system, %d through the forced two-level sort in its plain / staged forms) pinocchio=%d (%d of them behind a device list, %d with batch-affine rounds) decompressed_lists=%d"
+      % (n_msm, n_g16, n_der, n_ba, n_multi, n_rns, n_sort, n_pin, n_pin_multi, n_pin_ba, n_dec))

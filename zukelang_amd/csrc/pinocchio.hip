@@ -83,6 +83,8 @@ struct PinKey {
     // (pinocchio.ml:438-447,489-498).  share1[i] / share2[i] = the pool whose sorted references pool i's bucket accumulation reads, -1 = its own: set at
     // upload when the two base sets have the same geometry AND the same identity flags (msm_bases_same_geometry; v_k = 0 makes both of a pair the identity).
     int share1[PIN_G1] = {-1, -1, -1, -1, -1, -1}, share2[PIN_G2] = {-1, -1};
+    bool in_subgroup = true;            // the upload's verdict on ZK_KEY_SUBGROUP_CHECK, read once: were this key's points checked -- for every pool built
+                                        // from them, the derived h pool too (a shard whose slice was empty at upload has no MsmBases to ask)
     bool compact = false;               // pool 5 without v_all | w_all: si (n+1), or derived [lambda_t(s)] (n-1) | [Z(s)] | [1] | [s^(n-1)]  (header comment)
     DevBuf pw;                          // compact + derived: (n + t)^(n-1), t < n - 1
     std::unique_ptr<PinSlot> slots[PIN_MAX_SLOTS];
@@ -260,6 +262,7 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
     auto key = std::make_unique<PinKey>();
     PinKey& k = *key;
     k.n = n; k.m = m; k.rank = rank; k.world = world;
+    k.in_subgroup = key_subgroup_check();
     std::vector<uint32_t> mids;
     for (uint32_t i = 0; i < m; i++)
         if (mid[i]) mids.push_back(i);
@@ -287,7 +290,7 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
             if (e >= lo && e < hi) buf.insert(buf.end(), x, x + 96);
             e++;
         }
-        return msm_bases_from_bytes(k.g1[idx], CURVE_G1, buf.data(), buf.size() / 96, 0, true, c.stream, key_subgroup_check());
+        return msm_bases_from_bytes(k.g1[idx], CURVE_G1, buf.data(), buf.size() / 96, 0, true, c.stream, k.in_subgroup);
     };
     ZKCHK(pool1(0, VV, nm, {ONES + 96 * 0}));
     ZKCHK(pool1(1, YY, nm, {ONES + 96 * 1}));
@@ -300,7 +303,7 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
     if (compact_in < 0 && pin_compact_wanted()) {
         // every point is decoded and checked as before (of_bytes_exn); the pool then keeps v_all | w_all only if they fail the check of the header comment
         MsmBases full;
-        ZKCHK(msm_bases_from_bytes(full, CURVE_G1, SI, ph_full, 0, false, c.stream, key_subgroup_check()));
+        ZKCHK(msm_bases_from_bytes(full, CURVE_G1, SI, ph_full, 0, false, c.stream, k.in_subgroup));
         bool ok = false;
         ZKCHK(pin_compact_check(k.fr, full, n, m, &ok, c.stream));
         compact = ok ? 1 : 0;
@@ -315,7 +318,7 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
         buf.clear();
         if (lo < nm) buf.assign(base + 192 * lo, base + 192 * (hi < nm ? hi : nm));
         if (hi == nm + 1) buf.insert(buf.end(), extra, extra + 192);
-        return msm_bases_from_bytes(k.g2[idx], CURVE_G2, buf.data(), buf.size() / 192, 0, true, c.stream, key_subgroup_check());
+        return msm_bases_from_bytes(k.g2[idx], CURVE_G2, buf.data(), buf.size() / 192, 0, true, c.stream, k.in_subgroup);
     };
     ZKCHK(pool2(0, WW, ONES2));
     ZKCHK(pool2(1, WAW, ONES2 + 192));
@@ -385,7 +388,7 @@ static int pin_install_derived(PinKey& k, const uint8_t* d_pool, hipStream_t s) 
     uint64_t lo, hi;
     pin_slice(ph, k.rank, k.world, &lo, &hi);
     MsmBases nb;
-    if (hi > lo) ZKCHK(msm_bases_from_device_affine(nb, CURVE_G1, d_pool + 96 * lo, hi - lo, old.n ? old.c : 0, true, s, old.n ? old.in_subgroup : key_subgroup_check()));   // derived from checked points: msm.cuh, msm_fold
+    if (hi > lo) ZKCHK(msm_bases_from_device_affine(nb, CURVE_G1, d_pool + 96 * lo, hi - lo, old.n ? old.c : 0, true, s, k.in_subgroup));   // derived from checked points: msm.cuh, msm_fold
     if (k.compact) {
         ZKCHK(k.pw.alloc(32 * (size_t)(n > 1 ? n - 1 : 1)));
         ZKCHK(frstage_shifted_powers(k.pw.p, n, n - 1, n - 1, s));
@@ -499,17 +502,19 @@ static int pin_msms_enqueue(PinKey& k, PinSlot& sl, bool raw) {
     // window plan go out as ONE mixed G1 / G2 chain of launches (from 2^16 constraints up that is the whole group); one to-bytes launch.
     // G1 products [lo1, hi1), G2 products [lo2, hi2).
     auto group = [&](int lo1, int hi1, int lo2, int hi2, hipStream_t st) -> int {
-        // a pool whose scalar vector another pool of the group has sorted reads that sort (the source has the lower index: it ran first on this stream)
+        // a pool whose scalar vector another pool of the group has sorted reads that sort (the source has the lower index: it ran first on this stream) --
+        // unless a workspace of the pair runs batch-affine rounds (msm_accumulate_sorted refuses that pair): then it sorts the same vector itself.  Decided
+        // here, not at upload: the rounds are chosen when the slot's workspaces are allocated (ZK_MSM_BA_ROUNDS / ZK_MSM_BA_CURVES as they are then).
         for (int i = lo2; i < hi2; i++) {
             if (!k.g2[i].n) { HIPCHK(hipMemsetAsync(res + PIN_G1 * x1 + i * x2, 0, x2, st)); continue; }          // empty slice: the identity
             const int f = k.share2[i];
-            if (f >= lo2 && f < i) { MsmWorkspace *w1[1] = {&sl.ws2[i]}, *f1[1] = {&sl.ws2[f]}; ZKCHK(msm_accumulate_sorted(k.g2[i], w1, f1, 1, st)); }
+            if (f >= lo2 && f < i && !sl.ws2[i].ba_rounds && !sl.ws2[f].ba_rounds) { MsmWorkspace *w1[1] = {&sl.ws2[i]}, *f1[1] = {&sl.ws2[f]}; ZKCHK(msm_accumulate_sorted(k.g2[i], w1, f1, 1, st)); }
             else ZKCHK(msm_sort_accumulate(k.g2[i], sl.ws2[i], f < 0 ? sc2(i) : sc2(f), st));
         }
         for (int i = lo1; i < hi1; i++) {
             if (!k.g1[i].n) { HIPCHK(hipMemsetAsync(res + i * x1, 0, x1, st)); continue; }
             const int f = k.share1[i];
-            if (f >= lo1 && f < i) { MsmWorkspace *w1[1] = {&sl.ws1[i]}, *f1[1] = {&sl.ws1[f]}; ZKCHK(msm_accumulate_sorted(k.g1[i], w1, f1, 1, st)); }
+            if (f >= lo1 && f < i && !sl.ws1[i].ba_rounds && !sl.ws1[f].ba_rounds) { MsmWorkspace *w1[1] = {&sl.ws1[i]}, *f1[1] = {&sl.ws1[f]}; ZKCHK(msm_accumulate_sorted(k.g1[i], w1, f1, 1, st)); }
             else ZKCHK(msm_sort_accumulate(k.g1[i], sl.ws1[i], f < 0 ? sc1(i) : sc1(f), st));
         }
         bool done1[PIN_G1] = {}, done2[PIN_G2] = {};
