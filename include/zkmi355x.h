@@ -101,6 +101,32 @@ int zk_msm_g1(const uint8_t* bases, size_t nbases, const uint8_t* scalars, size_
 int zk_msm_g2(const uint8_t* bases, size_t nbases, const uint8_t* scalars, size_t nscalars,
               uint32_t window_bits, uint8_t out[192]);
 
+/* ---- resident MSM bases: a point list uploaded once, multiplied many times ----------------------
+ * The reference multiplies the SAME list again and again: sum_apply_powers calls G.apply_powers p ti once per variable with one ti
+ * (src/groth16/groth16.ml:116-121), G.dot runs on the same key maps for every proof (curve.ml:94-103).  A handle keeps the list on the
+ * device with its window tables, workspaces and staging buffers, so that a product costs one H2D copy, the launches and one D2H copy.
+ *   group: 0 = G1 (96-byte points), 1 = G2 (192-byte points), the encodings of zk_msm_g1/g2.
+ *   Upload checks every point as the key uploads do (of_bytes_exn, curve.ml:199-212): encoding (ZK_ERR_ARG), curve equation and [r] P = O
+ *   (ZK_ERR_NOT_ON_CURVE); no handle then.  The identity, duplicates and P, -P pairs are allowed.  ZK_KEY_SUBGROUP_CHECK=0 skips the [r] P = O
+ *   part as for keys (and the handle then never uses folded digits); the handle keeps the verdict of its upload.
+ *   zk_msm_resident = G.apply_powers cs xis over the uploaded list (curve.ml:112-118): nscalars > n -> ZK_ERR_APPLY_POWERS (:116), nscalars = 0 ->
+ *   the identity (:115), nscalars < n -> the first nscalars points; a scalar >= r -> ZK_ERR_SCALAR_RANGE (the handle stays usable).  The bytes
+ *   are those of zk_msm_g1/g2 on the same prefix.
+ *   zk_msm_resident_many: `count` such products over the same list; product k takes lens[k] scalars, concatenated in `scalars`; out: count
+ *   points.  Any lens[k] > n -> ZK_ERR_APPLY_POWERS before anything runs; lens[k] = 0 -> the identity.
+ *   Which path a product takes (the bytes are the same either way): when ONE call carries two or more products of 1 .. short_max scalars
+ *   (zk_bases_info, per group), those run in two launches, a bucket kernel over a narrow window table and then the encoding; so does the
+ *   only short product of a call when the list is long against it (length x 2048 < n in G1, x 4096 in G2).  Every other product -- longer
+ *   than short_max, or alone on a shorter list, so most zk_msm_resident calls -- runs the Pippenger chain of zk_msm_g1/g2 over all n points
+ *   of the handle (the scalars past the product's length are zero): its cost follows n, not the length.  Unknown or freed handle -> ZK_ERR_HANDLE.  The handle lives on the first device of the
+ *   list at upload, is called from one host thread like the key handles, and counts as a live key handle for zk_set_devices /
+ *   zk_set_device_list; zk_shutdown frees it. */
+int zk_bases_upload(int group, const uint8_t* points, size_t n, uint64_t* handle);
+int zk_bases_info(uint64_t handle, int* group, uint64_t* n, uint64_t* short_max);   /* any out may be NULL */
+int zk_bases_free(uint64_t handle);
+int zk_msm_resident(uint64_t handle, const uint8_t* scalars, size_t nscalars, uint8_t* out);
+int zk_msm_resident_many(uint64_t handle, const uint8_t* scalars, const uint64_t* lens, uint32_t count, uint8_t* out);
+
 /* G.of_Fr mapped over a vector (G1.one * s_i) -- src/lib/zk/curve.ml:180; the engine of
  * G.powers (curve.ml:106-109) and of keygen (groth16.ml:70-90, pinocchio.ml:104-156). */
 int zk_g1_of_fr(const uint8_t* scalars, size_t n, uint8_t* out /* n*96 */);

@@ -32,16 +32,74 @@ struct
   (* curve.ml:106-109: d + 1 points g^(s^0) .. g^(s^d) *)
   let powers d s = split (Mi355x.powers ~g2 d (Bls12_381.Fr.to_bytes s))
 
+  (* Resident bases (header, "resident MSM bases").  apply_powers memoises a device handle on the PHYSICAL xis list, dot on the physical key
+     map m (never on the fresh list Var.Map.bindings builds): the reference multiplies the same list again and again (sum_apply_powers,
+     groth16.ml:116-121; dot on the key maps of every proof, curve.ml:94-103).  The first call on a list goes through zk_msm_* as before, the
+     second uploads it, every later one multiplies the resident copy.  Ephemeron tables: an entry dies with its key, whose finaliser frees
+     the handle.  The hash is Hashtbl.hash, which looks at a bounded number of words whatever the list's length (List.length is O(n)). *)
+  type memo = Seen | Resident of Unsigned.UInt64.t | Refused
+
+  module By_list = Ephemeron.K1.Make (struct
+    type nonrec t = t list
+
+    let equal = ( == )
+    let hash (k : t) = Hashtbl.hash k
+  end)
+
+  module By_map = Ephemeron.K1.Make (struct
+    type nonrec t = t Var.Map.t
+
+    let equal = ( == )
+    let hash (k : t) = Hashtbl.hash k
+  end)
+
+  let by_list : memo By_list.t = By_list.create 16
+  let by_map : memo By_map.t = By_map.create 16
+
+  (* sum_i c_i x_i over the first (length cs) points of a resident list *)
+  let resident_apply h (cs : Base.Fr.t list) : t =
+    let sc = scalars_bytes cs and out = Bytes.create point_bytes in
+    Mi355x.(check (zk_msm_resident h (bytes_start sc) (sz (Bytes.length sc / 32)) (bytes_start out)));
+    of_bytes_exn out
+
+  (* the handle of `key` if it has one, uploading on the second sight; None: go through zk_msm_* (first sight, or the upload failed) *)
+  let resident ~find ~replace key (points : unit -> bytes) =
+    match find key with
+    | Some (Resident h) -> Some h
+    | Some Refused -> None
+    | None ->
+        replace key Seen;
+        None
+    | Some Seen -> (
+        match Mi355x.resident_upload ~g2 (points ()) with
+        | h ->
+            (try Gc.finalise (fun _ -> Mi355x.resident_free h) key with Invalid_argument _ -> ());
+            replace key (Resident h);
+            Some h
+        | exception _ ->
+            replace key Refused;
+            None)
+
   (* curve.ml:112-118: sum_i c_i x_i; runs out of coefficients quietly, of points with Invalid_argument "apply_powers" *)
   let apply_powers (cs : Base.Fr.t Polynomial.t) (xis : t list) : t =
-    match cs with
-    | [] -> zero
-    | _ -> of_bytes_exn (Mi355x.msm ~g2 (points_bytes xis) (scalars_bytes cs))
+    match cs, xis with
+    | [], _ -> zero
+    | _, [] -> of_bytes_exn (Mi355x.msm ~g2 (points_bytes xis) (scalars_bytes cs))
+    | _ -> (
+        match resident ~find:(By_list.find_opt by_list) ~replace:(By_list.replace by_list) xis (fun () -> points_bytes xis) with
+        | Some h -> resident_apply h cs
+        | None -> of_bytes_exn (Mi355x.msm ~g2 (points_bytes xis) (scalars_bytes cs)))
 
   (* curve.ml:94-103: equal key sets or `assert false` *)
   let dot (m : t Var.Map.t) (c : Base.Fr.t Var.Map.t) : t =
     if not (Var.Set.equal (Var.Map.domain m) (Var.Map.domain c)) then assert false;
-    apply_powers (List.map snd (Var.Map.bindings c)) (List.map snd (Var.Map.bindings m))
+    match List.map snd (Var.Map.bindings c) with
+    | [] -> zero
+    | cs -> (
+        let points () = points_bytes (List.map snd (Var.Map.bindings m)) in
+        match resident ~find:(By_map.find_opt by_map) ~replace:(By_map.replace by_map) m points with
+        | Some h -> resident_apply h cs
+        | None -> of_bytes_exn (Mi355x.msm ~g2 (points ()) (scalars_bytes cs)))
 end
 
 module Fr = Base.Fr

@@ -104,6 +104,24 @@ let msm ~g2 (points : bytes) (scalars : bytes) : bytes =
        (bytes_start out));
   out
 
+(* resident MSM bases (header, "resident MSM bases"): a point list uploaded and checked once, then multiplied many times.  The errors map as
+   for msm: Invalid_argument "apply_powers" when a product is longer than the list (curve.ml:116). *)
+let zk_bases_upload = fn "zk_bases_upload" (int @-> ocaml_bytes @-> size_t @-> ptr uint64_t @-> returning int)
+let zk_bases_info = fn "zk_bases_info" (uint64_t @-> ptr int @-> ptr uint64_t @-> ptr uint64_t @-> returning int)
+let zk_bases_free = fn "zk_bases_free" (uint64_t @-> returning int)
+let zk_msm_resident = fn "zk_msm_resident" (uint64_t @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> returning int)
+
+let zk_msm_resident_many =
+  fn "zk_msm_resident_many" (uint64_t @-> ocaml_bytes @-> ptr uint64_t @-> uint32_t @-> ocaml_bytes @-> returning int)
+
+let resident_upload ~g2 (points : bytes) : Unsigned.UInt64.t =
+  let psize = if g2 then 192 else 96 in
+  let h = allocate uint64_t Unsigned.UInt64.zero in
+  check (zk_bases_upload (if g2 then 1 else 0) (bytes_start points) (sz (Bytes.length points / psize)) h);
+  !@h
+
+let resident_free (h : Unsigned.UInt64.t) = ignore (zk_bases_free h)
+
 (* [g * s_0; g * s_1; ...] for the group's generator g: G.of_Fr mapped over a list (curve.ml:180), one kernel launch *)
 let of_fr_many ~g2 (scalars : bytes) : bytes =
   let psize = if g2 then 192 else 96 in

@@ -1,7 +1,8 @@
 """Host-side mirror of the reference's curve plugin `Curve.S` (src/lib/zk/curve.mli:46-54) for the
 operations on the prove path, backed by the HIP library.  Names and argument meaning follow the
 OCaml modules: `FFT_Fr.fft / ifft / polynomial_mul` (src/lib/zk/FFT.ml:69-105,222-233),
-`G.apply_powers`, `G.dot`, `G.powers`, `G.of_Fr` (src/lib/zk/curve.ml:94-118,180).
+`G.apply_powers`, `G.dot`, `G.powers`, `G.of_Fr` (src/lib/zk/curve.ml:94-118,180); `G1.resident(points)` keeps a point list on the
+device for many `apply_powers` over it, and `sum_apply_powers` mirrors the Groth16 fold built on that (src/groth16/groth16.ml:116-121).
 
 Values cross this layer in the byte formats of include/zkmi355x.h (Fr 32 B LE; G1 96 B, G2 192 B
 uncompressed big-endian).  Error behaviour mirrors the reference: `apply_powers` with fewer
@@ -16,6 +17,7 @@ from . import _lib
 
 FR_BYTES = 32
 ZK_ERR_APPLY_POWERS = -6
+ZK_ERR_HANDLE = -7
 
 
 def _np(buf):
@@ -83,6 +85,11 @@ class _Group:
             raise ValueError("apply_powers")
         _lib.check(rc)
         return out
+
+    @classmethod
+    def resident(cls, points):
+        """Upload `points` (uncompressed, back to back) once: a ResidentBases whose apply_powers(cs) is G.apply_powers cs points."""
+        return ResidentBases(cls, points)
 
     @classmethod
     def dot(cls, m, c, window_bits=0):
@@ -163,6 +170,87 @@ class _Group:
         if n:
             _lib.check(getattr(_lib.lib(), cls._decompress_batch)(_p(c), C.c_size_t(n), _p(out)))
         return bytes(out)
+
+
+class ResidentBases:
+    """A point list resident on the device (include/zkmi355x.h, "resident MSM bases"): uploaded and checked once (encoding, curve, [r] P = O),
+    then multiplied by many scalar vectors.  apply_powers(cs) = G.apply_powers cs points (curve.ml:112-118) over the first len(cs) points;
+    apply_powers_many([cs_0, cs_1, ...]) runs them all in one call.  Free with close() (or a `with` block); dropping the object frees it too."""
+
+    def __init__(self, group, points):
+        self.group = group
+        self.handle = None
+        p = _np(points)
+        n = len(p) // group.POINT_BYTES
+        if len(p) != n * group.POINT_BYTES:
+            raise ValueError("resident bases: length is not a multiple of the point size")
+        h = C.c_uint64()
+        _lib.check(_lib.lib().zk_bases_upload(C.c_int(0 if group.POINT_BYTES == 96 else 1), _p(p), C.c_size_t(n), C.byref(h)))
+        self.handle = h.value
+        nn, sm = C.c_uint64(), C.c_uint64()
+        _lib.check(_lib.lib().zk_bases_info(C.c_uint64(self.handle), None, C.byref(nn), C.byref(sm)))
+        self.n, self.short_max = nn.value, sm.value
+
+    def _check(self, rc):
+        if rc == ZK_ERR_APPLY_POWERS:
+            raise ValueError("apply_powers")
+        _lib.check(rc)
+
+    def _live(self):
+        if self.handle is None:
+            raise _lib.ZkError(ZK_ERR_HANDLE, "resident bases already closed")
+        return C.c_uint64(self.handle)
+
+    def apply_powers(self, cs):
+        c = _np(cs)
+        out = np.zeros(self.group.POINT_BYTES, dtype=np.uint8)
+        self._check(_lib.lib().zk_msm_resident(self._live(), _p(c), C.c_size_t(len(c) // FR_BYTES), _p(out)))
+        return out
+
+    def apply_powers_many(self, list_of_cs):
+        arrs = [_np(cs) for cs in list_of_cs]
+        k = len(arrs)
+        lens = (C.c_uint64 * max(1, k))(*[len(a) // FR_BYTES for a in arrs])
+        sc = np.concatenate(arrs) if k else np.zeros(0, dtype=np.uint8)
+        if not len(sc):
+            sc = np.zeros(FR_BYTES, dtype=np.uint8)
+        out = np.zeros(max(1, k) * self.group.POINT_BYTES, dtype=np.uint8)
+        self._check(_lib.lib().zk_msm_resident_many(self._live(), _p(sc), lens, C.c_uint32(k), _p(out)))
+        return [out[i * self.group.POINT_BYTES:(i + 1) * self.group.POINT_BYTES] for i in range(k)]
+
+    def close(self):
+        """Frees the device copy.  A handle that zk_shutdown already freed (ZK_ERR_HANDLE) counts as closed."""
+        if self.handle is not None:
+            h, self.handle = self.handle, None
+            rc = _lib.lib().zk_bases_free(C.c_uint64(h))
+            if rc != ZK_ERR_HANDLE:
+                _lib.check(rc)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sum_apply_powers(G, ti, ps, w):
+    """sum_apply_powers (src/groth16/groth16.ml:116-121): sum over the keys k of w of (G.apply_powers ps[k] ti) * w[k].  ps, w: dicts keyed by
+    variable (or equal-length sequences); ps[k] the coefficients (32-byte Fr, back to back), w[k] one Fr.  One resident upload of ti, one
+    apply_powers_many over every ps[k], one multi-scalar product of the K results by the w[k]."""
+    keys = sorted(w) if isinstance(w, dict) else range(len(w))
+    if isinstance(w, dict) and not set(w) <= set(ps):
+        raise KeyError("sum_apply_powers: a key of w has no polynomial in ps")
+    if not len(keys):
+        return G.apply_powers(b"", b"")
+    with G.resident(ti) as rb:
+        parts = rb.apply_powers_many([ps[k] for k in keys])
+    return G.apply_powers(b"".join(bytes(w[k]) for k in keys), b"".join(p.tobytes() for p in parts))
 
 
 class G1(_Group):
