@@ -8,7 +8,8 @@
  *   Fr      32 B little-endian canonical integer < r            (Bls12_381.Fr.to_bytes)
  *   G1      96 B uncompressed ZCash big-endian x || y           (G1.to_bytes, curve.ml:161)
  *   G2     192 B uncompressed x1 || x0 || y1 || y0              (G2.to_bytes)
- *   infinity: first byte 0x40, rest zero.
+ *   infinity: first byte 0x40, rest zero -- the ONE encoding of the identity: every decoder (uncompressed and compressed, host and device) refuses a
+ *   string whose infinity bit is set next to the sign bit, another bit of the first byte or a non-zero byte anywhere (ZK_ERR_ARG).
  *   Compressed outputs (48 B / 96 B) carry the 0x80 / 0x40 / 0x20 flag bits of
  *   to_compressed_bytes (curve.ml:199,208) -- the JSON form of proofs (groth16.ml:110-114).
  *
@@ -300,12 +301,16 @@ int zk_groth16_combine_device(const void* d_partials /* device */, size_t stride
  *   g2: ww | waw (n_mid each) | si2 (n+1, not used by the prover) | wt | wawt
  * zk_pinocchio_prove = ZKCompute.f (:427-514) with dv, dw, dy supplied in the order the reference draws
  * them (:428-430); all three zero gives Compute.f (:210-248), i.e. NonZK.prove.
+ * Precondition: si[0] is the G1 generator (ZK_ERR_ARG otherwise).  ZKCompute.f subtracts `one * dy` with G1.one (:485), not a point of the key, and
+ * the library lets that term ride on si[0]; every key KeyGen.generate makes has si[0] = [s^0] = one.  No other relation between key points is assumed.
  * proof: vv (G1) | ww (G2) | yy | h | vavv | waww (G2) | yayy | bvwy = 960 B uncompressed, the field order
  * of Compute.proof (:195-208).  ZK_ERR_REMAINDER as for Groth16.
  * The h product's points v_all | w_all carry the blinding terms sum_k (dw c_k) [v_k(s)] + sum_k (dv c_k) [w_k(s)] (:481-486) = dw [v(s)] + dv [w(s)]
  * with v = sum_k c_k v_k, w = sum_k c_k w_k -- the polynomials QAP.eval builds anyway.  At upload the library checks v_all / w_all against the
  * key's own powers (<v_all, rho> = <si, coefficients of sum_k rho_k v_k> for a pseudo-random rho, likewise w_all: true of every key
- * KeyGen.generate makes, :104-109,140-147) and then lets the two terms ride on si: the COMPACT h pool, n + 1 points instead of n + 1 + 2 m, same
+ * KeyGen.generate makes, :104-109,140-147; rho is seeded from a digest of the uploaded si | v_all | w_all bytes and from entropy drawn once per process,
+ * so it cannot be known when a key is written -- the check promises the compact pool only to keys that satisfy the relation, up to the 2^-64 of the
+ * seed; it does not validate a key in any other respect) and then lets the two terms ride on si: the COMPACT h pool, n + 1 points instead of n + 1 + 2 m, same
  * proof bytes.  A key that fails the check, or any key under zk_set_option("ZK_PIN_COMPACT_H", "0"), keeps the full pool and is used point by
  * point as ZKCompute.f uses it.  Products that carry the SAME scalar vector -- vv|vt and vav|vavt, yy|yt and yay|yayt, ww|wt and waw|wawt (:438-447,
  * 489-498) -- share one counting sort of it when their base sets have the same identity pattern (true of generated keys; decided per key at upload;
@@ -373,6 +378,11 @@ int zk_bench_field_mul(int kind, uint32_t iters, double* gmul_per_s);
  * integers) the device evaluates 23 base-field expressions through the lazy-reduction code paths of the group law and
  * returns them fully reduced (23 x 48 B per pair, little-endian); pairs (2k, 2k+1) also act as one Fp2 operand pair. */
 int zk_selftest_fp(const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
+/* Square roots as the decompression kernels take them (tests/test_gpu_field.py): n elements of Fp (field 0: 48 B big-endian each) or Fp2 (field 1:
+ * 96 B each, imaginary part | real part, the order of a G2 coordinate on the wire), one lane per element.  is_square[i] = 1 / 0; root[i] = of the two
+ * roots the one the ZCash sign rule calls the larger (Fp2: by the imaginary part, by the real part when that is zero) -- decided by the same device
+ * function as the sign bit of zk_g1/g2_decompress_batch -- and zeros when there is none.  An element >= p -> ZK_ERR_ARG. */
+int zk_selftest_sqrt(int field, const uint8_t* a, size_t n, uint8_t* root, uint8_t* is_square);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -253,6 +253,196 @@ def g2_compress(pt):
     return bytes(out)
 
 
+# ---------------------------------------------------------------- decoders (ZCash BLS12-381 serialization rules)
+# The rules below are taken from the TEXT of the ZCash serialization convention (the one the header of this file cites: three flag bits in the
+# most significant byte -- 0x80 compression, 0x40 infinity, 0x20 sign), NOT observed from the reference: its decoder is the C library behind
+# Bls12_381.G1/G2.of_bytes_exn / of_compressed_bytes_exn (curve.ml:199-212), which cannot be run here.  Rules:
+#   * the compression bit must match the form that is being read;
+#   * infinity bit set => every other bit of the string is zero, the sign bit included;
+#   * the sign bit is only meaningful in the compressed form: it must be zero in an uncompressed string;
+#   * every coordinate is a canonical integer < p;
+#   * compressed: y = the root of x^3 + b that is lexicographically larger iff the sign bit is set (Fp2: imaginary part first, the real part
+#     if the imaginary part is zero -- the rule of g2_compress above);
+#   * the point lies in the subgroup of order r: [r] P = O.
+OK, BAD_ENCODING, NOT_ON_CURVE, NOT_IN_SUBGROUP = "ok", "bad encoding", "not on the curve", "not in the subgroup"
+
+
+def fp_sqrt(a):
+    """A square root of a in Fp (p = 3 mod 4: a^((p+1)/4)), the LARGER of the two (> (p-1)/2; 0 for a = 0), or None if a is not a square."""
+    a %= P
+    y = pow(a, (P + 1) // 4, P)
+    if y * y % P != a:
+        return None
+    return max(y, (P - y) % P)
+
+
+def _fp2_is_larger(y):
+    """y lexicographically larger than -y: imaginary part first, real part when it is zero."""
+    ny = -y
+    return (y.b, y.a) > (ny.b, ny.a)
+
+
+def fp2_sqrt(a):
+    """The lexicographically larger square root of a in Fp2 = Fp[u]/(u^2 + 1), or None.  Written from the norm equation, with Euler's criterion
+    instead of trial roots: if y = y0 + y1 u and y^2 = a0 + a1 u then y0^2 - y1^2 = a0, 2 y0 y1 = a1 and N(y) = y0^2 + y1^2 = +-sqrt(N(a))."""
+    if a.is_zero():
+        return Fp2(0, 0)
+    euler = lambda v: pow(v % P, (P - 1) // 2, P)          # 1: non-zero square, P - 1: non-square, 0: zero
+    if a.b == 0:
+        if euler(a.a) == 1:
+            y = Fp2(pow(a.a, (P + 1) // 4, P), 0)
+        else:                                               # -1 is a non-residue: -a0 is a square and the root is purely imaginary
+            y = Fp2(0, pow(-a.a % P, (P + 1) // 4, P))
+    else:
+        norm = (a.a * a.a + a.b * a.b) % P
+        if euler(norm) != 1:
+            return None
+        s = pow(norm, (P + 1) // 4, P)
+        half = fp_inv(2)
+        t = (a.a + s) * half % P                           # y0^2 is (a0 + s)/2 or (a0 - s)/2: their product is -a1^2/4, a non-square, so exactly one is a square
+        if euler(t) != 1:
+            t = (a.a - s) * half % P
+        y0 = pow(t, (P + 1) // 4, P)
+        y = Fp2(y0, a.b * fp_inv(2 * y0))
+    if not (y * y == a):
+        return None
+    return y if _fp2_is_larger(y) else -y
+
+
+def pt_mul_jac(pt, k):
+    """k*pt like pt_mul, in Jacobian coordinates (a = 0 formulas of the Explicit-Formulas Database: dbl-2009-l, madd-2007-bl without its
+    shortcuts) with ONE inversion at the end: the decoders' [r] P = O over a few thousand strings.  tests/test_oracle.py pins it to pt_mul."""
+    if pt is None or k == 0:
+        return None
+    px, py = pt
+    one = Fp1(1) if isinstance(px, Fp1) else Fp2(1)
+    X = Y = Z = None                                        # None: the identity
+    for bit in bin(k)[2:]:
+        if X is not None:
+            if Y.is_zero():
+                X = None
+            else:
+                A, Bq = X * X, Y * Y
+                Cq = Bq * Bq
+                D = 2 * ((X + Bq) * (X + Bq) - A - Cq)
+                E = 3 * A
+                X3 = E * E - 2 * D
+                X, Y, Z = X3, E * (D - X3) - 8 * Cq, 2 * (Y * Z)
+        if bit == "1":
+            if X is None:
+                X, Y, Z = px, py, one
+                continue
+            ZZ = Z * Z
+            H, Rr = px * ZZ - X, py * (Z * ZZ) - Y
+            if H.is_zero():
+                if not Rr.is_zero():
+                    X = None
+                    continue
+                # the running point met pt itself: double it
+                A, Bq = X * X, Y * Y
+                Cq = Bq * Bq
+                D = 2 * ((X + Bq) * (X + Bq) - A - Cq)
+                E = 3 * A
+                X3 = E * E - 2 * D
+                X, Y, Z = X3, E * (D - X3) - 8 * Cq, 2 * (Y * Z)
+                continue
+            HH = H * H
+            HHH, V = H * HH, X * HH
+            X3 = Rr * Rr - HHH - 2 * V
+            X, Y, Z = X3, Rr * (V - X3) - Y * HHH, Z * H
+    if X is None or Z.is_zero():
+        return None
+    zi = Z.inv()
+    zi2 = zi * zi
+    return (X * zi2, Y * (zi2 * zi))
+
+
+def _in_subgroup(pt):
+    return pt_mul_jac(pt, R) is None
+
+
+def _flags(b, size, compressed):
+    """-> (verdict or None, infinity?) after the flag rules; the caller masks the three flag bits off the first coordinate."""
+    if len(b) != size:
+        return BAD_ENCODING, False
+    f = b[0]
+    if bool(f & 0x80) != compressed:
+        return BAD_ENCODING, False
+    if f & 0x40:
+        if f & 0x3F or any(b[1:]):
+            return BAD_ENCODING, True
+        return None, True
+    if not compressed and f & 0x20:
+        return BAD_ENCODING, False
+    return None, False
+
+
+def _checked(pt, b):
+    if not on_curve(pt, b):
+        return NOT_ON_CURVE, None
+    return (OK, pt) if _in_subgroup(pt) else (NOT_IN_SUBGROUP, None)
+
+
+def g1_decompress(b):
+    """48 compressed bytes -> (verdict, point)."""
+    b = bytes(b)
+    v, inf = _flags(b, 48, True)
+    if v or inf:
+        return (v or OK), None
+    x = int.from_bytes(bytes([b[0] & 0x1F]) + b[1:], "big")
+    if x >= P:
+        return BAD_ENCODING, None
+    y = fp_sqrt(x * x * x + 4)
+    if y is None:
+        return NOT_ON_CURVE, None
+    if not (b[0] & 0x20):
+        y = (P - y) % P
+    return _checked((Fp1(x), Fp1(y)), B1)
+
+
+def g2_decompress(b):
+    """96 compressed bytes (x1 | x0) -> (verdict, point)."""
+    b = bytes(b)
+    v, inf = _flags(b, 96, True)
+    if v or inf:
+        return (v or OK), None
+    x1 = int.from_bytes(bytes([b[0] & 0x1F]) + b[1:48], "big")
+    x0 = int.from_bytes(b[48:], "big")
+    if x0 >= P or x1 >= P:
+        return BAD_ENCODING, None
+    x = Fp2(x0, x1)
+    y = fp2_sqrt(x * x * x + B2)
+    if y is None:
+        return NOT_ON_CURVE, None
+    if not (b[0] & 0x20):
+        y = -y
+    return _checked((x, y), B2)
+
+
+def g1_decode(b):
+    """96 uncompressed bytes (x | y) -> (verdict, point)."""
+    b = bytes(b)
+    v, inf = _flags(b, 96, False)
+    if v or inf:
+        return (v or OK), None
+    x, y = (int.from_bytes(b[48 * i:48 * i + 48], "big") for i in range(2))
+    if x >= P or y >= P:
+        return BAD_ENCODING, None
+    return _checked((Fp1(x), Fp1(y)), B1)
+
+
+def g2_decode(b):
+    """192 uncompressed bytes (x1 | x0 | y1 | y0) -> (verdict, point)."""
+    b = bytes(b)
+    v, inf = _flags(b, 192, False)
+    if v or inf:
+        return (v or OK), None
+    x1, x0, y1, y0 = (int.from_bytes(b[48 * i:48 * i + 48], "big") for i in range(4))
+    if max(x0, x1, y0, y1) >= P:
+        return BAD_ENCODING, None
+    return _checked((Fp2(x0, x1), Fp2(y0, y1)), B2)
+
+
 def fr_to_bytes(a):
     return int(a % R).to_bytes(32, "little")
 

@@ -20,7 +20,7 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rnd = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 12345)
 frb = P.fr_to_bytes
 t_end = time.time() + budget
-n_msm = n_g16 = n_pin = n_der = n_ba = n_multi = n_rns = n_sort = n_pin_multi = n_pin_ba = n_dec = 0
+n_msm = n_g16 = n_pin = n_der = n_ba = n_multi = n_rns = n_sort = n_pin_multi = n_pin_ba = n_dec = n_crafted = 0
 _lib.check(_lib.lib().zk_init(0))
 while time.time() < t_end:
     # ---- MSM with duplicates, negations, identity, tiny / huge / zero scalars
@@ -193,6 +193,23 @@ while time.time() < t_end:
         if pin_ba:
             _lib.check(_lib.lib().zk_set_option(b"ZK_MSM_BA_ROUNDS", None))
             n_pin_ba += 1
+        if n_pin % 4 == 0:
+            # keys crafted against a rho anybody can compute (tests/test_gpu_pinocchio.py: compensating changes on v_all / w_all that the fixed-seed check of
+            # rounds 1-5 could not see), on a small random circuit: the full pool stays and the proof is the literal oracle's on the crafted bytes
+            from test_gpu_pinocchio import crafted_keys
+            n_c = rnd.randrange(2, 40)
+            cs_c, w_c = RC.random_r1cs(n_c, rnd.randrange(8, 8 + 2 * n_c), rnd.randrange(1 << 30), nnz=(1, 3))
+            if sum(1 for x in w_c if x % P.R) >= 3:
+                it_c = iter([rnd.randrange(1, P.R) for _ in range(8)])
+                pk_c, _ = PIN.ZK.keygen(lambda: next(it_c), cs_c)
+                q_c = O.QAP(cs_c.n, cs_c.m, *[O.CSR(M.ptr, M.col, M.val) for M in (cs_c.L, cs_c.R, cs_c.O)])
+                for name_c, key_c in crafted_keys(cs_c, w_c, pk_c).items():
+                    pr_c = PIN.ZK(cs_c, key_c)
+                    assert pr_c.pool_size(5) == cs_c.n + 1 + 2 * cs_c.m, ("a crafted key got the compact h pool", name_c, n_c)
+                    rc_c, ref_c = O.pinocchio_prove(q_c, bytes(key_c.g1), bytes(key_c.g2), cs_c.mid, b"".join(frb(x) for x in w_c), *(frb(x) for x in tox[8:]))
+                    assert rc_c == 0 and pr_c.prove_with(w_c, *tox[8:]).to_bytes() == ref_c, ("crafted Pinocchio key mismatch", name_c, n_c)
+                    pr_c.close()
+                n_crafted += 1
         os.environ.pop("ZK_FR_RNS", None)          # set for every fifth case from the upload to the last proof (the switch is read per call under ZK_TEST_FORMS)
         n_pin += 1
     # ---- every eighth round: a list of compressed points (valid, the identity, sometimes one bad one) through the GPU decompression against the host function
@@ -223,5 +240,5 @@ while time.time() < t_end:
         n_dec += 1
     if (n_msm % 10) == 0:
         print("soak: %d MSM cases, %d Groth16 cases (%d multi-device, %d RNS), %d Pinocchio cases ok" % (n_msm, n_g16, n_multi, n_rns, n_pin), flush=True)
-print("SOAK-OK msm=%d groth16=%d (of them %d with the derived Lagrange form, %d with batch-affine rounds, %d behind a multi-device handle, %d through the residue number system, %d through the forced two-level sort in its plain / staged forms) pinocchio=%d (%d of them behind a device list, %d with batch-affine rounds) decompressed_lists=%d"
-      % (n_msm, n_g16, n_der, n_ba, n_multi, n_rns, n_sort, n_pin, n_pin_multi, n_pin_ba, n_dec))
+print("SOAK-OK msm=%d groth16=%d (of them %d with the derived Lagrange form, %d with batch-affine rounds, %d behind a multi-device handle, %d through the residue number system, %d through the forced two-level sort in its plain / staged forms) pinocchio=%d (%d of them behind a device list, %d with batch-affine rounds) decompressed_lists=%d crafted_pinocchio_keys=%d"
+      % (n_msm, n_g16, n_der, n_ba, n_multi, n_rns, n_sort, n_pin, n_pin_multi, n_pin_ba, n_dec, n_crafted))

@@ -235,3 +235,55 @@ def test_caller_owned_scalar_vectors_are_range_checked():
     for ptr in d:
         _lib.check(L.zk_device_free(ptr))
     pr.close()
+
+
+def test_malformed_identities_are_a_bad_encoding_on_every_entry_that_takes_points():
+    """The identity has ONE uncompressed encoding, 40 00 .. 00.  The infinity bit next to the sign bit, to a low bit of the flag byte or to a non-zero
+    byte anywhere in the string (tests/encoding_cases.py) is refused by the reference's of_bytes_exn; here it is ZK_ERR_ARG from zk_msm_g1/g2,
+    zk_bases_upload, zk_groth16_pk_upload, zk_groth16_pk_upload_lagrange and zk_pinocchio_pk_upload, and no handle is left behind (a live key handle
+    pins the device list: zk_set_device_list succeeds again)."""
+    import encoding_cases as E
+    from zukelang_amd.curve import G1, G2
+    L = _lib.lib()
+    _lib.check(L.zk_init(0))
+    cs, w = RC.iterated_cubic(8, 3)
+    pk, _ = Groth16.keygen(seeded(0xE49), cs, lagrange=True)
+    pkp, _ = PIN.ZK.keygen(seeded(0xE4A), cs)
+    Groth16(cs, pk).close(); Groth16(cs, pk, lagrange=True).close(); PIN.ZK(cs, pkp).close()          # the honest keys pass
+
+    def put(arr, size, idx, data):
+        out = np.array(arr, dtype=np.uint8, copy=True)
+        out[size * idx:size * (idx + 1)] = np.frombuffer(data, dtype=np.uint8)
+        return out
+
+    def refused(fn):
+        with pytest.raises(_lib.ZkError) as e:
+            fn()
+        assert e.value.code == -1, str(e.value)
+
+    tried = 0
+    for grp, group, size in ((G1, 1, 96), (G2, 2, 192)):
+        pts = grp.of_Fr(RC.fr_bytes(list(range(1, 301))))
+        scal = RC.fr_bytes([7] * 300)
+        field = "g1" if group == 1 else "g2"
+        for label, bad in E.malformed_infinities(group, False):
+            assert E.oracle_verdict(group, False, bad)[0] == P.BAD_ENCODING
+            for idx in (0, 130, 299):
+                refused(lambda: grp.apply_powers(scal, put(pts, size, idx, bad)))
+                h = C.c_uint64(0)
+                arr = put(pts, size, idx, bad)
+                assert L.zk_bases_upload(C.c_int(group - 1), _p(arr), C.c_size_t(300), C.byref(h)) == -1, label
+                assert h.value == 0 and L.zk_bases_info(C.c_uint64(h.value), None, None, None) == -7
+            for idx in (0, len(getattr(pk, field)) // size - 1):
+                refused(lambda: Groth16(cs, type(pk)(**{"g1": pk.g1, "g2": pk.g2, field: put(getattr(pk, field), size, idx, bad)})))
+            lag = "lag_" + field
+            for idx in (0, len(getattr(pk, lag)) // size - 1):
+                key = type(pk)(**{"g1": pk.g1, "g2": pk.g2, "lag_g1": pk.lag_g1, "lag_g2": pk.lag_g2, lag: put(getattr(pk, lag), size, idx, bad)})
+                refused(lambda: Groth16(cs, key, lagrange=True))
+            for idx in (0, len(getattr(pkp, field)) // size - 1):
+                refused(lambda: PIN.ZK(cs, type(pkp)(**{"g1": pkp.g1, "g2": pkp.g2, field: put(getattr(pkp, field), size, idx, bad)})))
+            tried += 1
+    assert tried == 10
+    _lib.set_device_list([0])                                           # ZK_ERR_ARG while any key handle is alive
+    canonical = put(G1.of_Fr(RC.fr_bytes([1, 2, 3])), 96, 1, bytes([0x40]) + bytes(95))
+    G1.apply_powers(RC.fr_bytes([1, 1, 1]), canonical)                   # ... and the canonical identity is still a point

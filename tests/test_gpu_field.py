@@ -77,3 +77,70 @@ def test_field_battery_matches_big_integers():
         b0, b1 = (16 * x0 - y0) % p, (16 * x1 - y1) % p
         assert get(i, 21) == ((b0 * y0 - b1 * y1) % p, (b0 * y1 + b1 * y0) % p)[c], (i, "fp2 lane-pair product, lazily reduced left operand")
         assert get(i, 22) == ((b0 * b0 - b1 * b1) % p, 2 * b0 * b1 % p)[c], (i, "fp2 lane-pair square with the lazy difference")
+
+
+def be48(x):
+    return int(x).to_bytes(48, "big")
+
+
+def _selftest_sqrt(field, blobs):
+    n, B = len(blobs), 96 if field else 48
+    root = np.zeros(B * n, dtype=np.uint8)
+    sq = np.zeros(n, dtype=np.uint8)
+    _lib.check(_lib.lib().zk_selftest_sqrt(C.c_int(field), b"".join(blobs), C.c_size_t(n), root.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                           sq.ctypes.data_as(C.POINTER(C.c_uint8))))
+    raw = root.tobytes()
+    return [raw[B * i:B * (i + 1)] for i in range(n)], [int(x) for x in sq]
+
+
+def test_square_roots_and_the_sign_rule_match_big_integers():
+    """zk_selftest_sqrt: fp_sqrt_dev / fp2_sqrt_dev and the sign rule of k_decompress_g1/g2 (one device function for both) on bare field elements against
+    pyref.fp_sqrt / fp2_sqrt, which return the lexicographically larger root.  Fp2 covers what no subgroup point the suite can construct reaches: a zero
+    imaginary part of the ARGUMENT (root real or purely imaginary), a zero imaginary part of the ROOT (the sign then comes from the real part), and both
+    candidates (a0 + s)/2, (a0 - s)/2 for the real part's square.  Exact bytes; every class of input is counted and must occur."""
+    rnd = random.Random(0x5C207)
+    # ---- Fp
+    ts = [rnd.randrange(1, p) for _ in range(40)]
+    fp = [0, 1, p - 1, 4, 2, 3, (p - 1) // 2, (p + 1) // 2] + [t * t % p for t in ts] + [(-t * t) % p for t in ts]
+    fp += [rnd.randrange(p) for _ in range(4096 - len(fp))]
+    roots, sq = _selftest_sqrt(0, [be48(a) for a in fp])
+    seen = {"square": 0, "non-square": 0}
+    for a, r, s in zip(fp, roots, sq):
+        want = P.fp_sqrt(a)
+        seen["square" if want is not None else "non-square"] += 1
+        assert s == (want is not None) and r == be48(want or 0), ("Fp", hex(a), r.hex(), s)
+    assert all(seen.values()), seen
+    # ---- Fp2
+    F = P.Fp2
+    euler = lambda v: pow(v % p, (p - 1) // 2, p)
+    el = []
+    for t in ts[:24]:
+        c = t * t % p
+        el += [F(c, 0), F(-c, 0), F(0, c), F(0, -c), F(t, 0), F(0, t)]                        # (c, 0) with c a square / a non-square of Fp; (0, c); arbitrary ones
+        el += [F(t, 0) * F(t, 0), F(0, t) * F(0, t), F(t, t) * F(t, t), F(t, -t) * F(t, -t)]      # squares of (t, 0), (0, t), (t, t), (t, -t)
+    el += [F(0, 0), F(1, 0), F(0, 1), F(p - 1, 0), F(0, p - 1), F(4, 0), F(4, 4), F(p - 1, p - 1)]
+    while len(el) < 4096:
+        a = F(rnd.randrange(p), rnd.randrange(p))
+        el.append(a * a if rnd.random() < 0.5 else a)
+    roots, sq = _selftest_sqrt(1, [be48(a.b) + be48(a.a) for a in el])
+    seen = {"real argument, real root": 0, "real argument, imaginary root": 0, "norm not a square": 0, "first candidate": 0, "second candidate": 0,
+            "root with a zero imaginary part": 0, "root with a zero real part": 0}
+    for a, r, s in zip(el, roots, sq):
+        want = P.fp2_sqrt(a)
+        assert s == (want is not None), ("Fp2", a, s)
+        assert r == (be48(want.b) + be48(want.a) if want is not None else bytes(96)), ("Fp2", a, r.hex())
+        if a.b == 0 and not a.is_zero():
+            seen["real argument, real root" if want.b == 0 else "real argument, imaginary root"] += 1
+        elif want is None:
+            seen["norm not a square"] += 1
+        elif not a.is_zero():
+            s0 = pow((a.a * a.a + a.b * a.b) % p, (p + 1) // 4, p)                              # the root of the norm that a^((p+1)/4) gives
+            seen["first candidate" if euler((a.a + s0) * P.fp_inv(2)) == 1 else "second candidate"] += 1
+        if want is not None and not want.is_zero():
+            if want.b == 0:
+                seen["root with a zero imaginary part"] += 1
+            if want.a == 0:
+                seen["root with a zero real part"] += 1
+    assert all(seen.values()), seen
+    # an element >= p is refused
+    assert _lib.lib().zk_selftest_sqrt(C.c_int(0), be48(p), C.c_size_t(1), C.create_string_buffer(48), C.create_string_buffer(1)) == -1

@@ -237,3 +237,119 @@ def test_compact_h_pool_its_switch_and_its_fallback(maker):
         assert want[0] != exp[0]
         run(prover, want, "vav with an identity of its own")
         prover.close()
+
+
+def fixed_seed_rho(n, m):
+    """k_pin_rho of csrc/pinocchio.hip as rounds 1-5 seeded it -- a public constant mixed with n and m -- restated: four splitmix64 words per index,
+    little-endian, the top 32-bit word masked to 30 bits.  Anybody could compute these, so anybody could build the keys below."""
+    M = (1 << 64) - 1
+    seed = 0x5EEDC0DE2026 ^ (n << 32) ^ m
+    out = []
+    for k in range(m):
+        r = 0
+        for q in range(4):
+            x = (seed + (4 * k + q + 1) * 0x9E3779B97F4A7C15) & M
+            x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
+            x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M
+            x ^= x >> 31
+            r |= x << (64 * q)
+        out.append(r & ((1 << 254) - 1))
+    return out
+
+
+def crafted_keys(cs, w, pk):
+    """Keys whose v_all (or w_all) differs from the image of si by D with <rho, D> = 0 for the fixed-seed rho: two compensating points on v_all, two on
+    w_all, three on v_all.  The indices carry non-zero witness entries, so the blinding term dw sum_k c_k v_all[k] (pinocchio.ml:481-486) moves."""
+    n, m = cs.n, cs.m
+    rho = fixed_seed_rho(n, m)
+    nm = sum(1 for k in range(m) if cs.mid[k])
+    o_v = 5 * nm + n + 1
+    live = [k for k in range(m) if w[k] % P.R != 0 and rho[k] % P.R != 0]
+    i, j, l = live[0], live[len(live) // 2], live[-1]
+    assert len({i, j, l}) == 3
+    g = O.g1_generator()
+    inv = lambda x: pow(x, P.R - 2, P.R)
+
+    def shifted(base, deltas):
+        g1 = np.array(pk.g1, copy=True)
+        assert sum(rho[k] * d for k, d in deltas.items()) % P.R == 0          # the fixed-seed check cannot see it
+        for k, d in deltas.items():
+            off = 96 * (base + k)
+            g1[off:off + 96] = np.frombuffer(O.g1_add(bytes(g1[off:off + 96]), O.g1_mul(g, P.fr_to_bytes(d % P.R))), dtype=np.uint8)
+        return PIN.PKey(g1, pk.g2)
+    a, b = 0xA11CE, 0xB0B
+    return {"two points of v_all": shifted(o_v, {i: a, j: -a * rho[i] * inv(rho[j])}),
+            "two points of w_all": shifted(o_v + m, {i: a, j: -a * rho[i] * inv(rho[j])}),
+            "three points of v_all": shifted(o_v, {i: a, j: b, l: -(a * rho[i] + b * rho[j]) * inv(rho[l])})}
+
+
+@pytest.mark.parametrize("maker", [lambda: RC.readme_circuit(3), lambda: RC.random_r1cs(24, 40, 77), lambda: RC.iterated_cubic(64, 10)])
+def test_keys_crafted_against_a_predictable_rho_keep_the_full_pool(maker):
+    """The compact h pool is only valid for keys whose v_all / w_all are the images of si; the upload decides that with a random linear combination.
+    With a rho that can be computed in advance (the fixed seed of rounds 1-5) a key with compensating changes passes, is proved from si, and returns
+    ZK_OK with bytes ZKCompute.f does not compute from that key.  The rho is now drawn from the key's bytes and process entropy: such keys keep the
+    full pool and every proof -- as uploaded, derived, pipelined, compact option default and 0, behind device lists [0, 0] and [0, 0, 0] -- is the
+    literal oracle's on the crafted bytes.
+    Against the library of the parent commit (fixed seed) this test reported, once, on all three circuits: the upload returned ZK_OK and
+    "two points of v_all: a key that is not the image of its si keeps its full h pool (4 points kept)" (README circuit: n + 1 = 4 of 14) -- the
+    compact pool, from which the blinding terms are computed on si and not on the crafted points."""
+    from zukelang_amd import _lib
+    cs, w = maker()
+    n, m = cs.n, cs.m
+    assert n <= 64
+    L, R_, Oo = csrs(cs)
+    st = P.fr_stream(0x5EED0C0C)
+    tox = [next(st) for _ in range(8)]
+    it = iter(tox)
+    pk, _vk = PIN.ZK.keygen(lambda: next(it), cs)
+    ds = [[next(st) for _ in range(3)] for _ in range(2)] + [[0, 0, 0]]
+    q = O.QAP(n, m, L, R_, Oo)
+    nm = sum(1 for k in range(m) if cs.mid[k])
+
+    def literal(key):
+        out = []
+        for d in ds:
+            rc, ref = O.pinocchio_prove(q, bytes(key.g1), bytes(key.g2), cs.mid, frs(w), *(P.fr_to_bytes(x) for x in d))
+            assert rc == 0
+            out.append(ref)
+        return out
+
+    def run(prover, want, tag):
+        assert [prover.prove_with(w, *d).to_bytes() for d in ds] == want, tag
+        prover.derive_lagrange()
+        assert [prover.prove_with(w, *d).to_bytes() for d in ds] == want, tag + ", derived"
+        prover.set_witness(w)
+        for slot, d in enumerate(ds):
+            prover.prove_async(*d, slot)
+        for slot in range(len(ds)):
+            assert prover.prove_wait(slot).to_bytes() == want[slot], tag + ", pipelined"
+
+    honest = literal(pk)
+    keys = crafted_keys(cs, w, pk)
+    assert len(keys) == 3
+    for name, key in keys.items():
+        want = literal(key)
+        assert want[0] != honest[0] and want[1] != honest[1] and want[2] == honest[2], name      # the blinding terms see the change, the NonZK proof does not
+        full = bytes(key.g1[96 * 5 * nm:96 * (5 * nm + n + 1 + 2 * m)])
+        prover = PIN.ZK(cs, key)
+        pool = bytes(prover.pool_points(5))
+        assert len(pool) // 96 == n + 1 + 2 * m and pool == full, "%s: a key that is not the image of its si keeps its full h pool (%d points kept)" % (name, len(pool) // 96)
+        run(prover, want, name)
+        prover.close()
+        _set_option("ZK_PIN_COMPACT_H", 0)
+        try:
+            prover = PIN.ZK(cs, key)
+        finally:
+            _set_option("ZK_PIN_COMPACT_H", None)
+        run(prover, want, name + ", compact option 0")
+        prover.close()
+        for devs in ([0, 0], [0, 0, 0]):
+            _lib.set_device_list(devs)
+            prover = None
+            try:
+                prover = PIN.ZK(cs, key)
+                run(prover, want, name + ", device list %r" % devs)
+            finally:
+                if prover is not None:
+                    prover.close()                                        # a live key pins the device list
+                _lib.set_device_list([0])

@@ -322,3 +322,49 @@ def test_pinocchio_literal_equals_trapdoor_and_verifies(maker):
     bad = bytearray(proof)
     bad[384:480] = O.g1_add(bytes(proof[384:480]), O.g1_generator())
     assert not O.pinocchio_verify(vk1, vk2, io, bytes(bad))
+
+
+def test_decoder_oracle_round_trips_and_public_vectors():
+    """pyref.fp_sqrt / fp2_sqrt / g1,g2_decompress / g1,g2_decode / pt_mul_jac (the decoder oracle of tests/test_decoders.py): inverse of g1/g2_compress
+    over both signs of y, the generators' public compressed strings, the EIP-2537 coordinates of -G1, 2 G1, -G2, 2 G2 used above, and the rules
+    that make a string non-canonical."""
+    for k in (1, 2, 3, 0xDEADBEEF, P.R - 1, P.R - 2):
+        assert P.pt_mul_jac(P.G1, k) == P.pt_mul(P.G1, k) and P.pt_mul_jac(P.G2, k) == P.pt_mul(P.G2, k)
+        for pt, comp, dec, enc, raw in ((P.pt_mul(P.G1, k), P.g1_compress, P.g1_decompress, P.g1_to_bytes, P.g1_decode),
+                                        (P.pt_mul(P.G2, k), P.g2_compress, P.g2_decompress, P.g2_to_bytes, P.g2_decode)):
+            signs = set()
+            for q in (pt, P.pt_neg(pt)):
+                c = comp(q)
+                signs.add(c[0] & 0x20)
+                assert dec(c) == (P.OK, q) and raw(enc(q)) == (P.OK, q)
+            assert signs == {0, 0x20}
+    assert P.pt_mul_jac(P.G1, P.R) is None and P.pt_mul_jac(P.G2, P.R) is None and P.pt_mul_jac(None, 5) is None
+    for dec, comp, raw, enc in ((P.g1_decompress, P.g1_compress, P.g1_decode, P.g1_to_bytes), (P.g2_decompress, P.g2_compress, P.g2_decode, P.g2_to_bytes)):
+        assert dec(comp(None)) == (P.OK, None) and raw(enc(None)) == (P.OK, None)
+    d = json.load(open(GOLDEN))
+    assert P.g1_decompress(bytes.fromhex(d["g1_generator_compressed"])) == (P.OK, P.G1)
+    assert P.g2_decompress(bytes.fromhex(d["g2_generator_compressed"])) == (P.OK, P.G2)
+    # the EIP-2537 coordinates: -G1 and 2 G1 uncompressed, 2 G2 from its compressed string
+    neg_g1_y = "114d1d6855d545a8aa7d76c8cf2e21f267816aef1db507c96655b9d5caac42364e6f38ba0ecb751bad54dcd6b939c2ca"
+    assert P.g1_decode(P.G1_X.to_bytes(48, "big") + bytes.fromhex(neg_g1_y)) == (P.OK, P.pt_neg(P.G1))
+    two_g1_x = "0572cbea904d67468808c8eb50a9450c9721db309128012543902d0ac358a62ae28f75bb8f1c7c42c39a8c5529bf0f4e"
+    two_g1_y = "166a9d8cabc673a322fda673779d8e3822ba3ecb8670e461f73bb9021d5fd76a4c56d9d4cd16bd1bba86881979749d28"
+    assert P.g1_decompress(bytes.fromhex("a5" + two_g1_x[2:])) == (P.OK, (P.Fp1(int(two_g1_x, 16)), P.Fp1(int(two_g1_y, 16))))
+    assert P.g2_decompress(P.g2_compress(P.pt_mul(P.G2, 2)))[1] == P.pt_mul(P.G2, 2)
+    # square roots: the larger root, None for a non-square; Fp2 with a zero imaginary part on either side
+    for a in (0, 1, 4, 9, P.P - 1, 2):
+        r = P.fp_sqrt(a)
+        assert (r is None) == (pow(a, (P.P - 1) // 2, P.P) == P.P - 1) and (r is None or (r * r % P.P == a and r >= (P.P - r) % P.P))
+    assert P.fp_sqrt(P.P - 1) is None and P.fp_sqrt(4) == P.P - 2
+    for a in (P.Fp2(4, 0), P.Fp2(-4, 0), P.Fp2(0, 2), P.Fp2(3, 4), P.Fp2(5, 7) * P.Fp2(5, 7), P.Fp2(0, 0)):
+        r = P.fp2_sqrt(a)
+        assert r * r == a and (r.b, r.a) >= ((-r).b, (-r).a), a
+    assert P.fp2_sqrt(P.Fp2(4, 0)) == P.Fp2(-2, 0) and P.fp2_sqrt(P.Fp2(-4, 0)) == P.Fp2(0, -2)
+    # what makes a string non-canonical
+    g = P.g1_compress(P.G1)
+    assert P.g1_decompress(bytes([g[0] & 0x7F]) + g[1:])[0] == P.BAD_ENCODING and P.g1_decompress(g[:47])[0] == P.BAD_ENCODING
+    assert P.g1_decompress(bytes([0xE0]) + bytes(47))[0] == P.BAD_ENCODING and P.g1_decompress(bytes([0xC0]) + bytes(46) + b"\x01")[0] == P.BAD_ENCODING
+    assert P.g1_decompress(bytes([0x80 | 0x1A]) + (P.P % (1 << 376)).to_bytes(47, "big"))[0] == P.BAD_ENCODING          # x = p
+    assert P.g1_decode(bytes([0x60]) + bytes(95))[0] == P.BAD_ENCODING and P.g2_decode(bytes([0x40]) + bytes(190) + b"\x01")[0] == P.BAD_ENCODING
+    e = bytearray(P.g1_to_bytes(P.G1)); e[0] |= 0x20
+    assert P.g1_decode(bytes(e))[0] == P.BAD_ENCODING

@@ -48,4 +48,6 @@ def test_host_half_of_the_product_library_under_asan_ubsan():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "zukelang_amd", "csrc"), "asan-host"])
     so = os.path.join(ROOT, "zukelang_amd", "libzkhost_asan.so")
     # the verify surface (zk_pairing_*, zk_groth16_verify, zk_pinocchio_verify: csrc/pairing_host.hip) against the oracle, under the sanitizers
-    _run_under_sanitizers({"ZK_LIBZKMI355X_PATH": so}, ["tests/test_pairing_host.py", "-m", "not gpu"], timeout=1500)
+    # ... and the decoders (zk_g1/g2_decompress, the uncompressed decoder of zk_pairing_product) over the hostile-input matrix, with the wire readers on
+    # point strings of the wrong length: a decoder that reads past the Python buffer it was handed is a sanitizer report
+    _run_under_sanitizers({"ZK_LIBZKMI355X_PATH": so}, ["tests/test_pairing_host.py", "tests/test_decoders.py", "-m", "not gpu"], timeout=1500)

@@ -151,3 +151,71 @@ def test_vectorised_compression_is_the_per_point_function():
             assert many[Cb * i:Cb * (i + 1)] == one, (grp.__name__, i)
             signs.add(one[0] & 0x20)
         assert signs == {0, 0x20}
+
+
+def _records_of_every_reader():
+    """(reader, record) for the six readers: the golden JSON where tests/golden/ holds such a record, else one written by the module's own writer from
+    oracle points."""
+    import os
+    from zukelang_amd.pinocchio import PKey as PPKey, VKey as PVKey, Proof as PProof
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    pkey_js, proof_js = (bytes.fromhex(line) for line in open(os.path.join(here, "readme_groth16_wire.hex")).read().split())
+    pt1 = lambda k: P.g1_to_bytes(P.pt_mul_jac(P.G1, k))
+    pt2 = lambda k: P.g2_to_bytes(P.pt_mul_jac(P.G2, k))
+    io_vars = [("ONE", 1), ("v", 6)]
+    vk = VKey(pt1(1), np.frombuffer(pt1(8) + pt1(9), dtype=np.uint8), pt2(1), pt2(10), pt2(11), bytes(range(64)) * 9)
+    n = 3
+    all_vars = [("ONE", 1), ("c", 4), ("c", 5), ("input", 3), ("v", 6)]
+    mids, ios = all_vars[1:4], [all_vars[0], all_vars[4]]
+    k, m = len(mids), len(all_vars)
+    ppk = PPKey(np.frombuffer(b"".join(pt1(100 + i) for i in range(5 * k + (n + 1) + 2 * m + 7)), dtype=np.uint8),
+                np.frombuffer(b"".join(pt2(300 + i) for i in range(2 * k + (n + 1) + 2)), dtype=np.uint8))
+    pvk = PVKey(np.frombuffer(b"".join(pt1(500 + i) for i in range(3 + 2 * len(ios))), dtype=np.uint8),
+                np.frombuffer(b"".join(pt2(600 + i) for i in range(6 + len(ios))), dtype=np.uint8))
+    pproof = PProof(*[(pt1 if g == 1 else pt2)(700 + i) for i, (_f, g) in enumerate(wire._PIN_FIELDS)])
+    return [(wire.groth16_proof_of_json, proof_js), (wire.groth16_pkey_of_json, pkey_js), (wire.groth16_vkey_of_json, wire.groth16_vkey_to_json(vk, io_vars)),
+            (wire.pinocchio_proof_of_json, wire.pinocchio_proof_to_json(pproof)), (wire.pinocchio_vkey_of_json, wire.pinocchio_vkey_to_json(pvk, ios)),
+            (wire.pinocchio_pkey_of_json, wire.pinocchio_pkey_to_json(ppk, n, mids, all_vars))]
+
+
+def test_every_reader_refuses_wrong_lengths_and_malformed_identities():
+    """One point string at a time -- the first, a middle and the last G1 and G2 field of the record -- replaced by strings of 0, 1, 47, 49, 95 and 97
+    bytes and by the malformed identities of tests/encoding_cases.py: every reader raises ValueError, of the class "length" resp. "point" (the same
+    two classes a list of 256 points or more raises on the GPU path: tests/test_gpu_decompress.py)."""
+    import encoding_cases as E
+    records = _records_of_every_reader()
+    assert len(records) == 6
+    for reader, record in records:
+        assert E.check_reader_refuses_bad_point_strings(wire, reader, record) >= 2 * len(E.bad_point_strings(1)), reader.__name__
+
+
+def test_fr_fields_follow_the_reference_grammar_not_pythons():
+    """Fr.t_of_yojson = Fr.of_z (Z.of_string s) (reference: src/lib/zk/curve.ml:140, src/lib/misclib/misc.ml:38).  Neither zarith nor the curve library
+    can be run here; the last column says where each expectation comes from."""
+    import pytest
+    r = P.R
+    js = lambda s: wire.json_bytes_string(s if isinstance(s, bytes) else s.encode())
+    table = [
+        # input                          expectation      source
+        (js("0"),                        0,               "golden fixtures: Z.to_string writes plain decimal digits"),
+        (js("5"),                        5,               "golden fixtures"),
+        (js(str(r - 1)),                 r - 1,           "golden fixtures: the largest canonical value"),
+        (js(" 5"),                       ValueError,      "Python-only spelling (int() strips white space): must not pass silently"),
+        (js("5\n"),                      ValueError,      "Python-only spelling"),
+        (js("1_000"),                    ValueError,      "Python-only spelling (PEP 515 underscores)"),
+        (js("\u0665".encode("utf-8")),   ValueError,      "Python-only spelling (int() reads non-ASCII digits from str)"),
+        (js(""),                         ValueError,      "no integer in any grammar"),
+        (b"5",                           ValueError,      "a JSON number, not a string: string_of_yojson raises (misc.ml:38)"),
+        (b"[\"5\"]",                     ValueError,      "not a string"),
+        (js("7" * 400),                  int("7" * 400) % r, "Fr.of_z reduces mod r: the curve library's DOCUMENTATION (its source is not in the reference tree)"),
+        (js(str(r)),                     0,               "Fr.of_z reduces mod r: documentation"),
+        (js(str(r + 3)),                 3,               "Fr.of_z reduces mod r: documentation"),
+        (js("-1"),                       r - 1,           "Z.of_string reads a leading '-'; Fr.of_z reduces mod r: documentation"),
+    ]
+    for data, want, source in table:
+        if want is ValueError:
+            with pytest.raises(ValueError):
+                wire.fr_of_json(data)
+        else:
+            got = wire.fr_of_json(data)
+            assert got == want and 0 <= got < r, (data[:40], source)

@@ -434,6 +434,12 @@ static int decompress_api(Curve curve, const uint8_t* in, size_t n, uint8_t* out
 }
 int zk_g1_decompress_batch(const uint8_t* in, size_t n, uint8_t* out) { return decompress_api(CURVE_G1, in, n, out); }
 int zk_g2_decompress_batch(const uint8_t* in, size_t n, uint8_t* out) { return decompress_api(CURVE_G2, in, n, out); }
+// the square roots and the sign rule of the two entry points above on bare field elements (the self tests of include/zkmi355x.h, next to zk_selftest_fp)
+int zk_selftest_sqrt(int field, const uint8_t* a, size_t n, uint8_t* root, uint8_t* is_square) {
+    if (!a || !root || !is_square || !n || (field != 0 && field != 1)) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_sqrt: null argument, no elements, or a field other than 0 (Fp) / 1 (Fp2)");
+    ZKCHK(ensure_init());
+    return points_selftest_sqrt(field, a, n, root, is_square, ctx().stream);
+}
 int zk_g1_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G1, scalars, n, out); }
 int zk_g2_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G2, scalars, n, out); }
 int zk_g1_powers(uint32_t d, const uint8_t s[32], uint8_t* out) { return powers_api(CURVE_G1, d, s, out); }

@@ -26,11 +26,17 @@ FF_INLINE void fpw_to_be(uint8_t* p, const FpWords& a) {
 }
 FF_INLINE bool fpw_canonical(const FpWords& a) { return words_are_canonical<FpParams>(a.w); }
 
+// the ONE encoding of the identity: `first` (the infinity bit next to the form's compression bit), then zeros -- the sign bit is not free either
+FF_INLINE bool canonical_infinity(const uint8_t* p, int len, uint8_t first) {
+    uint32_t o = p[0] ^ first;
+    for (int k = 1; k < len; k++) o |= p[k];
+    return o == 0;
+}
 // G1: x | y ; G2: x1 | x0 | y1 | y0  (ZCash uncompressed)
 FF_INLINE int aff_decode(Aff<Fp>& out, const uint8_t* p) {
     uint8_t flags = p[0];
     if (flags & 0x80) return 2;                       // compressed encodings are not accepted here
-    if (flags & 0x40) { out = aff_inf<Fp>(); return 0; }
+    if (flags & 0x40) { out = aff_inf<Fp>(); return canonical_infinity(p, 96, 0x40) ? 0 : 2; }
     const FpWords x = fpw_from_be(p), y = fpw_from_be(p + 48);
     if (!fpw_canonical(x) || !fpw_canonical(y)) return 2;
     out = {fp_to_mont(x), fp_to_mont(y)};
@@ -39,7 +45,7 @@ FF_INLINE int aff_decode(Aff<Fp>& out, const uint8_t* p) {
 FF_INLINE int aff_decode(Aff<Fp2>& out, const uint8_t* p) {
     uint8_t flags = p[0];
     if (flags & 0x80) return 2;
-    if (flags & 0x40) { out = aff_inf<Fp2>(); return 0; }
+    if (flags & 0x40) { out = aff_inf<Fp2>(); return canonical_infinity(p, 192, 0x40) ? 0 : 2; }
     const FpWords x1 = fpw_from_be(p), x0 = fpw_from_be(p + 48), y1 = fpw_from_be(p + 96), y0 = fpw_from_be(p + 144);
     if (!fpw_canonical(x0) || !fpw_canonical(x1) || !fpw_canonical(y0) || !fpw_canonical(y1)) return 2;
     out = {{fp_to_mont(x0), fp_to_mont(x1)}, {fp_to_mont(y0), fp_to_mont(y1)}};
@@ -107,8 +113,10 @@ __global__ __launch_bounds__(64) void k_proof_to_bytes(const uint8_t* g1, uint32
 // The reference's JSON holds every key point COMPRESSED (Bls12_381.G1/G2.to_compressed_bytes): a 2^20-constraint key is five million square roots and
 // subgroup checks on the way in -- half an hour of one host core through zk_g1/g2_decompress, a second here.  One lane per point: x from its 48 / 96
 // big-endian bytes, y = sqrt(x^3 + b) by the power (p + 1) / 4 (p = 3 mod 4; in Fp2 through the norm), the sign bit's choice of root, then the
-// subgroup check and the encoder above.  Same verdicts as the host functions: flag 2 = bad encoding (compression bit missing, coordinate >= p),
-// 1 = x is not the abscissa of a curve point.
+// subgroup check and the encoder above.  Same verdicts as the host functions: kind 2 = bad encoding (compression bit missing, coordinate >= p, infinity
+// bit on a string that is not C0 00 .. 00), 1 = x is not the abscissa of a curve point, 4 = outside the subgroup (k_subgroup_check).  A list fails with
+// the verdict of its FIRST bad element, as a reader that decodes the elements in order does: every bad lane files index << 3 | kind under atomicMin.
+FF_INLINE void first_failure(unsigned long long* first, uint64_t i, int kind) { atomicMin(first, (unsigned long long)(i << 3) | (unsigned long long)kind); }
 __device__ static const uint32_t FP_SQRT_EXP[12] = {0xffffeaabu, 0xee7fbfffu, 0xac54ffffu, 0x07aaffffu, 0x3dac3d89u, 0xd9cc34a8u,
                                                     0x3ce144afu, 0xd91dd2e1u, 0x90d2eb35u, 0x92c6e9edu, 0x8e5ff9a6u, 0x0680447au};      // (p + 1) / 4, 379 bits
 __device__ static const uint32_t FP_HALF_PM1[12] = {0xffffd555u, 0xdcff7fffu, 0x58a9ffffu, 0x0f55ffffu, 0x7b587b12u, 0xb3986950u,
@@ -134,6 +142,10 @@ template <int A> FF_INLINE bool fp_is_large(const FpB<A>& y) {          // canon
         if (!decided && w.w[k] != FP_HALF_PM1[k]) { gt = w.w[k] > FP_HALF_PM1[k]; decided = true; }
     return gt;
 }
+// "is this y the larger one of y, -y": the ZCash sign of a point.  Fp: the canonical integer above (p - 1) / 2.  Fp2: the same question put to the
+// imaginary part, and to the real part when the imaginary part is zero.  The decompression kernels and zk_selftest_sqrt both decide here.
+FF_INLINE bool y_is_larger(const FpB<2>& y) { return fp_is_large(y); }
+FF_INLINE bool y_is_larger(const Fp2B<2>& y) { return fe_is_zero(y.c1) ? fp_is_large(y.c0) : fp_is_large(y.c1); }
 // a square root of a in Fp2 = Fp[u] / (u^2 + 1) (either one: the caller fixes the sign); false: a is not a square
 FF_INLINE bool fp2_sqrt_dev(Fp2B<2>& out, const Fp2B<2>& a) {
     if (fe_is_zero(a.c1)) {
@@ -152,7 +164,7 @@ FF_INLINE bool fp2_sqrt_dev(Fp2B<2>& out, const Fp2B<2>& a) {
     const Fp2B<4> sq = fe_sqr(out);
     return fe_eq(sq.c0, a.c0) && fe_eq(sq.c1, a.c1);
 }
-__global__ __launch_bounds__(128) void k_decompress_g1(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, int* flag) {
+__global__ __launch_bounds__(128) void k_decompress_g1(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, unsigned long long* first) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     alignas(16) uint8_t xb[48];
@@ -160,24 +172,27 @@ __global__ __launch_bounds__(128) void k_decompress_g1(uint8_t* __restrict__ den
     const uint8_t f0 = xb[0];
     xb[0] &= 0x1f;
     Aff<Fp> out = aff_inf<Fp>();
-    if (!(f0 & 0x80)) atomicOr(flag, 2);
-    else if (!(f0 & 0x40)) {
+    if (!(f0 & 0x80)) first_failure(first, i, 2);
+    else if (f0 & 0x40) {
+        xb[0] = f0;
+        if (!canonical_infinity(xb, 48, 0xC0)) first_failure(first, i, 2);
+    } else {
         const FpWords xw = fpw_from_be(xb);
-        if (!fpw_canonical(xw)) atomicOr(flag, 2);
+        if (!fpw_canonical(xw)) first_failure(first, i, 2);
         else {
             const FpB<2> x = fp_to_mont(xw);
             const FpB<2> rhs = fp_red2(fe_add(fe_mul(fe_sqr(x), x), FieldOps<Fp>::curve_b()));
             FpB<2> y;
-            if (!fp_sqrt_dev(y, rhs)) atomicOr(flag, 1);
+            if (!fp_sqrt_dev(y, rhs)) first_failure(first, i, 1);
             else {
-                if (fp_is_large(y) != ((f0 & 0x20) != 0)) y = fp_red2(fe_neg(y));
+                if (y_is_larger(y) != ((f0 & 0x20) != 0)) y = fp_red2(fe_neg(y));
                 out = {x, y};
             }
         }
     }
     aff_store<Fp>(dense + 96 * i, out);
 }
-__global__ __launch_bounds__(128) void k_decompress_g2(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, int* flag) {
+__global__ __launch_bounds__(128) void k_decompress_g2(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, unsigned long long* first) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     alignas(16) uint8_t xb[96];          // x.c1 (with the flags) | x.c0
@@ -185,20 +200,22 @@ __global__ __launch_bounds__(128) void k_decompress_g2(uint8_t* __restrict__ den
     const uint8_t f0 = xb[0];
     xb[0] &= 0x1f;
     Aff<Fp2> out = aff_inf<Fp2>();
-    if (!(f0 & 0x80)) atomicOr(flag, 2);
-    else if (!(f0 & 0x40)) {
+    if (!(f0 & 0x80)) first_failure(first, i, 2);
+    else if (f0 & 0x40) {
+        xb[0] = f0;
+        if (!canonical_infinity(xb, 96, 0xC0)) first_failure(first, i, 2);
+    } else {
         const FpWords x1w = fpw_from_be(xb), x0w = fpw_from_be(xb + 48);
-        if (!fpw_canonical(x1w) || !fpw_canonical(x0w)) atomicOr(flag, 2);
+        if (!fpw_canonical(x1w) || !fpw_canonical(x0w)) first_failure(first, i, 2);
         else {
             const Fp2B<2> x = {fp_to_mont(x0w), fp_to_mont(x1w)};
             const auto cube = fe_mul(fe_sqr(x), x);
             const Fp2 b = FieldOps<Fp2>::curve_b();
             const Fp2B<2> rhs = {fp_red2(fe_add(cube.c0, b.c0)), fp_red2(fe_add(cube.c1, b.c1))};
             Fp2B<2> y;
-            if (!fp2_sqrt_dev(y, rhs)) atomicOr(flag, 1);
+            if (!fp2_sqrt_dev(y, rhs)) first_failure(first, i, 1);
             else {
-                const bool large = fe_is_zero(y.c1) ? fp_is_large(y.c0) : fp_is_large(y.c1);
-                if (large != ((f0 & 0x20) != 0)) y = {fp_red2(fe_neg(y.c0)), fp_red2(fe_neg(y.c1))};
+                if (y_is_larger(y) != ((f0 & 0x20) != 0)) y = {fp_red2(fe_neg(y.c0)), fp_red2(fe_neg(y.c1))};
                 out = {Fp2(x), Fp2(y)};
             }
         }
@@ -206,12 +223,52 @@ __global__ __launch_bounds__(128) void k_decompress_g2(uint8_t* __restrict__ den
     aff_store<Fp2>(dense + 192 * i, out);
 }
 
+// zk_selftest_sqrt: the square roots and the sign rule above on bare field elements, one lane per element, as k_decompress_* call them.
+// field 0: 48 B big-endian each; field 1: 96 B each, imaginary part | real part (the order of a G2 coordinate on the wire).  root = the root that
+// y_is_larger calls the larger one (zeros when a is not a square), is_square = 1 / 0.  An element >= p sets *flag.
+__global__ __launch_bounds__(128) void k_selftest_sqrt(uint8_t* __restrict__ root, uint8_t* __restrict__ is_square, const uint8_t* __restrict__ in, uint64_t n,
+                                                       int field, int* flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int B = field ? 96 : 48;
+    alignas(16) uint8_t ab[96], rb[96];
+    for (int k = 0; k < B; k++) { ab[k] = in[B * i + k]; rb[k] = 0; }
+    bool sq = false;
+    if (!field) {
+        const FpWords aw = fpw_from_be(ab);
+        if (!fpw_canonical(aw)) atomicOr(flag, 2);
+        else {
+            FpB<2> y;
+            sq = fp_sqrt_dev(y, fp_to_mont(aw));
+            if (sq) {
+                if (!y_is_larger(y)) y = fp_red2(fe_neg(y));
+                fpw_to_be(rb, fp_from_mont(y));
+            }
+        }
+    } else {
+        const FpWords a1w = fpw_from_be(ab), a0w = fpw_from_be(ab + 48);
+        if (!fpw_canonical(a1w) || !fpw_canonical(a0w)) atomicOr(flag, 2);
+        else {
+            Fp2B<2> y;
+            sq = fp2_sqrt_dev(y, Fp2B<2>{fp_to_mont(a0w), fp_to_mont(a1w)});
+            if (sq) {
+                if (!y_is_larger(y)) y = {fp_red2(fe_neg(y.c0)), fp_red2(fe_neg(y.c1))};
+                fpw_to_be(rb, fp_from_mont(y.c1));
+                fpw_to_be(rb + 48, fp_from_mont(y.c0));
+            }
+        }
+    }
+    for (int k = 0; k < B; k++) root[B * i + k] = rb[k];
+    is_square[i] = sq ? 1 : 0;
+}
+
 // ------------------------------------------------------------------ prime-order subgroup check of uploaded KEY points: [r] P = O
 // The reference's points come from Bls12_381.G1/G2.of_bytes_exn / of_compressed_bytes_exn (curve.ml:199-212), which raise on a point of the curve
 // that lies outside the r-torsion; a key uploaded to the library as raw bytes gets the same treatment here.  Plain double-and-add over the bits of r
 // (a compile-time constant: the branch is wave-uniform), out-of-line group operations: ~255 doublings + 127 additions per point, 0.3 s of a 2^20 key.
 __device__ static const uint32_t FR_ORDER_BITS[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-template <class F> __global__ __launch_bounds__(128) void k_subgroup_check(const uint8_t* __restrict__ dense, uint64_t n, int* flag) {
+// `first` (may be null): the list readers' first-failure word of k_decompress_*, filed next to the flag.
+template <class F> __global__ __launch_bounds__(128) void k_subgroup_check(const uint8_t* __restrict__ dense, uint64_t n, int* flag, unsigned long long* first) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     constexpr int B = FieldOps<F>::WORDS * 8;
@@ -222,7 +279,10 @@ template <class F> __global__ __launch_bounds__(128) void k_subgroup_check(const
         acc = xyzz_dbl(acc);
         if ((FR_ORDER_BITS[b >> 5] >> (b & 31)) & 1u) xyzz_madd(acc, p);
     }
-    if (!xyzz_is_inf(acc)) atomicOr(flag, 4);
+    if (!xyzz_is_inf(acc)) {
+        atomicOr(flag, 4);
+        if (first) atomicMin(first, (unsigned long long)(i << 3) | 4ull);
+    }
 }
 
 // ------------------------------------------------------------------ base tables: table[j*n + i] = 2^(c*j) * P_i, j < nw
@@ -410,8 +470,8 @@ int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, ui
     ZKCHK(points_bytes_to_affine(curve, dense.p, raw.p, n, flag.as<int>(), s));
     if (check_subgroup) {
         ScopedTimer t("subgroup_check", s);
-        if (curve == CURVE_G1) hipLaunchKernelGGL(k_subgroup_check<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>());
-        else hipLaunchKernelGGL(k_subgroup_check<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>());
+        if (curve == CURVE_G1) hipLaunchKernelGGL(k_subgroup_check<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), (unsigned long long*)nullptr);
+        else hipLaunchKernelGGL(k_subgroup_check<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), (unsigned long long*)nullptr);
     }
     int h = 0;
     HIPCHK(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, s));
@@ -457,25 +517,50 @@ int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, 
     ZKCHK(din.alloc(cb * n));
     ZKCHK(dense.alloc(ub * n));
     ZKCHK(dout.alloc(ub * n));
-    ZKCHK(flag.alloc(4));
-    HIPCHK(hipMemsetAsync(flag.p, 0, 4, s));
+    ZKCHK(flag.alloc(16));                                  // the subgroup kernel's flag word | the first failure: index << 3 | kind, all ones = none
+    HIPCHK(hipMemsetAsync(flag.p, 0, 8, s));
+    HIPCHK(hipMemsetAsync(flag.as<uint8_t>() + 8, 0xFF, 8, s));
+    unsigned long long* first = (unsigned long long*)(flag.as<uint8_t>() + 8);
     HIPCHK(hipMemcpyAsync(din.p, in, cb * n, hipMemcpyHostToDevice, s));
     if (curve == CURVE_G1) {
-        hipLaunchKernelGGL(k_decompress_g1, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, flag.as<int>());
-        hipLaunchKernelGGL(k_subgroup_check<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>());
+        hipLaunchKernelGGL(k_decompress_g1, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, first);
+        hipLaunchKernelGGL(k_subgroup_check<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), first);
     } else {
-        hipLaunchKernelGGL(k_decompress_g2, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, flag.as<int>());
-        hipLaunchKernelGGL(k_subgroup_check<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>());
+        hipLaunchKernelGGL(k_decompress_g2, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, first);
+        hipLaunchKernelGGL(k_subgroup_check<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), first);
     }
     HIPCHK(hipGetLastError());
     ZKCHK(points_affine_to_bytes(curve, dout.p, dense.p, n, s));
-    int h = 0;
-    HIPCHK(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, s));
+    unsigned long long h = 0;
+    HIPCHK(hipMemcpyAsync(&h, first, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out, dout.p, ub * n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (h & 2) ZK_FAIL(ZK_ERR_ARG, "decompress: a point's compression flag is not set or a coordinate is >= p");
-    if (h & 1) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "decompress: an abscissa is not on the curve");
-    if (h & 4) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "decompress: a point is on the curve but outside the prime-order subgroup");
+    if (h != ~0ull) {          // the verdict of the first bad element of the list
+        const int kind = (int)(h & 7);
+        if (kind == 2) ZK_FAIL(ZK_ERR_ARG, "decompress: a point's compression flag is not set, a coordinate is >= p, or the infinity bit is set on a string that is not the identity's");
+        if (kind == 1) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "decompress: an abscissa is not on the curve");
+        ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "decompress: a point is on the curve but outside the prime-order subgroup");
+    }
+    return ZK_OK;
+}
+
+int points_selftest_sqrt(int field, const uint8_t* a, uint64_t n, uint8_t* root, uint8_t* is_square, hipStream_t s) {
+    const size_t B = field ? 96 : 48;
+    DevBuf din, droot, dsq, flag;
+    ZKCHK(din.alloc(B * n));
+    ZKCHK(droot.alloc(B * n));
+    ZKCHK(dsq.alloc(n));
+    ZKCHK(flag.alloc(4));
+    HIPCHK(hipMemsetAsync(flag.p, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(din.p, a, B * n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_selftest_sqrt, grid_for(n, 128), dim3(128), 0, s, droot.as<uint8_t>(), dsq.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, field, flag.as<int>());
+    HIPCHK(hipGetLastError());
+    int h = 0;
+    HIPCHK(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(root, droot.p, B * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(is_square, dsq.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_sqrt: an element is >= p");
     return ZK_OK;
 }
 

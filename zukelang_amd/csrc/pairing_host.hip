@@ -373,10 +373,20 @@ template <class PT, class F> static PT jac_to_affine(const Jac<F>& t) {
 }
 template <class PT, class F> static bool in_subgroup(const PT& p) { return Ops<F>::is_zero(jac_mul<PT, F>(p, HP_R, 4).Z); }
 
+// the ONE encoding of the identity: the infinity bit next to the form's compression bit, every other bit of the string zero (the sign bit included)
+static bool canonical_infinity(const uint8_t* b, size_t len, uint8_t first) {
+    uint8_t o = b[0] ^ first;
+    for (size_t i = 1; i < len; i++) o |= b[i];
+    return o == 0;
+}
 // ZCash uncompressed decoding + curve and subgroup membership; 0 ok, else a ZK_ERR code
 static int g1_decode(G1& out, const uint8_t* b) {
     if (b[0] & 0x80) return ZK_ERR_ARG;
-    if (b[0] & 0x40) { out.inf = true; out.x = fp_zero(); out.y = fp_zero(); return ZK_OK; }
+    if (b[0] & 0x40) {
+        if (!canonical_infinity(b, 96, 0x40)) return ZK_ERR_ARG;
+        out.inf = true; out.x = fp_zero(); out.y = fp_zero();
+        return ZK_OK;
+    }
     if (!fp_from_be(out.x, b) || !fp_from_be(out.y, b + 48)) return ZK_ERR_ARG;
     out.inf = false;
     const Fp rhs = fp_add(fp_mul(fp_sqr(out.x), out.x), fp_from_u64(4));
@@ -386,7 +396,11 @@ static int g1_decode(G1& out, const uint8_t* b) {
 }
 static int g2_decode(G2& out, const uint8_t* b) {
     if (b[0] & 0x80) return ZK_ERR_ARG;
-    if (b[0] & 0x40) { out.inf = true; out.x = f2_zero(); out.y = f2_zero(); return ZK_OK; }
+    if (b[0] & 0x40) {
+        if (!canonical_infinity(b, 192, 0x40)) return ZK_ERR_ARG;
+        out.inf = true; out.x = f2_zero(); out.y = f2_zero();
+        return ZK_OK;
+    }
     if (!fp_from_be(out.x.b, b) || !fp_from_be(out.x.a, b + 48) || !fp_from_be(out.y.b, b + 96) || !fp_from_be(out.y.a, b + 144)) return ZK_ERR_ARG;
     out.inf = false;
     const Fp four = fp_from_u64(4);
@@ -575,7 +589,11 @@ int zk_g1_decompress(const uint8_t in[48], uint8_t out[96]) {
     if (!in || !out) ZK_FAIL(ZK_ERR_ARG, "zk_g1_decompress: null");
     if (!(in[0] & 0x80)) ZK_FAIL(ZK_ERR_ARG, "zk_g1_decompress: compression flag not set");
     memset(out, 0, 96);
-    if (in[0] & 0x40) { out[0] = 0x40; return ZK_OK; }
+    if (in[0] & 0x40) {
+        if (!hp::canonical_infinity(in, 48, 0xC0)) ZK_FAIL(ZK_ERR_ARG, "zk_g1_decompress: infinity bit set on a string that is not the identity's");
+        out[0] = 0x40;
+        return ZK_OK;
+    }
     uint8_t xb[48];
     memcpy(xb, in, 48);
     xb[0] &= 0x1f;
@@ -593,7 +611,11 @@ int zk_g2_decompress(const uint8_t in[96], uint8_t out[192]) {
     if (!in || !out) ZK_FAIL(ZK_ERR_ARG, "zk_g2_decompress: null");
     if (!(in[0] & 0x80)) ZK_FAIL(ZK_ERR_ARG, "zk_g2_decompress: compression flag not set");
     memset(out, 0, 192);
-    if (in[0] & 0x40) { out[0] = 0x40; return ZK_OK; }
+    if (in[0] & 0x40) {
+        if (!hp::canonical_infinity(in, 96, 0xC0)) ZK_FAIL(ZK_ERR_ARG, "zk_g2_decompress: infinity bit set on a string that is not the identity's");
+        out[0] = 0x40;
+        return ZK_OK;
+    }
     uint8_t xb[96];
     memcpy(xb, in, 96);
     xb[0] &= 0x1f;

@@ -32,6 +32,7 @@
 
 #include <map>
 #include <memory>
+#include <random>
 #include <string.h>
 
 namespace zk {
@@ -183,7 +184,30 @@ static bool pin_compact_wanted() {          // read per key (set-up path)
     const char* e = ::zk::opt("ZK_PIN_COMPACT_H");
     return !(e && atoi(e) == 0);
 }
-// rho[k]: pseudo-random canonical scalars below 2^254 (splitmix64 of the index: a consistency check of a key against itself, not a secret)
+// The seed of rho.  The check is a random linear combination, and it is worth its 2^-254 only if rho cannot be known before the key's bytes are fixed:
+// with a seed anybody can compute (rounds 1-5: a constant mixed with n and m) a key with v_all[i] += [a] G, v_all[j] -= [a rho_i / rho_j] G passes, is
+// proved from si, and the proof differs from what ZKCompute.f computes from that key.  So the seed is a digest of the very bytes that are checked
+// (si | v_all | w_all: changing a point changes every rho) mixed with 64 bits of entropy drawn once per process (the digest is no cryptographic hash;
+// the entropy is what a key's author cannot have seen).  Verdicts do not depend on the draw: a key KeyGen.generate made passes under every rho, a key
+// that breaks the relation fails under all but a negligible share (2^-64: the seed's width) of the draws.
+static uint64_t pin_rho_seed(const uint8_t* bytes, size_t len, uint32_t n, uint32_t m) {
+    static const uint64_t process_entropy = [] {
+        std::random_device rd;
+        return ((uint64_t)rd() << 32) | (uint64_t)rd();
+    }();
+    uint64_t h = 0x5EEDC0DE2026ull ^ ((uint64_t)n << 32) ^ m;
+    for (size_t i = 0; i + 8 <= len; i += 8) {          // len is a multiple of 96
+        uint64_t w;
+        memcpy(&w, bytes + i, 8);
+        h = (h ^ w) * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+    }
+    h ^= process_entropy;
+    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+    h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+    return h ^ (h >> 31);
+}
+// rho[k]: pseudo-random canonical scalars below 2^254 (splitmix64 of seed and index)
 __global__ void k_pin_rho(uint32_t* __restrict__ rho, uint64_t m, uint64_t seed) {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= m) return;
@@ -214,9 +238,9 @@ __global__ void k_pin_check_scalars(uint32_t* __restrict__ out, const uint32_t* 
 #pragma unroll
     for (int q = 0; q < 4; q++) fe_store<FrParams>(out + 8 * (q * ph + i), x[q]);
 }
-// *ok = the key's v_all / w_all equal sum_j (v_k)_j si[j] / sum_j (w_k)_j si[j] for every variable k (up to the 2^-254 of a random combination).
+// *ok = the key's v_all / w_all equal sum_j (v_k)_j si[j] / sum_j (w_k)_j si[j] for every variable k (up to the chance of a random combination under `seed`).
 // `full`: si | v_all | w_all as a plain (one-window) base set.
-static int pin_compact_check(const FrStage& fr, const MsmBases& full, uint32_t n, uint32_t m, bool* ok, hipStream_t s) {
+static int pin_compact_check(const FrStage& fr, const MsmBases& full, uint32_t n, uint32_t m, uint64_t seed, bool* ok, hipStream_t s) {
     *ok = false;
     const uint64_t ph = (uint64_t)n + 1 + 2 * (uint64_t)m;
     if (full.n != ph) ZK_FAIL(ZK_ERR_ARG, "pin_compact_check: unexpected pool length");
@@ -228,7 +252,7 @@ static int pin_compact_check(const FrStage& fr, const MsmBases& full, uint32_t n
     ZKCHK(rho.alloc(32 * (size_t)m));
     ZKCHK(scal.alloc(32 * 4 * (size_t)ph));
     ZKCHK(res.alloc(4 * xyzz_bytes(CURVE_G1)));
-    hipLaunchKernelGGL(k_pin_rho, g1d(m), dim3(256), 0, s, rho.as<uint32_t>(), (uint64_t)m, 0x5EEDC0DE2026ull ^ ((uint64_t)n << 32) ^ m);
+    hipLaunchKernelGGL(k_pin_rho, g1d(m), dim3(256), 0, s, rho.as<uint32_t>(), (uint64_t)m, seed);
     HIPCHK(hipGetLastError());
     ZKCHK(frstage_eval(fr, fs, rho.p, s));          // v_rho = sum_k rho_k v_k and w_rho as coefficient vectors (rho satisfies no gate: flags and h are not read)
     hipLaunchKernelGGL(k_pin_check_scalars, g1d(ph), dim3(256), 0, s, scal.as<uint32_t>(), (const uint32_t*)fs.d.as<uint32_t>(),
@@ -241,6 +265,14 @@ static int pin_compact_check(const FrStage& fr, const MsmBases& full, uint32_t n
     return ZK_OK;
 }
 
+// the G1 generator, uncompressed (x | y big-endian): what si[0] of an evaluation key has to be (pin_key_build)
+static const uint8_t G1_GENERATOR_BYTES[96] = {
+    0x17, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
+    0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
+    0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb,
+    0x08, 0xb3, 0xf4, 0x81, 0xe3, 0xaa, 0xa0, 0xf1, 0xa0, 0x9e, 0x30, 0xed, 0x74, 0x1d, 0x8a, 0xe4,
+    0xfc, 0xf5, 0xe0, 0x95, 0xd5, 0xd0, 0x0a, 0xf6, 0x00, 0xdb, 0x18, 0xcb, 0x2c, 0x04, 0xb3, 0xed,
+    0xd0, 0x3c, 0xc7, 0x44, 0xa2, 0x88, 0x8a, 0xe4, 0x0c, 0xaa, 0x23, 0x29, 0x46, 0xc5, 0xe7, 0xe1};
 static int pin_lookup(uint64_t handle, PinKey** out) {
     auto it = g_pin.find(handle);
     if (it == g_pin.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown Pinocchio key handle");
@@ -270,6 +302,11 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
     if (n < 1) ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload: need at least 1 constraint");      // an EMPTY I_mid is fine: the pools keep their appended single points
     if (pk_g1_points != 5 * nm + (n + 1) + 2 * (uint64_t)m + 7) ZK_FAIL(ZK_ERR_DOMAIN, "pinocchio pk_upload: G1 key length");
     if (pk_g2_points != 2 * nm + (n + 1) + 2) ZK_FAIL(ZK_ERR_DOMAIN, "pinocchio pk_upload: G2 key length");
+    // si[0] must be the generator: ZKCompute.f subtracts `one * dy` -- G1.one, not a point of the key (pinocchio.ml:485) -- and the library lets that term
+    // ride on si[0] (the h pool has no base of its own for it).  True of every key KeyGen.generate makes (si[0] = [s^0]); a key that breaks it is refused
+    // here rather than proved with other bytes than the reference's.
+    if (memcmp(pk_g1 + 96 * (5 * nm), G1_GENERATOR_BYTES, 96) != 0)
+        ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload: si[0] is not the G1 generator (the blinding term -dy * one of pinocchio.ml:485 rides on si[0])");
     ZKCHK(frstage_init(k.fr, n, m, L, R, O, c.stream));
     // slices of the flattened key (pinocchio.ml:37-60; layout in include/zkmi355x.h)
     const uint8_t *VV = pk_g1, *YY = VV + 96 * nm, *VAV = YY + 96 * nm, *YAY = VAV + 96 * nm, *BV = YAY + 96 * nm,
@@ -305,7 +342,7 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
         MsmBases full;
         ZKCHK(msm_bases_from_bytes(full, CURVE_G1, SI, ph_full, 0, false, c.stream, k.in_subgroup));
         bool ok = false;
-        ZKCHK(pin_compact_check(k.fr, full, n, m, &ok, c.stream));
+        ZKCHK(pin_compact_check(k.fr, full, n, m, pin_rho_seed(SI, 96 * ph_full, n, m), &ok, c.stream));
         compact = ok ? 1 : 0;
     }
     k.compact = compact != 0;

@@ -14,6 +14,7 @@ escapes only '"', '\\', the control characters (\\b \\f \\n \\r \\t, the rest as
 writer and parser below work on BYTES and reproduce exactly that.
 """
 import ctypes as C
+import re
 
 from . import _lib
 from .curve import G1, G2
@@ -162,38 +163,56 @@ def _loads_body(data):
     return v
 
 
-def _decompress(fn, comp, n_out):
+def _point_error(e):
+    """One error type for a point string the decoders refuse, one point at a time on the host or as a list on the GPU: ValueError, with the library's code
+    and text (a bad encoding, an abscissa off the curve, a point outside the subgroup)."""
+    return ValueError("wire: bad point (%s)" % e)
+
+
+def _decompress(fn, comp, n_in, n_out):
+    _need(isinstance(comp, (bytes, bytearray)), "a point is a JSON string")
+    _need(len(comp) == n_in, "a compressed G%d point is %d bytes" % (n_in // 48, n_in))          # before the C call: it reads n_in bytes whatever it is given
     out = C.create_string_buffer(n_out)
-    _lib.check(fn(bytes(comp), out))
+    try:
+        _lib.check(fn(bytes(comp), out))
+    except _lib.ZkError as e:
+        raise _point_error(e) from None
     return out.raw
 
 
 def g1_of_json(b):
-    return _decompress(_lib.lib().zk_g1_decompress, b, 96)
+    return _decompress(_lib.lib().zk_g1_decompress, b, 48, 96)
 
 
 def g2_of_json(b):
-    return _decompress(_lib.lib().zk_g2_decompress, b, 192)
+    return _decompress(_lib.lib().zk_g2_decompress, b, 96, 192)
 
 
 # A key is lists of thousands to millions of compressed points: from BATCH_MIN points up a list goes through the GPU in one call
 # (zk_g1/g2_decompress_batch: ~1 s for the five million points of a 2^20 key against half an hour of one host core), shorter ones -- proofs,
-# verification keys, the fixtures of the CPU tests -- through the one-point host calls.  Same checks, same bytes either way.
+# verification keys, the fixtures of the CPU tests -- through the one-point host calls.  Same checks, same bytes either way, and the same error: the
+# verdict of the FIRST string of the list that is refused.
 BATCH_MIN = 256
 
 
-def g1s_of_json(bs):
+def _many(grp, bs, size, one):
     if len(bs) < BATCH_MIN:
-        return b"".join(g1_of_json(b) for b in bs)
-    _need(all(len(b) == 48 for b in bs), "a compressed G1 point is 48 bytes")
-    return G1.of_compressed_bytes_many(b"".join(bs))
+        return b"".join(one(b) for b in bs)
+    for b in bs:
+        _need(isinstance(b, (bytes, bytearray)), "a point is a JSON string")
+        _need(len(b) == size, "a compressed G%d point is %d bytes" % (size // 48, size))
+    try:
+        return grp.of_compressed_bytes_many(b"".join(bs))
+    except _lib.ZkError as e:
+        raise _point_error(e) from None
+
+
+def g1s_of_json(bs):
+    return _many(G1, bs, 48, g1_of_json)
 
 
 def g2s_of_json(bs):
-    if len(bs) < BATCH_MIN:
-        return b"".join(g2_of_json(b) for b in bs)
-    _need(all(len(b) == 96 for b in bs), "a compressed G2 point is 96 bytes")
-    return G2.of_compressed_bytes_many(b"".join(bs))
+    return _many(G2, bs, 96, g2_of_json)
 
 
 # ---- Groth16 (groth16.ml:110-114, 36-43, 24-34)
@@ -274,9 +293,20 @@ def fr_to_json(x):
     return dumps(str(int(x)))        # Z.yojson_of_t: the decimal string
 
 
+_FR_DIGITS = re.compile(rb"-?[0-9]+")
+_FR_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+
+
 @_reader
 def fr_of_json(data):
-    return int(loads(data).decode())
+    """Fr.t_of_yojson = Fr.of_z (Z.of_string s) (curve.ml:140, misc.ml:38): the JSON value is a STRING holding what Z.to_string writes -- ASCII decimal
+    digits with an optional leading '-' -- and Fr.of_z reduces the integer mod r (the curve library documents of_z as accepting any integer and
+    reducing it; taken from its documentation, not its source, which is not part of the reference tree).  Python's int() grammar is wider (surrounding
+    white space, '_' between digits, non-ASCII digits): none of that is what the reference writes, and all of it is refused."""
+    s = loads(data)
+    _need(isinstance(s, bytes), "an Fr element is a JSON string of decimal digits")
+    _need(_FR_DIGITS.fullmatch(s) is not None, "an Fr element is a JSON string of decimal digits")
+    return int(s) % _FR_ORDER
 
 
 # ---- Pinocchio keys (pinocchio.ml:37-60 pkey, :62-75 vkey), record fields in declaration order.
