@@ -6,6 +6,8 @@
  *   NonZK.prove (:536-538, Compute.f :210-248)    the same call with dv = dw = dy = 0
  *   verify  (Verify.f :254-420)    zk_pinocchio_verify on the flattened verification key; a wrong public input is rejected
  *   a long-lived key: zk_pinocchio_pk_derive_lagrange, after which the same calls give the same bytes
+ *   a stored derived key: zk_pinocchio_pk_upload_lagrange takes the evaluation key plus the points [lambda_t(s)] | [Z(s)]
+ *                                  (examples/readme_pinocchio_lagrange_fixture.h) and starts where the derivation ends; one-entry device lists only
  * With arguments -- HIP device indices, e.g. `c_pinocchio 0 1` -- the SAME calls run on a multi-device key: zk_set_device_list cuts every pool of the
  * key over the listed devices behind the one handle (an index may repeat: several shards on one card), and every byte stays the same.
  * on the README circuit `x*x*x + x + 3` (README.md:49).  Every output is compared with the first-principles bytes of
@@ -17,6 +19,7 @@
 #include <string.h>
 
 #include "readme_pinocchio_fixture.h"
+#include "readme_pinocchio_lagrange_fixture.h"
 #include "zkmi355x.h"
 
 #define CHECK(call)                                                                                   \
@@ -105,6 +108,22 @@ int main(int argc, char** argv) {
     CHECK(zk_pinocchio_prove_wait(h, 1, proof));
     SAME(proof, PFIX_PROOF_NONZK, "NonZK proof (slot 1)");
     CHECK(zk_pinocchio_pk_free(h));
+    if (argc <= 1) {
+        /* a host that stored the derived h bases (or knows s) hands them in with the key: the same pool, the same proof, no derivation */
+        CHECK(zk_pinocchio_pk_upload_lagrange(N, M, &L, &R, &O, PFIX_MID, g1, PK1, g2, PK2, PFIX_H_LAGRANGE, &h));
+        CHECK(zk_pinocchio_pool_points(h, 5, pool, sizeof pool / 96, &cnt));
+        if (cnt != sizeof PFIX_DERIVED_H_POOL / 96) { fprintf(stderr, "uploaded Lagrange-form h pool has %lu points\n", (unsigned long)cnt); return 4; }
+        SAME(pool, PFIX_DERIVED_H_POOL, "uploaded Lagrange-form h pool");
+        memset(proof, 0, sizeof proof);
+        CHECK(zk_pinocchio_prove(h, PFIX_WITNESS, PFIX_DELTAS, PFIX_DELTAS + 32, PFIX_DELTAS + 64, proof));
+        SAME(proof, PFIX_PROOF, "ZK proof from the uploaded Lagrange-form key");
+        CHECK(zk_pinocchio_pk_free(h));
+    }
     printf("c-pinocchio ok (%d device entr%s): keygen, ZK / NonZK proofs (uploaded and derived key, blocking and pipelined) and verify equal the first-principles fixture\n", argc > 1 ? argc - 1 : 1, argc > 2 ? "ies" : "y");
+    if (argc <= 1) {
+        printf("proof (upload_lagrange): ");
+        for (i = 0; i < 960; i++) printf("%02x", proof[i]);
+        printf("\n");
+    }
     return 0;
 }

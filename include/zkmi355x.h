@@ -167,6 +167,13 @@ typedef struct {
  * ZK_ERR_ARG for a malformed matrix (row_ptr not monotone, column >= cols), ZK_ERR_SCALAR_RANGE for a value >= r. */
 int zk_fr_spmv(uint32_t rows, uint32_t cols, const zk_csr* M, const uint8_t* x /* cols * 32 */, uint8_t* y /* rows * 32 */);
 
+/* The Lagrange basis of the QAP's integer points first .. first+n-1 (QAP.ml:84,92) at x: out[i] = l_i(x) = prod_{j != i} (x - first - j) / (i - j), i < n, and
+ * z_out (may be NULL) = prod_j (x - first - j) -- what `Poly.apply` of the n interpolation polynomials and of the target gives (QAP.ml:84-100), for EVERY
+ * x < r: the formula divides by nothing that depends on x, so at a point of the domain one value is 1, the others 0 and z = 0.  first = 0 is the
+ * domain of v, w, y; first = n (with n - 1 points) that of the shifted points the Lagrange-form keys carry h on.  Canonical Fr bytes in and out.
+ * ZK_ERR_ARG for n = 0, n > 2^24 or first + n > 2^32; ZK_ERR_SCALAR_RANGE for x >= r. */
+int zk_fr_lagrange_at(uint32_t n, uint32_t first, const uint8_t x[32], uint8_t* out /* n*32 */, uint8_t z_out[32]);
+
 
 /* Proving key of groth16.ml:24-34, fields in declaration order, plus the circuit.
  *   g1: a | d1 | b1 | ti1[n+2] | tiztd[n-1] | ltd_mid[n_mid]   (ltd_mid in Var.Map key order)
@@ -213,6 +220,30 @@ int zk_groth16_pk_install_lagrange(uint64_t handle, const void* d_g1, const void
  * point-sharded multi-GPU prover: the rank keeps its contiguous slice of both pools (same slicing rule as zk_groth16_pk_upload_sharded) and
  * from then on answers zk_groth16_prove_partial*.  How a derived Lagrange-form key reaches N GPUs: every rank uploads, derives, shards. */
 int zk_groth16_pk_shard(uint64_t handle, uint32_t rank, uint32_t world);
+/* ---- key generation in one call (a host that generates its own keys knows the trapdoor) ------------------------------------------------
+ * Groth16 setup, groth16.ml:45-108: every exponent of the key is computed on the device from the trapdoor and the circuit (l_i(tau) as in
+ * zk_fr_lagrange_at, the per-variable L_k(tau) of :59-68 through three transposed sparse products instead of one Poly.apply per variable), every
+ * point comes from the fixed-base kernel (G.of_Fr, curve.ml:180).
+ *   toxic = alpha | beta | gamma | delta | tau, the order Fr.gen is called (:51-55), canonical Fr bytes.
+ *   pk_g1 / pk_g2 (each may be NULL): the key's bytes, ALWAYS in the reference's format -- tau powers, the layouts of zk_groth16_pk_upload, what
+ *     pkey_to_yojson must see; *_points must be 3 + (n+2) + (n-1) + |mids| and 2 + (n+2) where the pointer is given (ZK_ERR_DOMAIN otherwise).
+ *   vk_g1 = one1 | ltgm_io (1 + n_io points, Var order), vk_g2 = one2 | gm | d (groth16.ml:36-43; each may be NULL; ab = e(alpha, beta) is the caller's
+ *     pairing of pk_g1[0] and pk_g2[0], :103).
+ *   handle (may be NULL): a live key handle, as if the bytes had been uploaded -- `form` chooses what it holds: ZK_KEY_FORM_TAU_POWERS what
+ *     zk_groth16_pk_upload would have built, ZK_KEY_FORM_LAGRANGE what upload + zk_groth16_pk_derive_lagrange would (same zk_groth16_pool_points
+ *     bytes, every prove entry point works on it) in the time of a few fixed-base launches.  Bytes and handle come out of ONE pass over the same
+ *     device exponents; the handle's base sets are built from the generated points where they lie (no host round trip, no decoding).  Generated
+ *     points are multiples of the generator: ZK_KEY_SUBGROUP_CHECK does not apply to them.  zk_groth16_pk_free / zk_shutdown as for uploaded keys.
+ * Status: ZK_ERR_ARG for a null L / R / O / mid / toxic, an unknown form, n outside [1, 2^24], m = 0, gamma = 0 or delta = 0 (the reference divides by
+ * them, :70-90), a malformed matrix, and for handle != NULL while the device list has several entries (multi-device keygen is not offered; the
+ * bytes can be had on any list, computed on its first device); ZK_ERR_DOMAIN for a wrong *_points; ZK_ERR_SCALAR_RANGE for a trapdoor scalar or a
+ * matrix coefficient >= r; ZK_ERR_HIP without a GPU -- the argument checks (null, form, counts, trapdoor) come first. */
+#define ZK_KEY_FORM_TAU_POWERS 0
+#define ZK_KEY_FORM_LAGRANGE   1
+int zk_groth16_keygen(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                      const uint8_t toxic[160], uint32_t form,
+                      uint8_t* pk_g1, size_t pk_g1_points, uint8_t* pk_g2, size_t pk_g2_points,
+                      uint8_t* vk_g1 /* (1 + n_io) * 96 */, uint8_t* vk_g2 /* 3 * 192 */, uint64_t* handle);
 /* The key's resident base pool (group 1 or 2) as uncompressed points, in pool order: what was uploaded, or the derived Lagrange-form pool.
  * out == NULL: only *count. */
 int zk_groth16_pool_points(uint64_t handle, int group, uint8_t* out, size_t capacity_points, size_t* count);
@@ -324,6 +355,25 @@ int zk_pinocchio_pk_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr
  * follow: v = kappa_v X^(n-1) + (degree <= n-2), so dw [v(s)] + dv [w(s)] ride on [lambda_t(s)] through the values v(n+t), w(n+t) the prover
  * already extrapolates, plus ONE more base [s^(n-1)] = si[n-1] for the leading coefficients. */
 int zk_pinocchio_pk_derive_lagrange(uint64_t handle);
+/* zk_pinocchio_pk_upload plus the n points h_lagrange = [lambda_t(s)] (n-1) | [Z(s)] (lambda_t the Lagrange basis of the points n .. 2n-2): the first n
+ * points of pool 5 after zk_pinocchio_pk_derive_lagrange, for a host that knows s or stored a derived key.  Runs the ordinary upload (every check,
+ * the one behind the compact h pool included), decodes and checks h_lagrange like any key point (encoding, curve, [r] P = O unless
+ * ZK_KEY_SUBGROUP_CHECK=0), and installs pool 5 exactly as the derivation does: h_lagrange | si[0] | si[n-1], or h_lagrange | si[0] | v_all | w_all for a
+ * full pool.  That h_lagrange belongs to the key's si is the CALLER'S PROMISE, as for zk_groth16_pk_upload_lagrange: the library does not check it, and
+ * points that break it give proofs that do not verify.  Device lists of one entry only (ZK_ERR_ARG otherwise). */
+int zk_pinocchio_pk_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                                    const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points,
+                                    const uint8_t* h_lagrange /* n * 96 */, uint64_t* handle);
+/* KeyGen.generate, pinocchio.ml:77-189, in one call; arguments, forms, handle and status codes as zk_groth16_keygen (no trapdoor value is refused
+ * but one >= r: the reference divides by none).
+ *   toxic = rv | rw | s | av | aw | ay | b | gm (:83-91);  pk_g1 / pk_g2: the layouts of zk_pinocchio_pk_upload, 5 |mids| + (n+1) + 2m + 7 and
+ *   2 |mids| + (n+1) + 2 points;  vk_g1 = one | aw | bgm | vv_io | yy_io (3 + 2 n_io), vk_g2 = one2 | av | ay | gm2 | bgm2 | yt | ww_io (6 + n_io), :62-75.
+ *   The handle's h pool is compact whenever ZK_PIN_COMPACT_H allows it: a generated key satisfies the relation behind it by construction, so the
+ *   check of the upload is not run; ZK_PIN_SHARED_SORT is decided as at upload.  ZK_KEY_FORM_LAGRANGE: pool 5 as after zk_pinocchio_pk_derive_lagrange. */
+int zk_pinocchio_keygen(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                        const uint8_t toxic[256], uint32_t form,
+                        uint8_t* pk_g1, size_t pk_g1_points, uint8_t* pk_g2, size_t pk_g2_points,
+                        uint8_t* vk_g1 /* (3 + 2 n_io) * 96 */, uint8_t* vk_g2 /* (6 + n_io) * 192 */, uint64_t* handle);
 /* A resident base pool of the key as uncompressed points, in pool order (out == NULL: only *count).  Pools 0..5 are the G1 products
  * vv|vt, yy|yt, vav|vavt, yay|yayt, bvwy|vbt|wbt|ybt and the h pool; 6..7 the G2 products ww|wt and waw|wawt (pinocchio.ml:37-60).
  * The h pool by key form:  compact (default): si (n + 1 points); after zk_pinocchio_pk_derive_lagrange [lambda_t(s)] (n-1) | [Z(s)] | [1] | [s^(n-1)];

@@ -11,7 +11,8 @@
      prove   groth16.ml:235-237 + Base.prove :123-161 + sum_apply_powers :116-121 + QAP.eval (QAP.ml:120-135)
              -> one call zk_groth16_prove on a key uploaded once; r and s are drawn HERE, r first (:124-125)
      keygen  groth16.ml:227-233 + setup :45-108
-             -> same exponents, all [x]_1 / [x]_2 in two fixed-base launches; registers the circuit with the library
+             -> one call zk_groth16_keygen: the trapdoor is drawn HERE in the reference's order (:51-55), exponents and points are the device's;
+                the key's bytes and a live handle in Lagrange form come back (a multi-device list: the bytes, then the ordinary upload)
      verify  groth16.ml:163-173 -> unchanged in substance: three pairings of the host's own Pairing
    The records and their yojson are the reference's (groth16.ml:24-43,110-114): the JSON of keys and proofs is the wire format. *)
 
@@ -123,9 +124,8 @@ module Make (C : Curve.S) = struct
     Handles.replace handles pkey h;
     h
 
-  let register_circuit (circuit : circuit) (qap : qap) (pkey : pkey) =
-    let vars = List.map fst (Var.Map.bindings qap.v) in
-    ignore (upload vars (matrices_of_gates (index_of_vars vars) circuit.Circuit.gates) (Poly.degree qap.QAP.target) pkey)
+  (* a key whose bytes exist on the host -- read from JSON, or generated while the device list had several entries -- enters the library here *)
+  let register = upload
 
   let handle_of (qap : qap) (pkey : pkey) =
     match Handles.find_opt handles pkey with
@@ -144,52 +144,57 @@ module Make (C : Curve.S) = struct
     let gamma = Fr.gen rng in
     let delta = Fr.gen rng in
     let tau = Fr.gen rng in
-    let at_tau p = Poly.apply p tau in
-    (* L_k(tau) = beta v_k(tau) + alpha w_k(tau) + y_k(tau) *)
-    let l_tau =
-      Var.Map.mapi
-        (fun k vk -> Fr.((beta * at_tau vk) + (alpha * at_tau (Var.Map.find k qap.w)) + at_tau (Var.Map.find k qap.y)))
-        qap.v
+    (* ONE library call (zk_groth16_keygen): every exponent of groth16.ml:59-90 is computed on the device from the trapdoor and the circuit's
+       rows, every point by the fixed-base kernel.  The bytes that come back are the key in the reference's format; the handle that comes back
+       with them already holds the key's Lagrange form (the fast prover's), so nothing is sent or derived a second time -- on a device list of one
+       entry; on a longer list no handle is offered and the bytes are registered like a key read from JSON (below). *)
+    let vars = List.map fst (Var.Map.bindings qap.v) in
+    let m = List.length vars in
+    let is_mid v = Var.Set.mem v circuit.Circuit.mids in
+    let mids = List.filter is_mid vars and ios = List.filter (fun v -> not (is_mid v)) vars in
+    let io_set = Var.Set.union circuit.Circuit.inputs_public circuit.Circuit.outputs in
+    if not (List.for_all (fun v -> Var.Set.mem v io_set) ios) then assert false;
+    let mid = Mi355x.cat (List.map (fun v -> Bytes.make 1 (if is_mid v then '\001' else '\000')) vars) in
+    let n_ti = n + 2 and n_tiz = max (n - 1) 0 and n_mid = List.length mids and n_io = List.length ios in
+    let l, r, o = matrices_of_gates (index_of_vars vars) circuit.Circuit.gates in
+    let p1, p2, v1, v2, h =
+      Mi355x.keygen_call Mi355x.zk_groth16_keygen ~n ~m l r o ~mid
+        ~toxic:(fr_bytes [ alpha; beta; gamma; delta; tau ])
+        ~form:Mi355x.key_form_lagrange
+        ~g1_points:(3 + n_ti + n_tiz + n_mid)
+        ~g2_points:(2 + n_ti) ~vk1_points:(1 + n_io) ~vk2_points:3
     in
-    let io = Var.Set.union circuit.Circuit.inputs_public circuit.Circuit.outputs in
-    let over set divisor = Var.Map.map (fun x -> Fr.(x / divisor)) (Var.Map.restrict set l_tau) in
-    let l_mid = over circuit.Circuit.mids delta and l_io = over io gamma in
-    let tau_powers count =
-      let rec go acc x i = if i = count then List.rev acc else go (x :: acc) Fr.(x * tau) (i + 1) in
-      go [] Fr.one 0
-    in
-    let z_over_delta = Fr.(at_tau qap.target / delta) in
-    let ti = tau_powers (n + 2) in
-    let tiz = List.map (fun x -> Fr.(x * z_over_delta)) (tau_powers (n - 1)) in
-    (* every G1 element of both keys in ONE fixed-base launch, every G2 element in another *)
-    let e1 = (alpha :: delta :: beta :: ti) @ tiz @ values l_mid @ values l_io in
-    let e2 = (beta :: delta :: gamma :: ti) in
-    let p1 = Mi355x.of_fr_many ~g2:false (fr_bytes e1) and p2 = Mi355x.of_fr_many ~g2:true (fr_bytes e2) in
-    let n_ti = n + 2 and n_tiz = max (n - 1) 0 and n_mid = Var.Map.cardinal l_mid in
     let take b at off count = List.init count (fun i -> at b (off + i)) in
-    let rekey m points = Var.Map.of_list (List.map2 (fun (k, _) p -> (k, p)) (Var.Map.bindings m) points) in
+    let rekey ks points = Var.Map.of_list (List.combine ks points) in
     let pkey : pkey =
       { a = g1_at p1 0;
         d1 = g1_at p1 1;
         b1 = g1_at p1 2;
         ti1 = take p1 g1_at 3 n_ti;
         tiztd = take p1 g1_at (3 + n_ti) n_tiz;
-        ltd_mid = rekey l_mid (take p1 g1_at (3 + n_ti + n_tiz) n_mid);
+        ltd_mid = rekey mids (take p1 g1_at (3 + n_ti + n_tiz) n_mid);
         b2 = g2_at p2 0;
         d2 = g2_at p2 1;
-        ti2 = take p2 g2_at 3 n_ti
+        ti2 = take p2 g2_at 2 n_ti
       }
     in
     let vkey : vkey =
-      { one1 = G1.one;
-        ltgm_io = rekey l_io (take p1 g1_at (3 + n_ti + n_tiz + n_mid) (Var.Map.cardinal l_io));
-        one2 = G2.one;
-        gm = g2_at p2 2;
-        d = pkey.d2;
+      { one1 = g1_at v1 0;
+        ltgm_io = rekey ios (take v1 g1_at 1 n_io);
+        one2 = g2_at v2 0;
+        gm = g2_at v2 1;
+        d = g2_at v2 2;
         ab = Pairing.pairing pkey.a pkey.b2
       }
     in
-    register_circuit circuit qap pkey;
+    (match h with
+    | Some h ->
+        Gc.finalise (fun _ -> ignore (Mi355x.zk_groth16_pk_free h)) pkey;
+        Handles.replace handles pkey h
+    | None ->
+        (* a device list of several entries (Mi355x.use_all_devices): the generated bytes go through zk_groth16_pk_upload, which shards the key over
+           the list behind one handle; derive_lagrange_on_upload applies to it as to any uploaded key *)
+        ignore (register vars (l, r, o) n pkey));
     (pkey, vkey)
 
   (* ---------------------------------------------------------------- prove *)

@@ -65,6 +65,13 @@ let zk_init = fn "zk_init" (int @-> returning int)
 let zk_shutdown = fn "zk_shutdown" (void @-> returning int)
 let zk_set_devices = fn "zk_set_devices" (uint64_t @-> returning int)
 let zk_sync = fn "zk_sync" (void @-> returning int)
+let zk_get_device_list = fn "zk_get_device_list" (ptr int32_t @-> uint32_t @-> ptr uint32_t @-> returning int)
+
+(* entries of the library's device list (0 before the first call that binds a device): more than one after zk_set_devices / use_all_devices *)
+let device_list_length () =
+  let n = allocate uint32_t Unsigned.UInt32.zero in
+  check (zk_get_device_list (from_voidp int32_t null) (u32 0) n);
+  Unsigned.UInt32.to_int !@n
 
 (* knobs that are not test-only, by name (the environment stays a fallback): see the header *)
 let zk_set_option = fn "zk_set_option" (string @-> string @-> returning int)
@@ -188,6 +195,46 @@ let matrix_of_rows (rows : (int * bytes) list list) : matrix =
    tau -- every u_k(tau) of a keygen at once, where the reference runs Poly.apply per variable *)
 let zk_fr_spmv = fn "zk_fr_spmv" (uint32_t @-> uint32_t @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> returning int)
 
+(* l_i(x), i < n, over the QAP's points first .. first+n-1 and Z(x) (header: zk_fr_lagrange_at): what Poly.apply gives for the n interpolation
+   polynomials and the target (QAP.ml:84-100), exact for every x, the domain's own points included *)
+let zk_fr_lagrange_at = fn "zk_fr_lagrange_at" (uint32_t @-> uint32_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> returning int)
+
+let lagrange_at ~n ~first (x : bytes) : bytes * bytes =
+  let out = Bytes.create (32 * n) and z = Bytes.create 32 in
+  check (zk_fr_lagrange_at (u32 n) (u32 first) (bytes_start x) (bytes_start out) (bytes_start z));
+  (out, z)
+
+(* ------------------------------------------------------------------ key generation in one call (header: zk_groth16_keygen, zk_pinocchio_keygen)
+   groth16.ml:45-108 and pinocchio.ml:77-189: the trapdoor goes in (canonical Fr bytes, in the order Fr.gen is called), the key's bytes in the
+   reference's format come out together with a live handle -- ZK_KEY_FORM_LAGRANGE: the handle already holds the Lagrange form, the fast prover's. *)
+
+let key_form_tau_powers = 0
+let key_form_lagrange = 1
+
+let zk_groth16_keygen =
+  fn "zk_groth16_keygen"
+    (uint32_t @-> uint32_t @-> ptr csr @-> ptr csr @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> size_t
+   @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ocaml_bytes @-> ptr uint64_t @-> returning int)
+
+let zk_pinocchio_keygen =
+  fn "zk_pinocchio_keygen"
+    (uint32_t @-> uint32_t @-> ptr csr @-> ptr csr @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> size_t
+   @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ocaml_bytes @-> ptr uint64_t @-> returning int)
+
+(* one keygen call: (pk_g1, pk_g2, vk_g1, vk_g2, handle option); the *_points are the lengths the header gives for this circuit.  A handle can only
+   be had on a device list of ONE entry (header); on a longer list -- after use_all_devices -- the call is made with handle = NULL (the bytes can
+   be had on any list) and returns None: the caller then uploads the bytes, which builds the multi-device key behind one handle as before. *)
+let keygen_call f ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(toxic : bytes) ~form ~g1_points ~g2_points ~vk1_points ~vk2_points =
+  let g1 = Bytes.create (96 * g1_points) and g2 = Bytes.create (192 * g2_points) in
+  let vk1 = Bytes.create (96 * vk1_points) and vk2 = Bytes.create (192 * vk2_points) in
+  let want_handle = device_list_length () <= 1 in
+  let h = allocate uint64_t Unsigned.UInt64.zero in
+  check
+    (f (u32 n) (u32 m) (addr l.c) (addr r.c) (addr o.c) (bytes_start mid) (bytes_start toxic) (u32 form) (bytes_start g1) (sz g1_points)
+       (bytes_start g2) (sz g2_points) (bytes_start vk1) (bytes_start vk2)
+       (if want_handle then h else from_voidp uint64_t null));
+  (g1, g2, vk1, vk2, if want_handle then Some !@h else None)
+
 (* ------------------------------------------------------------------ Groth16: groth16.ml:24-34,116-161,235-237 *)
 
 let zk_groth16_pk_upload =
@@ -255,6 +302,12 @@ let zk_pinocchio_prove_wait = fn "zk_pinocchio_prove_wait" (uint64_t @-> uint32_
 
 let zk_pinocchio_verify =
   fn "zk_pinocchio_verify" (ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ptr int @-> returning int)
+
+(* zk_pinocchio_pk_upload plus the stored h bases [lambda_t(s)] (n-1) | [Z(s)] of a derived key (header): the key starts in its derived form *)
+let zk_pinocchio_pk_upload_lagrange =
+  fn "zk_pinocchio_pk_upload_lagrange"
+    (uint32_t @-> uint32_t @-> ptr csr @-> ptr csr @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> size_t
+   @-> ocaml_bytes @-> ptr uint64_t @-> returning int)
 
 let pinocchio_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in

@@ -7,8 +7,8 @@
      ZK.prove     pinocchio.ml:559-561 + ZKCompute.f :427-514 + QAP.eval  -> zk_pinocchio_prove; dv, dw, dy drawn HERE in the
                   order of :428-430
      NonZK.prove  pinocchio.ml:536-538 + Compute.f :210-248                -> the same call with dv = dw = dy = 0 (no rng use)
-     keygen       pinocchio.ml:530-534 + KeyGen.generate :77-189           -> same exponents (rv, rw, s, av, aw, ay, b, gm drawn
-                  in the order of :83-91), every key point in two fixed-base launches
+     keygen       pinocchio.ml:530-534 + KeyGen.generate :77-189           -> one call zk_pinocchio_keygen (rv, rw, s, av, aw, ay, b, gm drawn
+                  HERE in the order of :83-91; exponents and points are the device's; a multi-device list: the bytes, then the ordinary upload)
      verify       pinocchio.ml:540-541,563 + Verify.f :254-420             -> zk_pinocchio_verify (13 pairings on the host, in the
                   library: it takes only G1 / G2 points, so no GT encoding is involved).  Where the reference `assert`s the
                   four knowledge-of-coefficient checks and returns the divisibility check, this returns false for any failing
@@ -143,6 +143,9 @@ module Make (C : Curve.S) = struct
     Handles.replace handles k h;
     h
 
+  (* a key whose bytes exist on the host -- read from JSON, or generated while the device list had several entries -- enters the library here *)
+  let register = upload
+
   let handle_of (qap : qap) (k : pkey) =
     match Handles.find_opt handles k with
     | Some h -> h
@@ -163,52 +166,32 @@ module Make (C : Curve.S) = struct
     let ay = Fr.gen rng in
     let b = Fr.gen rng in
     let gm = Fr.gen rng in
-    let ry = Fr.(rv * rw) in
-    let t = Poly.apply qap.QAP.target s in
-    let at_s polys = Var.Map.map (fun p -> Poly.apply p s) polys in
-    let v_s = at_s qap.QAP.v and w_s = at_s qap.QAP.w and y_s = at_s qap.QAP.y in
+    (* ONE library call (zk_pinocchio_keygen): the exponents of pinocchio.ml:93-175 on the device, the points by the fixed-base kernel; the
+       bytes are the evaluation and verification keys in the reference's format, the handle already holds the derived h pool (a device list of
+       one entry; on a longer list no handle is offered and the bytes are registered like a key read from JSON, below). *)
+    let vars = keys qap.QAP.v in
+    let m = List.length vars in
     let mids = circuit.Circuit.mids and ios = Circuit.ios circuit in
-    let scaled set f m = values (Var.Map.map (fun x -> Fr.(x * f)) (Var.Map.restrict set m)) in
-    let s_powers =
-      let rec go acc x i = if i > n then List.rev acc else go (x :: acc) Fr.(x * s) (i + 1) in
-      go [] Fr.one 0
+    let n_mid = Var.Set.cardinal mids and n_io = Var.Set.cardinal ios in
+    if n_mid + n_io <> m then assert false;
+    let mid = Mi355x.cat (List.map (fun v -> Bytes.make 1 (if Var.Set.mem v mids then '\001' else '\000')) vars) in
+    let l, r, o = matrices_of_gates (index_of_vars vars) circuit.Circuit.gates in
+    let p1, p2, v1, v2, h =
+      Mi355x.keygen_call Mi355x.zk_pinocchio_keygen ~n ~m l r o ~mid
+        ~toxic:(fr_bytes [ rv; rw; s; av; aw; ay; b; gm ])
+        ~form:Mi355x.key_form_lagrange
+        ~g1_points:((5 * n_mid) + n + 1 + (2 * m) + 7)
+        ~g2_points:((2 * n_mid) + n + 1 + 2)
+        ~vk1_points:(3 + (2 * n_io))
+        ~vk2_points:(6 + n_io)
     in
-    let vt = Fr.(rv * t) and wt = Fr.(rw * t) and yt = Fr.(ry * t) in
-    let n_mid = Var.Set.cardinal mids and n_io = Var.Set.cardinal ios and m = Var.Map.cardinal v_s in
-    let combined =
-      List.map
-        (fun k -> Fr.(((rv * Var.Map.find k v_s) + (rw * Var.Map.find k w_s) + (ry * Var.Map.find k y_s)) * b))
-        (Var.Set.elements mids)
-    in
-    let e1 =
-      scaled mids rv v_s @ scaled mids ry y_s
-      @ scaled mids Fr.(rv * av) v_s
-      @ scaled mids Fr.(ry * ay) y_s
-      @ combined @ s_powers @ values v_s @ values w_s
-      @ [ vt; yt; Fr.(vt * av); Fr.(yt * ay); Fr.(vt * b); Fr.(wt * b); Fr.(yt * b) ]
-      (* verification key, G1 part *)
-      @ [ aw; Fr.(gm * b) ]
-      @ scaled ios rv v_s @ scaled ios ry y_s
-    in
-    let e2 =
-      scaled mids rw w_s
-      @ scaled mids Fr.(rw * aw) w_s
-      @ s_powers
-      @ [ wt; Fr.(wt * aw) ]
-      (* verification key, G2 part *)
-      @ [ av; ay; gm; Fr.(gm * b); yt ]
-      @ scaled ios rw w_s
-    in
-    let p1 = Mi355x.of_fr_many ~g2:false (fr_bytes e1) and p2 = Mi355x.of_fr_many ~g2:true (fr_bytes e2) in
     let map_of set at buf off = Var.Map.of_list (List.mapi (fun i k -> (k, at buf (off + i))) (Var.Set.elements set)) in
-    let all_vars = Var.Map.domain v_s in
+    let all_vars = Var.Set.of_list vars in
     let o_si = 5 * n_mid in
     let o_all = o_si + n + 1 in
     let o_single = o_all + (2 * m) in
-    let o_vk = o_single + 7 in
     let o2_si = 2 * n_mid in
     let o2_single = o2_si + n + 1 in
-    let o2_vk = o2_single + 2 in
     let pkey : pkey =
       { vv = map_of mids g1_at p1 0;
         yy = map_of mids g1_at p1 n_mid;
@@ -233,22 +216,28 @@ module Make (C : Curve.S) = struct
       }
     in
     let vkey : vkey =
-      { one = G1.one;
-        one2 = G2.one;
-        aw = g1_at p1 o_vk;
-        bgm = g1_at p1 (o_vk + 1);
-        vv_io = map_of ios g1_at p1 (o_vk + 2);
-        yy_io = map_of ios g1_at p1 (o_vk + 2 + n_io);
-        av = g2_at p2 o2_vk;
-        ay = g2_at p2 (o2_vk + 1);
-        gm2 = g2_at p2 (o2_vk + 2);
-        bgm2 = g2_at p2 (o2_vk + 3);
-        yt = g2_at p2 (o2_vk + 4);
-        ww_io = map_of ios g2_at p2 (o2_vk + 5)
+      { one = g1_at v1 0;
+        one2 = g2_at v2 0;
+        aw = g1_at v1 1;
+        bgm = g1_at v1 2;
+        vv_io = map_of ios g1_at v1 3;
+        yy_io = map_of ios g1_at v1 (3 + n_io);
+        av = g2_at v2 1;
+        ay = g2_at v2 2;
+        gm2 = g2_at v2 3;
+        bgm2 = g2_at v2 4;
+        yt = g2_at v2 5;
+        ww_io = map_of ios g2_at v2 6
       }
     in
-    let vars = keys qap.QAP.v in
-    ignore (upload vars (matrices_of_gates (index_of_vars vars) circuit.Circuit.gates) n pkey);
+    (match h with
+    | Some h ->
+        Gc.finalise (fun _ -> ignore (Mi355x.zk_pinocchio_pk_free h)) pkey;
+        Handles.replace handles pkey h
+    | None ->
+        (* a device list of several entries (Mi355x.use_all_devices): the generated bytes go through zk_pinocchio_pk_upload, which cuts every pool over
+           the list behind one handle; derive_lagrange_on_upload applies to it as to any uploaded key *)
+        ignore (register vars (l, r, o) n pkey));
     (pkey, vkey)
 
   (* ---------------------------------------------------------------- prove *)

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("ZK_LIBZKMI355X_PATH") or os.path.join(_HERE, "libzkmi
 # every symbol include/zkmi355x.h declares (checked by tests/test_abi.py without a GPU)
 EXPORTS = [
     "zk_strerror", "zk_last_error", "zk_device_count", "zk_init", "zk_shutdown", "zk_set_devices", "zk_set_device_list", "zk_get_device_list", "zk_set_option",
-    "zk_fr_ntt", "zk_fr_poly_mul", "zk_fr_spmv", "zk_msm_g1", "zk_msm_g2",
+    "zk_fr_ntt", "zk_fr_poly_mul", "zk_fr_spmv", "zk_fr_lagrange_at", "zk_msm_g1", "zk_msm_g2",
     "zk_bases_upload", "zk_bases_info", "zk_bases_free", "zk_msm_resident", "zk_msm_resident_many", "zk_g1_of_fr", "zk_g2_of_fr",
     "zk_g1_powers", "zk_g2_powers", "zk_g1_compress", "zk_g2_compress", "zk_g1_decompress", "zk_g2_decompress", "zk_g1_decompress_batch", "zk_g2_decompress_batch",
     "zk_groth16_pk_upload", "zk_groth16_pk_upload_lagrange", "zk_groth16_pk_derive_lagrange", "zk_groth16_lagrange_pool_sizes", "zk_groth16_pk_derive_lagrange_sets", "zk_groth16_pk_install_lagrange", "zk_groth16_pk_shard", "zk_groth16_shard_range", "zk_groth16_pool_points", "zk_groth16_pk_free", "zk_groth16_prove", "zk_groth16_reserve_slots", "zk_groth16_prove_async", "zk_groth16_prove_wait", "zk_groth16_set_witness", "zk_groth16_qap_eval",
@@ -23,6 +23,7 @@ EXPORTS = [
     "zk_device_malloc", "zk_device_free", "zk_device_memcpy",
     "zk_pinocchio_pk_upload", "zk_pinocchio_pk_derive_lagrange", "zk_pinocchio_pool_points", "zk_pinocchio_pk_free", "zk_pinocchio_prove",
     "zk_pinocchio_reserve_slots", "zk_pinocchio_set_witness", "zk_pinocchio_prove_async", "zk_pinocchio_prove_wait",
+    "zk_groth16_keygen", "zk_pinocchio_keygen", "zk_pinocchio_pk_upload_lagrange",
     "zk_pairing_product", "zk_pairing_check", "zk_groth16_verify", "zk_pinocchio_verify",
     "zk_profile_enable", "zk_profile_reset", "zk_profile_get", "zk_profile_names", "zk_profile_counter", "zk_sync",
     "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_sqrt",
@@ -39,6 +40,18 @@ class CSR(C.Structure):
     _fields_ = [("row_ptr", C.POINTER(C.c_uint32)), ("col", C.POINTER(C.c_uint32)), ("val", C.POINTER(C.c_uint8))]
 
 
+_P8, _PCSR, _PH = C.POINTER(C.c_uint8), C.POINTER(CSR), C.POINTER(C.c_uint64)
+_KEYGEN = [C.c_uint32, C.c_uint32, _PCSR, _PCSR, _PCSR, _P8, _P8, C.c_uint32, _P8, C.c_size_t, _P8, C.c_size_t, _P8, _P8, _PH]
+# argument types of the key-generation entries, in the header's order (tests/test_keygen_surface.py holds them to include/zkmi355x.h); ctypes then checks
+# every call against them.  The older entries are called with explicitly typed ctypes values.
+PROTOTYPES = {
+    "zk_fr_lagrange_at": [C.c_uint32, C.c_uint32, _P8, _P8, _P8],
+    "zk_groth16_keygen": _KEYGEN,
+    "zk_pinocchio_keygen": _KEYGEN,
+    "zk_pinocchio_pk_upload_lagrange": [C.c_uint32, C.c_uint32, _PCSR, _PCSR, _PCSR, _P8, _P8, C.c_size_t, _P8, C.c_size_t, _P8, _PH],
+}
+KEY_FORMS = {"tau_powers": 0, "lagrange": 1}          # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
+
 _lib = None
 
 
@@ -52,6 +65,10 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
+        for name, args in PROTOTYPES.items():
+            fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
+            if fn is not None:
+                fn.argtypes, fn.restype = args, C.c_int
     return _lib
 
 

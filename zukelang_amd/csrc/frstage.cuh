@@ -61,6 +61,12 @@ int frstage_shifted_powers(void* d_out, uint32_t n, uint32_t e, uint32_t cnt, hi
 // subproduct-tree tables over the points offset .. offset + n2 - 1 (plain Montgomery form, see frstage.hip)
 int frstage_tree_tables(uint32_t n2, uint32_t log_n2, uint32_t offset, void* pntt, DevBuf& q, hipStream_t s, std::vector<DevBuf>* p_rns = nullptr, uint32_t rns_first_level = 0);
 
+// pieces of the stage that key generation (keygen.hip) runs on their own: a matrix on the device (validated like the key's own: ZK_ERR_ARG for a
+// malformed one, ZK_ERR_SCALAR_RANGE for a coefficient >= r), out = M x over its rows (x, out Montgomery, on the device), and the table 1/i!, i < count
+int frstage_upload_csr(CsrDev& d, const zk_csr* h, uint32_t rows, uint32_t cols, hipStream_t s);
+int frstage_spmv(const CsrDev& d, uint32_t rows, const void* d_x, void* d_out, hipStream_t s);
+int frstage_invfact(void* d_invfact, uint32_t count, hipStream_t s);
+
 // a*b via NTT on device (Montgomery in/out); out must hold na+nb-1 elements
 int dev_poly_mul(const void* d_a, uint64_t na, const void* d_b, uint64_t nb, void* d_out, hipStream_t s);
 

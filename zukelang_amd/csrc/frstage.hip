@@ -676,6 +676,28 @@ int frstage_shifted_powers(void* d_out, uint32_t n, uint32_t e, uint32_t cnt, hi
     return ZK_OK;
 }
 
+// ---- pieces of the stage that key generation (keygen.hip) runs on their own
+int frstage_upload_csr(CsrDev& d, const zk_csr* h, uint32_t rows, uint32_t cols, hipStream_t s) { return upload_csr(d, h, rows, cols, s); }
+// out = M x over `rows` rows of an uploaded matrix; x and out in Montgomery form on the device
+int frstage_spmv(const CsrDev& d, uint32_t rows, const void* d_x, void* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(k_spmv, g1d(rows), dim3(256), 0, s, (const uint32_t*)FRP(d.ptr), (const uint32_t*)FRP(d.col), (const uint32_t*)FRP(d.val), (const uint32_t*)d_x, (uint32_t*)d_out, rows);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// d_invfact[i] = 1/i! for i < count (Montgomery): the table of frstage_init, for callers that have no key yet
+int frstage_invfact(void* d_invfact, uint32_t count, hipStream_t s) {
+    const uint32_t nch = (count + FCH - 1) / FCH;
+    DevBuf prod, alt;
+    ZKCHK(prod.alloc(32 * (size_t)nch));
+    ZKCHK(alt.alloc(32 * (size_t)count));
+    hipLaunchKernelGGL(k_fact_chunk_prod, g1d(nch, 64), dim3(64), 0, s, FRP(prod), count);
+    hipLaunchKernelGGL(k_fact_chunk_scan, dim3(1), dim3(64), 0, s, FRP(prod), nch);
+    hipLaunchKernelGGL(k_invfact, g1d(nch, 64), dim3(64), 0, s, (uint32_t*)d_invfact, FRP(alt), (const uint32_t*)FRP(prod), count);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));          // prod and alt die with this frame
+    return ZK_OK;
+}
+
 }  // namespace zk
 
 using namespace zk;

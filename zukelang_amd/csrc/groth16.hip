@@ -161,8 +161,12 @@ static uint32_t key_window(uint64_t g1_points, bool in_subgroup) {
     return msm_auto_window(g1_points, true);
 }
 int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
-                      const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, bool lagrange, bool shard_of_group) {
-    if (!mid || !pk_g1 || !pk_g2 || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "pk_upload: null argument");
+                      const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, bool lagrange, bool shard_of_group,
+                      const void* d_g1, const void* d_g2) {
+    // d_g1 / d_g2 (both or neither): the pools as dense affine points in device memory, computed by the library itself (keygen.hip) -- pk_g1 / pk_g2 are
+    // then not read
+    const bool generated = d_g1 && d_g2;
+    if (!mid || (!generated && (!pk_g1 || !pk_g2)) || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "pk_upload: null argument");
     if (world == 0 || rank >= world) ZK_FAIL(ZK_ERR_ARG, "pk_upload: bad rank / world");
     ZKCHK(ensure_init());
     Ctx& c = ctx();
@@ -196,10 +200,18 @@ int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, 
     // (zk_set_option "key_subgroup_check") skips the subgroup part for keys that were checked before (it is [r] P = O per point: 0.3 s at 2^20
     // constraints, 1.4 s at 2^22).  Read per key (set-up path).  A key uploaded without the check never gets folded windows: msm.cuh.
     const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    const bool chk = !(e_chk && atoi(e_chk) == 0);
+    const bool chk = generated || !(e_chk && atoi(e_chk) == 0);
     const uint32_t cw = key_window(k.hi1 - k.lo1, chk);
-    ZKCHK(msm_bases_from_bytes(k.g1, CURVE_G1, pk_g1 + 96 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, chk));
-    ZKCHK(msm_bases_from_bytes(k.g2, CURVE_G2, pk_g2 + 192 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, chk));
+    if (generated) {
+        // in_subgroup = true without the [r] P = O test, and so folded windows (msm.cuh: msm_fold): every point of a generated key is [e] G for an
+        // exponent the library computed itself, a multiple of the generator of the prime-order group.  ZK_KEY_SUBGROUP_CHECK governs points that come
+        // from outside; there are none here.
+        ZKCHK(msm_bases_from_device_affine(k.g1, CURVE_G1, (const uint8_t*)d_g1 + 96 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, true));
+        ZKCHK(msm_bases_from_device_affine(k.g2, CURVE_G2, (const uint8_t*)d_g2 + 192 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, true));
+    } else {
+        ZKCHK(msm_bases_from_bytes(k.g1, CURVE_G1, pk_g1 + 96 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, chk));
+        ZKCHK(msm_bases_from_bytes(k.g2, CURVE_G2, pk_g2 + 192 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, chk));
+    }
     ZKCHK(k.mid_idx.alloc(4 * (size_t)(k.n_mid ? k.n_mid : 1)));
     if (k.n_mid) HIPCHK(hipMemcpyAsync(k.mid_idx.p, mids.data(), 4 * (size_t)k.n_mid, hipMemcpyHostToDevice, c.stream));
     ZKCHK(k.wit_resident.alloc(32 * (size_t)m));
@@ -219,6 +231,15 @@ static int upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, cons
     if (whole && ctx_count() > 1) return group_upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, lagrange, handle);
     std::unique_ptr<Groth16Key> key;
     ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, rank, world, lagrange));
+    *handle = g_next_handle++;
+    g_keys[*handle] = std::move(key);
+    return ZK_OK;
+}
+// a key whose pools the library computed itself (keygen.hip: dense affine points in device memory, pool order) under a handle of its own
+int groth16_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const void* d_g1, size_t g1_points,
+                            const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle) {
+    std::unique_ptr<Groth16Key> key;
+    ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, nullptr, g1_points, nullptr, g2_points, 0, 1, lagrange, false, d_g1, d_g2));
     *handle = g_next_handle++;
     g_keys[*handle] = std::move(key);
     return ZK_OK;

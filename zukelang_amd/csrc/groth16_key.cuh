@@ -58,7 +58,10 @@ struct Groth16Key {
 // Builds a key (whole: rank 0 of world 1, or rank's shard) on the CURRENT virtual device; nothing is registered under a handle.
 int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
                       const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, bool lagrange,
-                      bool shard_of_group = false);
+                      bool shard_of_group = false, const void* d_g1 = nullptr, const void* d_g2 = nullptr);
+// keygen.hip: a whole key from pools the library generated on the device (dense affine points, pool order), registered under a new handle
+int groth16_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const void* d_g1, size_t g1_points,
+                            const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle);
 int groth16_slot_get(Groth16Key& k, uint32_t idx, Slot** out);
 // host half of a proof's inputs (witness handed over as a host buffer, r, s) into the slot's pinned staging memory; fails when the slot is busy
 int groth16_stage_inputs(Groth16Key& k, Slot& sl, const uint8_t* sol, const uint8_t* r, const uint8_t* s);

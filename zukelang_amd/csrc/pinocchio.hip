@@ -284,6 +284,22 @@ static inline void pin_slice(uint64_t full, uint32_t rank, uint32_t world, uint6
     *hi = full * (rank + 1) / world;
 }
 
+// which products read another product's sort (PinKey::share1 / share2), decided per key once its base sets exist
+static int pin_decide_shared_sort(PinKey& k, hipStream_t s) {
+    const char* e = ::zk::opt("ZK_PIN_SHARED_SORT");          // 0: every product sorts for itself (A/B, tests)
+    if (e && atoi(e) == 0) return ZK_OK;
+    auto try_share = [&](const MsmBases& a, const MsmBases& b, int* slot, int from) -> int {
+        if (!a.n || !b.n) return ZK_OK;
+        bool same = false;
+        ZKCHK(msm_bases_same_geometry(a, b, &same, s));
+        if (same) *slot = from;
+        return ZK_OK;
+    };
+    ZKCHK(try_share(k.g1[0], k.g1[2], &k.share1[2], 0));
+    ZKCHK(try_share(k.g1[1], k.g1[3], &k.share1[3], 1));
+    ZKCHK(try_share(k.g2[0], k.g2[1], &k.share2[1], 0));
+    return ZK_OK;
+}
 // Builds a key -- whole (rank 0 of world 1) or rank's shard -- on the CURRENT virtual device; nothing is registered under a handle.
 // compact_in: -1 = decide here (the upload's consistency check of v_all / w_all against si, header comment: needs the WHOLE h pool, so rank 0 of a
 // group runs it and hands its verdict to the other shards), 0 / 1 = the verdict.
@@ -359,21 +375,7 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
     };
     ZKCHK(pool2(0, WW, ONES2));
     ZKCHK(pool2(1, WAW, ONES2 + 192));
-    {
-        const char* e = ::zk::opt("ZK_PIN_SHARED_SORT");          // 0: every product sorts for itself (A/B, tests)
-        if (!(e && atoi(e) == 0)) {
-            auto try_share = [&](const MsmBases& a, const MsmBases& b, int* slot, int from) -> int {
-                if (!a.n || !b.n) return ZK_OK;
-                bool same = false;
-                ZKCHK(msm_bases_same_geometry(a, b, &same, c.stream));
-                if (same) *slot = from;
-                return ZK_OK;
-            };
-            ZKCHK(try_share(k.g1[0], k.g1[2], &k.share1[2], 0));
-            ZKCHK(try_share(k.g1[1], k.g1[3], &k.share1[3], 1));
-            ZKCHK(try_share(k.g2[0], k.g2[1], &k.share2[1], 0));
-        }
-    }
+    ZKCHK(pin_decide_shared_sort(k, c.stream));
     ZKCHK(k.mid_idx.alloc(4 * (nm ? nm : 1)));
     if (nm) HIPCHK(hipMemcpyAsync(k.mid_idx.p, mids.data(), 4 * nm, hipMemcpyHostToDevice, c.stream));
     ZKCHK(k.wit_resident.alloc(32 * (size_t)m));
@@ -436,6 +438,65 @@ static int pin_install_derived(PinKey& k, const uint8_t* d_pool, hipStream_t s) 
     k.full1[5] = ph; k.lo1[5] = lo; k.hi1[5] = hi;
     k.lagrange = true;
     for (uint32_t i = 0; i < PIN_MAX_SLOTS; i++) k.slots[i].reset();          // the h pool changed its length (compact) and the Fr scratch its form: slots are rebuilt on demand
+    return ZK_OK;
+}
+// A whole key from pools the library generated itself (keygen.hip): d_g1 / d_g2 hold the evaluation key in the layout of zk_pinocchio_pk_upload as
+// dense affine points on the current device; d_hl != nullptr: [lambda_t(s)] (n-1) | [Z(s)] as well, and the key comes out in its derived form (what
+// upload + zk_pinocchio_pk_derive_lagrange leave).  No decoding and no checks: every point is [e] G for an exponent computed here, so it has order r
+// (in_subgroup = true: folded windows are allowed, msm.cuh) and v_all / w_all satisfy the relation behind the compact h pool by construction -- the
+// rho check of the upload is skipped, ZK_PIN_COMPACT_H alone decides.
+int pin_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* d_g1, const uint8_t* d_g2,
+                        const uint8_t* d_hl, uint64_t* handle) {
+    Ctx& c = ctx();
+    auto key = std::make_unique<PinKey>();
+    PinKey& k = *key;
+    k.n = n; k.m = m;
+    k.in_subgroup = true;
+    std::vector<uint32_t> mids;
+    for (uint32_t i = 0; i < m; i++)
+        if (mid[i]) mids.push_back(i);
+    const uint64_t nm = k.n_mid = (uint32_t)mids.size();
+    ZKCHK(frstage_init(k.fr, n, m, L, R, O, c.stream));
+    const uint64_t SI = 5 * nm, ONES = SI + (n + 1) + 2 * (uint64_t)m, ONES2 = 2 * nm + (n + 1);
+    DevBuf tmp;
+    ZKCHK(tmp.alloc(192 * (nm + 3)));
+    // pool = key[base, base + nm) | key[extra, extra + nextra)
+    auto pool = [&](MsmBases& b, Curve cv, const uint8_t* d_key, uint64_t base, uint64_t extra, uint64_t nextra, uint64_t* full, uint64_t* hi) -> int {
+        const size_t pb = aff_bytes(cv);
+        if (nm) HIPCHK(hipMemcpyAsync(tmp.p, d_key + pb * base, pb * nm, hipMemcpyDeviceToDevice, c.stream));
+        HIPCHK(hipMemcpyAsync(tmp.as<uint8_t>() + pb * nm, d_key + pb * extra, pb * nextra, hipMemcpyDeviceToDevice, c.stream));
+        *full = *hi = nm + nextra;
+        ZKCHK(msm_bases_from_device_affine(b, cv, tmp.p, nm + nextra, 0, true, c.stream, true));
+        HIPCHK(hipStreamSynchronize(c.stream));          // tmp is reused by the next pool
+        return ZK_OK;
+    };
+    for (int i = 0; i < 4; i++) ZKCHK(pool(k.g1[i], CURVE_G1, d_g1, i * nm, ONES + i, 1, &k.full1[i], &k.hi1[i]));
+    ZKCHK(pool(k.g1[4], CURVE_G1, d_g1, 4 * nm, ONES + 4, 3, &k.full1[4], &k.hi1[4]));
+    ZKCHK(pool(k.g2[0], CURVE_G2, d_g2, 0, ONES2, 1, &k.full2[0], &k.hi2[0]));
+    ZKCHK(pool(k.g2[1], CURVE_G2, d_g2, nm, ONES2 + 1, 1, &k.full2[1], &k.hi2[1]));
+    k.compact = pin_compact_wanted();
+    const uint8_t* si = d_g1 + 96 * SI;
+    if (!d_hl) {
+        const uint64_t ph = pin_h_points(n, m, false, k.compact);          // si, or si | v_all | w_all: contiguous in the key
+        ZKCHK(msm_bases_from_device_affine(k.g1[5], CURVE_G1, si, ph, 0, true, c.stream, true));
+        k.full1[5] = k.hi1[5] = ph;
+    } else {
+        // the pool pin_derive_pool builds:  [lambda_t(s)] (n-1) | [Z(s)] | [1] = si[0] | [s^(n-1)] = si[n-1]   resp.   ... | [1] | v_all | w_all
+        DevBuf hp;
+        ZKCHK(hp.alloc(96 * pin_h_points(n, m, true, k.compact)));
+        HIPCHK(hipMemcpyAsync(hp.p, d_hl, 96 * (uint64_t)n, hipMemcpyDeviceToDevice, c.stream));
+        HIPCHK(hipMemcpyAsync(hp.as<uint8_t>() + 96 * (uint64_t)n, si, 96, hipMemcpyDeviceToDevice, c.stream));
+        if (k.compact) HIPCHK(hipMemcpyAsync(hp.as<uint8_t>() + 96 * ((uint64_t)n + 1), si + 96 * (uint64_t)(n - 1), 96, hipMemcpyDeviceToDevice, c.stream));
+        else HIPCHK(hipMemcpyAsync(hp.as<uint8_t>() + 96 * ((uint64_t)n + 1), si + 96 * ((uint64_t)n + 1), 96 * 2 * (uint64_t)m, hipMemcpyDeviceToDevice, c.stream));
+        ZKCHK(pin_install_derived(k, hp.as<uint8_t>(), c.stream));          // synchronises: hp has been read
+    }
+    ZKCHK(pin_decide_shared_sort(k, c.stream));
+    ZKCHK(k.mid_idx.alloc(4 * (nm ? nm : 1)));
+    if (nm) HIPCHK(hipMemcpyAsync(k.mid_idx.p, mids.data(), 4 * nm, hipMemcpyHostToDevice, c.stream));
+    ZKCHK(k.wit_resident.alloc(32 * (size_t)m));
+    HIPCHK(hipStreamSynchronize(c.stream));
+    *handle = g_pin_next++;
+    g_pin[*handle] = std::move(key);
     return ZK_OK;
 }
 static int pin_check_idle(PinKey& k, const char* who) {
@@ -869,6 +930,33 @@ int zk_pinocchio_pk_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr
     if (ctx_count() > 1) return pin_group_upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, handle);
     std::unique_ptr<PinKey> key;
     ZKCHK(pin_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, -1));
+    *handle = g_pin_next++;
+    g_pin[*handle] = std::move(key);
+    return ZK_OK;
+}
+// zk_pinocchio_pk_upload plus the derived h bases handed in by the caller: the ordinary upload (every check, the compact check included), then
+// h_lagrange = [lambda_t(s)] (n-1) | [Z(s)] decoded and checked like any key point, then pool 5 installed exactly as after a derivation.  That the
+// points belong to the key's si is the caller's promise (include/zkmi355x.h).
+int zk_pinocchio_pk_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                                    const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, const uint8_t* h_lagrange, uint64_t* handle) {
+    if (!handle || !mid || !pk_g1 || !pk_g2 || !h_lagrange || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload_lagrange: null argument");
+    ZKCHK(ensure_init());
+    if (ctx_count() > 1) ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload_lagrange: single-device keys only (a multi-device key derives its h bases: zk_pinocchio_pk_derive_lagrange)");
+    Ctx& c = ctx();
+    std::unique_ptr<PinKey> key;
+    ZKCHK(pin_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, -1));
+    PinKey& k = *key;
+    MsmBases hl;          // decoding, curve equation and (unless ZK_KEY_SUBGROUP_CHECK=0) [r] P = O, as for every point of the key
+    ZKCHK(msm_bases_from_bytes(hl, CURVE_G1, h_lagrange, n, 0, false, c.stream, k.in_subgroup));
+    const uint64_t ph = pin_h_points(n, m, true, k.compact);
+    DevBuf pool;
+    ZKCHK(pool.alloc(96 * ph));
+    uint8_t* p = pool.as<uint8_t>();
+    ZKCHK(msm_bases_dense(hl, 0, n, p, c.stream));
+    ZKCHK(msm_bases_dense(k.g1[5], 0, 1, p + 96 * (uint64_t)n, c.stream));                                                  // [1] = si[0]
+    if (k.compact) ZKCHK(msm_bases_dense(k.g1[5], n - 1, 1, p + 96 * ((uint64_t)n + 1), c.stream));                         // [s^(n-1)]
+    else ZKCHK(msm_bases_dense(k.g1[5], (uint64_t)n + 1, 2 * (uint64_t)m, p + 96 * ((uint64_t)n + 1), c.stream));           // v_all | w_all
+    ZKCHK(pin_install_derived(k, p, c.stream));
     *handle = g_pin_next++;
     g_pin[*handle] = std::move(key);
     return ZK_OK;

@@ -249,6 +249,31 @@ class Groth16:
                   Pairing.pairing(bytes(pk.g1[:96]), bytes(pk.g2[:192])))        # ab = e(alpha, beta), groth16.ml:103
         return pk, vk
 
+    @classmethod
+    def generate(cls, rng, circuit: R1CS, form="lagrange"):
+        """keygen and upload in ONE library call (zk_groth16_keygen): returns (prover, pkey, vkey).  Draws alpha, beta, gamma, delta, tau from
+        `rng` in keygen's order, so the same rng gives the same key bytes; every exponent and every point is computed on the device.  pkey is in
+        the reference's format (tau powers) whatever `form` says; form = "lagrange" | "tau_powers" chooses what the prover's handle holds --
+        "lagrange": what upload + derive_lagrange() would have built (no basis conversion per proof), without the derivation's cost."""
+        P = FR_MODULUS
+        toxic = fr_bytes([rng() % P for _ in range(5)])
+        n, m = circuit.n, circuit.m
+        mid = np.ascontiguousarray(circuit.mid, dtype=np.uint8)
+        n_mid = int(np.count_nonzero(mid))
+        g1 = np.zeros(96 * (3 + (n + 2) + (n - 1) + n_mid), dtype=np.uint8)
+        g2 = np.zeros(192 * (2 + (n + 2)), dtype=np.uint8)
+        v1 = np.zeros(96 * (1 + m - n_mid), dtype=np.uint8)
+        v2 = np.zeros(192 * 3, dtype=np.uint8)
+        L, R, O = _csr(circuit.L), _csr(circuit.R), _csr(circuit.O)
+        h = C.c_uint64()
+        _lib.check(_lib.lib().zk_groth16_keygen(n, m, C.byref(L), C.byref(R), C.byref(O), _p(mid), _p(toxic), _lib.KEY_FORMS[form],
+                                                _p(g1), len(g1) // 96, _p(g2), len(g2) // 192, _p(v1), _p(v2), C.byref(h)))
+        self = cls.__new__(cls)
+        self.circuit, self.rank, self.world, self._keep, self.handle = circuit, 0, 1, (circuit,), h
+        vk = VKey(bytes(v1[:96]), v1[96:], bytes(v2[:192]), bytes(v2[192:384]), bytes(v2[384:]),
+                  Pairing.pairing(bytes(g1[:96]), bytes(g2[:192])))        # ab = e(alpha, beta), groth16.ml:103
+        return self, PKey(g1, g2), vk
+
     def __init__(self, circuit: R1CS, pkey: PKey, rank=0, world=1, lagrange=False):
         """Uploads the proving key and the circuit once (device-resident until `close`).  lagrange=True uploads the
         Lagrange-form pools of an extended key instead (single GPU): same proofs, no basis conversion per proof."""

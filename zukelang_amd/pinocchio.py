@@ -59,6 +59,11 @@ def _uks(circuit, s):
     return vk, wk, yk, t
 
 
+def generate(rng, circuit: R1CS, form="lagrange", zk=True):
+    """(prover, pkey, vkey) from one library call: ZK.generate / NonZK.generate (zk_pinocchio_keygen)."""
+    return (ZK if zk else NonZK).generate(rng, circuit, form)
+
+
 def keygen(rng, circuit: R1CS):
     """KeyGen.generate (pinocchio.ml:77-189): exponents on the host, points from the fixed-base kernel."""
     P = FR_MODULUS
@@ -79,8 +84,34 @@ def keygen(rng, circuit: R1CS):
     return (PKey(G1.of_Fr(fr_bytes(e1)), G2.of_Fr(fr_bytes(e2))), VKey(G1.of_Fr(fr_bytes(v1)), G2.of_Fr(fr_bytes(v2))))
 
 
+def _generate(cls, rng, circuit: R1CS, form="lagrange"):
+    """KeyGen.generate and upload in ONE library call (zk_pinocchio_keygen): returns (prover, pkey, vkey).  Draws rv, rw, s, av, aw, ay, b, gm from
+    `rng` in keygen's order, so the same rng gives the same key bytes.  pkey is the reference's evaluation key whatever `form` says;
+    form = "lagrange" | "tau_powers" chooses the prover's h pool -- "lagrange": as after derive_lagrange(), without the derivation."""
+    P = FR_MODULUS
+    toxic = fr_bytes([rng() % P for _ in range(8)])
+    n, m = circuit.n, circuit.m
+    mid = np.ascontiguousarray(circuit.mid, dtype=np.uint8)
+    n_mid = int(np.count_nonzero(mid))
+    n_io = m - n_mid
+    g1 = np.zeros(96 * (5 * n_mid + (n + 1) + 2 * m + 7), dtype=np.uint8)
+    g2 = np.zeros(192 * (2 * n_mid + (n + 1) + 2), dtype=np.uint8)
+    v1 = np.zeros(96 * (3 + 2 * n_io), dtype=np.uint8)
+    v2 = np.zeros(192 * (6 + n_io), dtype=np.uint8)
+    L, R, O = _csr(circuit.L), _csr(circuit.R), _csr(circuit.O)
+    h = C.c_uint64()
+    _lib.check(_lib.lib().zk_pinocchio_keygen(n, m, C.byref(L), C.byref(R), C.byref(O), _p(mid), _p(toxic), _lib.KEY_FORMS[form],
+                                              _p(g1), len(g1) // 96, _p(g2), len(g2) // 192, _p(v1), _p(v2), C.byref(h)))
+    self = cls.__new__(cls)
+    self.circuit, self._keep, self.handle = circuit, (circuit,), h
+    return self, PKey(g1, g2), VKey(v1, v2)
+
+
 class _Prover:
-    def __init__(self, circuit: R1CS, pkey: PKey):
+    def __init__(self, circuit: R1CS, pkey: PKey, lagrange=None):
+        """Uploads the evaluation key and the circuit once.  lagrange = the n points [lambda_t(s)] (n-1) | [Z(s)] (the first n points of pool 5 of a
+        derived key, or of a keygen that knew s): the key then starts in its derived form (zk_pinocchio_pk_upload_lagrange) -- that the points belong
+        to this key is the caller's promise."""
         self.circuit = circuit
         self._keep = (circuit, pkey)
         L, R, O = _csr(circuit.L), _csr(circuit.R), _csr(circuit.O)
@@ -88,9 +119,23 @@ class _Prover:
         g1 = np.ascontiguousarray(pkey.g1, dtype=np.uint8)
         g2 = np.ascontiguousarray(pkey.g2, dtype=np.uint8)
         mid = np.ascontiguousarray(circuit.mid, dtype=np.uint8)
-        _lib.check(_lib.lib().zk_pinocchio_pk_upload(C.c_uint32(circuit.n), C.c_uint32(circuit.m), C.byref(L), C.byref(R), C.byref(O),
-                                                    _p(mid), _p(g1), C.c_size_t(len(g1) // 96), _p(g2), C.c_size_t(len(g2) // 192), C.byref(h)))
+        if lagrange is not None:
+            hl = np.ascontiguousarray(lagrange, dtype=np.uint8).reshape(-1)
+            if len(hl) != 96 * circuit.n:
+                raise ValueError("lagrange: n points [lambda_t(s)] (n-1) | [Z(s)] of 96 bytes each")
+            _lib.check(_lib.lib().zk_pinocchio_pk_upload_lagrange(circuit.n, circuit.m, C.byref(L), C.byref(R), C.byref(O), _p(mid),
+                                                                 _p(g1), len(g1) // 96, _p(g2), len(g2) // 192, _p(hl), C.byref(h)))
+        else:
+            _lib.check(_lib.lib().zk_pinocchio_pk_upload(C.c_uint32(circuit.n), C.c_uint32(circuit.m), C.byref(L), C.byref(R), C.byref(O),
+                                                        _p(mid), _p(g1), C.c_size_t(len(g1) // 96), _p(g2), C.c_size_t(len(g2) // 192), C.byref(h)))
         self.handle = h
+
+    generate = classmethod(_generate)
+
+    @classmethod
+    def from_lagrange(cls, circuit: R1CS, pkey: PKey, h_lagrange):
+        """A prover whose key starts in its derived form: pkey plus the stored h bases (see `lagrange` above)."""
+        return cls(circuit, pkey, lagrange=h_lagrange)
 
     def derive_lagrange(self):
         """zk_pinocchio_pk_derive_lagrange: the h pool rewritten for the values of h (bases derived from the key's own powers si on the
