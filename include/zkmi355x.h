@@ -409,6 +409,30 @@ int zk_groth16_verify(const uint8_t ab[576], const uint8_t* ltgm_io /* n_io * 96
 int zk_pinocchio_verify(const uint8_t* vk_g1, const uint8_t* vk_g2, const uint8_t* io_scalars, size_t n_io,
                         const uint8_t proof[960], int* ok);
 
+/* ---- the same three on the device, many per call (zukelang_amd/csrc/pairing_dev.hip) ---------------------
+ * The calls above cost one host core milliseconds to tens of milliseconds each; a host that checks a stream of proofs hands them over in batches instead.  All three run on
+ * the first device of the list, are synchronous, keep nothing after they return, check their arguments before they touch the device and return
+ * ZK_ERR_HIP where there is none: the device path has no CPU fallback.  A lone proof is quicker through the host calls (profiles/verify_many.json).
+ * zk_pairing_product_many (Pairing.pairing, curve.mli:46-54): `count` products; product k takes lens[k] pairs, the pairs of all products
+ * concatenated in g1_points / g2_points.  gt_out block k = the 576 bytes zk_pairing_product returns for those pairs (lens[k] = 0, or an identity on
+ * either side of every pair: 1).  Every point is checked as there (encoding, curve, subgroup); a bad point fails the whole call with the code of the
+ * FIRST bad point in the host's decoding order (G1 of pair i, then G2 of pair i), and gt_out then holds nothing to rely on. */
+int zk_pairing_product_many(const uint8_t* g1_points, const uint8_t* g2_points, const uint64_t* lens, uint32_t count,
+                            uint8_t* gt_out /* count * 576 */);
+/* Groth16.verify (groth16.ml:163-173) of `count` proofs under one key, the key laid out as for zk_groth16_verify.  A null argument or a bad key
+ * point fails the call with that function's code.  A proof's own defects never do: ok[i] = its *ok, status[i] = the code the single-proof call
+ * would return for proof i under this key -- ZK_OK; ZK_ERR_ARG / ZK_ERR_NOT_ON_CURVE for the first bad point of the proof in the order A, B, C;
+ * ZK_ERR_SCALAR_RANGE for a public input >= r -- and ok[i] = 0 whenever status[i] != 0.  status may be NULL.  count = 0: ZK_OK, nothing touched.
+ * A malformed ab compares unequal to every product, as on the host: every ok[i] = 0. */
+int zk_groth16_verify_many(const uint8_t ab[576], const uint8_t* ltgm_io, size_t n_io, const uint8_t gm[192], const uint8_t d[192],
+                           const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 384 */, uint32_t count,
+                           uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
+/* Pinocchio Verify.f (pinocchio.ml:254-420) of `count` proofs under one key, vk_g1 / vk_g2 as for zk_pinocchio_verify; ok and status as above, the
+ * points of a proof in the order vv, ww, yy, h, vavv, waww, yayy, bvwy. */
+int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_io,
+                             const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 960 */, uint32_t count,
+                             uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------
  * With profiling on, kernel families are bracketed by HIP events on the stream they run on;
  * zk_profile_get returns the summed milliseconds and launch count since the last reset. */
@@ -433,6 +457,11 @@ int zk_selftest_fp(const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
  * roots the one the ZCash sign rule calls the larger (Fp2: by the imaginary part, by the real part when that is zero) -- decided by the same device
  * function as the sign bit of zk_g1/g2_decompress_batch -- and zeros when there is none.  An element >= p -> ZK_ERR_ARG. */
 int zk_selftest_sqrt(int field, const uint8_t* a, size_t n, uint8_t* root, uint8_t* is_square);
+/* The device's Fp12 (tests/test_gpu_pairing.py): n elements in the GT encoding through the functions the pairing kernels call, one group of lanes
+ * per element.  op 0: a b | 1: a^2 | 2: 1 / a (0 for 0) | 3: conjugate a^(p^6) | 4: Frobenius a^p | 5: a^(p^2) | 6: a times the sparse element made
+ * of b's coefficients of w^0, w^3, w^5 (the shape of a Miller line: c0.c0, c1.c1, c1.c2) | 7: a^((p^12 - 1) / r).  b is read by ops 0 and 6.
+ * A coefficient >= p -> ZK_ERR_ARG. */
+int zk_selftest_fp12(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -5,7 +5,8 @@
    product / fixed-base kernel on the MI355X.  The O(m n) structure of `sum_apply_powers` (groth16.ml:116-121) remains with
    this seam alone -- seam 2 (groth16_mi355x.ml, pinocchio_mi355x.ml) removes it.
 
-   Fr, GT and Pairing are the host's own (opam bls12-381): a verifier needs a handful of pairings, not a GPU. *)
+   Fr, GT and Pairing are the host's own (opam bls12-381): the verifier of ONE proof needs a handful of pairings, not a GPU.  Lists of
+   proofs are checked on the device by `verify_many` of the seam-2 modules (groth16_mi355x.ml, pinocchio_mi355x.ml). *)
 
 module Base = Curve.Bls12_381
 

@@ -14,6 +14,7 @@
              -> one call zk_groth16_keygen: the trapdoor is drawn HERE in the reference's order (:51-55), exponents and points are the device's;
                 the key's bytes and a live handle in Lagrange form come back (a multi-device list: the bytes, then the ordinary upload)
      verify  groth16.ml:163-173 -> unchanged in substance: three pairings of the host's own Pairing
+             verify_many (an extra): a list of proofs under one key -> one call zk_groth16_verify_many, the pairings on the device
    The records and their yojson are the reference's (groth16.ml:24-43,110-114): the JSON of keys and proofs is the wire format. *)
 
 open Zukelang
@@ -252,4 +253,47 @@ module Make (C : Curve.S) = struct
     let e = Pairing.pairing in
     let public_part = G1.dot vkey.ltgm_io input_output in
     GT.(e proof.a proof.b - e public_part vkey.gm - e proof.c vkey.d = vkey.ab)
+
+  (* ---------------------------------------------------------------- verify_many
+     `verify` for a list of (public inputs, proof) under one key in ONE library call, on the device (zk_groth16_verify_many): the three
+     pairings of every proof side by side.  A lone proof is quicker through `verify`.
+     The library compares GT elements as the 12 Fp coefficients of the tower Fp12 = Fp6[w] / (w^2 - v), Fp6 = Fp2[v] / (v^3 - (1 + u)), 48 bytes
+     big-endian each (include/zkmi355x.h); GT.to_bytes of opam bls12-381 writes the same coefficients in the same order, little-endian.  That is
+     CHECKED, not assumed: before the first batch of a process e(G1.one, G2.one) is computed by both sides, and a difference fails before any proof
+     is judged.  After that a batch is ONE library call. *)
+  let gt_lib_bytes (x : GT.t) : bytes =
+    let b = GT.to_bytes x in
+    if Bytes.length b <> 576 then failwith "verify_many: GT.to_bytes is not 12 x 48 bytes";
+    Bytes.init 576 (fun i -> Bytes.get b ((i / 48 * 48) + 47 - (i mod 48)))
+
+  (* the check of that byte order: ONCE per process, at the first batch (a pairing on each side) *)
+  let gt_order_checked =
+    lazy
+      (let probe = Bytes.create 576 in
+       Mi355x.(
+         check
+           (zk_pairing_product
+              (bytes_start (G1.to_bytes G1.one))
+              (bytes_start (G2.to_bytes G2.one))
+              (sz 1) (bytes_start probe)));
+       if not (Bytes.equal probe (gt_lib_bytes (Pairing.pairing G1.one G2.one))) then
+         failwith "verify_many: the library's GT encoding is not GT.to_bytes with every coefficient reversed")
+
+  let verify_many (jobs : (f Var.Map.t * proof) list) (vkey : vkey) : bool list =
+    List.iter (fun (io, _) -> assert (Var.Set.equal (Var.Map.domain io) (Var.Map.domain vkey.ltgm_io))) jobs;
+    Lazy.force gt_order_checked;
+    let count = List.length jobs in
+    let ok = Bytes.make (max count 1) (Char.chr 0) in
+    let io_all = fr_bytes (List.concat_map (fun (io, _) -> values io) jobs) in
+    let proofs = Mi355x.cat (List.concat_map (fun (_, (p : proof)) -> [ G1.to_bytes p.a; G2.to_bytes p.b; G1.to_bytes p.c ]) jobs) in
+    Mi355x.(
+      check
+        (zk_groth16_verify_many
+           (bytes_start (gt_lib_bytes vkey.ab))
+           (bytes_start (g1_bytes (values vkey.ltgm_io)))
+           (sz (Var.Map.cardinal vkey.ltgm_io))
+           (bytes_start (G2.to_bytes vkey.gm))
+           (bytes_start (G2.to_bytes vkey.d))
+           (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
+    List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
 end

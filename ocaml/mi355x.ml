@@ -267,6 +267,25 @@ let zk_groth16_verify =
   fn "zk_groth16_verify"
     (ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> ptr int @-> returning int)
 
+(* the library's host pairing: prod_i e(P_i, Q_i) in its own GT encoding (groth16_mi355x.ml holds GT.to_bytes to it once per process) *)
+let zk_pairing_product = fn "zk_pairing_product" (ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> returning int)
+
+(* The verifiers in batches, on the device (include/zkmi355x.h, "the same three on the device"): one library call checks a list of proofs.
+   ok: one byte per proof; status: one code per proof, or null. *)
+let zk_pairing_product_many =
+  fn "zk_pairing_product_many" (ocaml_bytes @-> ocaml_bytes @-> ptr uint64_t @-> uint32_t @-> ocaml_bytes @-> returning int)
+
+let zk_groth16_verify_many =
+  fn "zk_groth16_verify_many"
+    (ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes
+   @-> ptr int32_t @-> returning int)
+
+let zk_pinocchio_verify_many =
+  fn "zk_pinocchio_verify_many"
+    (ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
+
+let no_status : int32 ptr = from_voidp int32_t null
+
 let groth16_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in
   check

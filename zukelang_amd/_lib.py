@@ -25,8 +25,9 @@ EXPORTS = [
     "zk_pinocchio_reserve_slots", "zk_pinocchio_set_witness", "zk_pinocchio_prove_async", "zk_pinocchio_prove_wait",
     "zk_groth16_keygen", "zk_pinocchio_keygen", "zk_pinocchio_pk_upload_lagrange",
     "zk_pairing_product", "zk_pairing_check", "zk_groth16_verify", "zk_pinocchio_verify",
+    "zk_pairing_product_many", "zk_groth16_verify_many", "zk_pinocchio_verify_many",
     "zk_profile_enable", "zk_profile_reset", "zk_profile_get", "zk_profile_names", "zk_profile_counter", "zk_sync",
-    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_sqrt",
+    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_sqrt", "zk_selftest_fp12",
 ]
 
 
@@ -40,7 +41,7 @@ class CSR(C.Structure):
     _fields_ = [("row_ptr", C.POINTER(C.c_uint32)), ("col", C.POINTER(C.c_uint32)), ("val", C.POINTER(C.c_uint8))]
 
 
-_P8, _PCSR, _PH = C.POINTER(C.c_uint8), C.POINTER(CSR), C.POINTER(C.c_uint64)
+_P8, _PCSR, _PH, _PI32 = C.POINTER(C.c_uint8), C.POINTER(CSR), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
 _KEYGEN = [C.c_uint32, C.c_uint32, _PCSR, _PCSR, _PCSR, _P8, _P8, C.c_uint32, _P8, C.c_size_t, _P8, C.c_size_t, _P8, _P8, _PH]
 # argument types of the key-generation entries, in the header's order (tests/test_keygen_surface.py holds them to include/zkmi355x.h); ctypes then checks
 # every call against them.  The older entries are called with explicitly typed ctypes values.
@@ -49,6 +50,14 @@ PROTOTYPES = {
     "zk_groth16_keygen": _KEYGEN,
     "zk_pinocchio_keygen": _KEYGEN,
     "zk_pinocchio_pk_upload_lagrange": [C.c_uint32, C.c_uint32, _PCSR, _PCSR, _PCSR, _P8, _P8, C.c_size_t, _P8, C.c_size_t, _P8, _PH],
+}
+# the batched verifiers and the Fp12 hook, typed the same way (tests/test_verify_many_surface.py holds them to the header).  A table of their own:
+# tests/test_keygen_surface.py holds PROTOTYPES to exactly the key-generation entries.
+VERIFY_PROTOTYPES = {
+    "zk_pairing_product_many": [_P8, _P8, _PH, C.c_uint32, _P8],
+    "zk_groth16_verify_many": [_P8, _P8, C.c_size_t, _P8, _P8, _P8, _P8, C.c_uint32, _P8, _PI32],
+    "zk_pinocchio_verify_many": [_P8, _P8, C.c_size_t, _P8, _P8, C.c_uint32, _P8, _PI32],
+    "zk_selftest_fp12": [C.c_int, _P8, _P8, C.c_size_t, _P8],
 }
 KEY_FORMS = {"tau_powers": 0, "lagrange": 1}          # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
 
@@ -65,7 +74,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in PROTOTYPES.items():
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

@@ -128,6 +128,10 @@ int proof_points_to_bytes_dev(const void* d_g1, uint32_t n1, const uint32_t* off
 // bytes (device copy of host encoding) -> affine Montgomery; *d_flag |= 1 not on curve, |= 2 bad encoding
 int points_bytes_to_affine(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, int* d_flag, hipStream_t s);
 int points_affine_to_bytes(Curve curve, void* d_bytes, const void* d_affine, uint64_t n, hipStream_t s);
+// decode + curve check (+ [r] P = O) with one verdict byte per point: 0 good | 2 encoding | 1 curve | 4 subgroup; rejected points become the identity
+int points_decode_verdicts(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, uint8_t* d_verdict, bool check_subgroup, hipStream_t s);
+// out[i] = a[i] + b[i] over encoded, already checked points (host bytes in, host bytes out)
+int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, hipStream_t s);
 // n ZCash-COMPRESSED points (host, 48 / 96 B) -> uncompressed (host, 96 / 192 B): square roots, curve and subgroup checks on the device (msm_points.hip)
 int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, hipStream_t s);
 int points_selftest_sqrt(int field, const uint8_t* a, uint64_t n, uint8_t* root, uint8_t* is_square, hipStream_t s);          // zk_selftest_sqrt

@@ -285,6 +285,48 @@ template <class F> __global__ __launch_bounds__(128) void k_subgroup_check(const
     }
 }
 
+// The two checks above with ONE VERDICT PER POINT instead of one flag per list (the batched verifiers of pairing_dev.hip: a proof's bad point is that
+// proof's status, not the call's): 0 good, 2 bad encoding, 1 not on the curve, 4 on the curve but outside the subgroup -- the kinds of the list readers.
+// A rejected point is stored as the identity.  (0, 0) WITHOUT the infinity bit is how this library's affine format spells the identity, but on the wire
+// it is a point that fails the curve equation, as it does in g1_decode / g2_decode of pairing_host.hip.
+template <class F> __global__ void k_bytes_to_affine_verdict(uint8_t* dst, const uint8_t* src, uint64_t n, uint8_t* verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int B = FieldOps<F>::WORDS * 8;
+    Aff<F> a;
+    uint8_t v = 0;
+    if (aff_decode(a, src + B * i)) v = 2;
+    else if ((!(src[B * i] & 0x40) && aff_is_inf(a)) || !aff_on_curve(a)) v = 1;
+    if (v) a = aff_inf<F>();
+    aff_store<F>(dst + B * i, a);
+    verdict[i] = v;
+}
+template <class F> __global__ __launch_bounds__(128) void k_subgroup_verdict(const uint8_t* __restrict__ dense, uint64_t n, uint8_t* verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int B = FieldOps<F>::WORDS * 8;
+    const Aff<F> p = aff_load<F>(dense + B * i);
+    if (aff_is_inf(p)) return;
+    Xyzz<F> acc = xyzz_from_aff(p);                      // the top bit (254) of r
+    for (int b = 253; b >= 0; b--) {
+        acc = xyzz_dbl(acc);
+        if ((FR_ORDER_BITS[b >> 5] >> (b & 31)) & 1u) xyzz_madd(acc, p);
+    }
+    if (!xyzz_is_inf(acc)) verdict[i] = 4;
+}
+
+// out[i] = a[i] + b[i] on dense affine points, every case of the group law (an identity operand, P + P, P + (-P)): the verifier's vio + vv and the like
+// (pinocchio.ml:418-420), G.add of curve.ml:159-191
+template <class F> __global__ __launch_bounds__(64) void k_aff_add(uint8_t* __restrict__ out, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int B = FieldOps<F>::WORDS * 8;
+    Xyzz<F> acc = xyzz_from_aff(aff_load<F>(a + B * i));
+    const Aff<F> q = aff_load<F>(b + B * i);
+    xyzz_madd(acc, q);
+    aff_store<F>(out + B * i, xyzz_to_aff(acc));
+}
+
 // ------------------------------------------------------------------ base tables: table[j*n + i] = 2^(c*j) * P_i, j < nw
 // `dense` holds the n base points in the dense affine format (what the key arrived as); the table takes them -- and with nw > 1 their
 // multiples by 2^(c j) -- in the 128-byte record layout of ec.cuh (TableLayout).
@@ -422,6 +464,38 @@ int points_bytes_to_affine(Curve curve, void* d_aff, const void* d_bytes, uint64
     if (curve == CURVE_G1) hipLaunchKernelGGL(k_bytes_to_affine<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_flag);
     else hipLaunchKernelGGL(k_bytes_to_affine<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_flag);
     HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+int points_decode_verdicts(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, uint8_t* d_verdict, bool check_subgroup, hipStream_t s) {
+    if (!n) return ZK_OK;
+    if (curve == CURVE_G1) {
+        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
+        if (check_subgroup) hipLaunchKernelGGL(k_subgroup_verdict<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+    } else {
+        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
+        if (check_subgroup) hipLaunchKernelGGL(k_subgroup_verdict<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+    }
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// n sums a[i] + b[i] of encoded points (host bytes, both lists already checked) -> n encoded points (host)
+int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, hipStream_t s) {
+    if (!n) return ZK_OK;
+    const size_t ab = aff_bytes(curve);
+    DevBuf raw, da, db, dv;
+    ZKCHK(raw.alloc(2 * ab * n));
+    ZKCHK(da.alloc(2 * ab * n));
+    ZKCHK(db.alloc(ab * n));
+    ZKCHK(dv.alloc(2 * n));
+    HIPCHK(hipMemcpyAsync(raw.p, a, ab * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(raw.as<uint8_t>() + ab * n, b, ab * n, hipMemcpyHostToDevice, s));
+    ZKCHK(points_decode_verdicts(curve, da.p, raw.p, 2 * n, dv.as<uint8_t>(), false, s));
+    if (curve == CURVE_G1) hipLaunchKernelGGL(k_aff_add<Fp>, grid_for(n, 64), dim3(64), 0, s, db.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>() + ab * n, n);
+    else hipLaunchKernelGGL(k_aff_add<Fp2>, grid_for(n, 64), dim3(64), 0, s, db.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>() + ab * n, n);
+    HIPCHK(hipGetLastError());
+    ZKCHK(points_affine_to_bytes(curve, raw.p, db.p, n, s));
+    HIPCHK(hipMemcpyAsync(out, raw.p, ab * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return ZK_OK;
 }
 int points_affine_to_bytes(Curve curve, void* d_bytes, const void* d_aff, uint64_t n, hipStream_t s) {

@@ -1,0 +1,429 @@
+// Pairings in batches on the device (scope row f1; include/zkmi355x.h: zk_pairing_product_many, zk_groth16_verify_many, zk_pinocchio_verify_many):
+// many products of pairings -- many proofs' verifications -- per call.  The single-proof verifiers stay on the host (pairing_host.hip, which this
+// file does not touch: the host-only sanitizer library is built from it alone); a stream of proofs is checked here.  Same definitions, same bytes:
+// Pairing.pairing of curve.mli:46-54, Groth16.verify of groth16.ml:163-173, Verify.f of pinocchio.ml:254-420.
+//
+//   bytes -> affine + one verdict per point    k_bytes_to_affine_verdict, k_subgroup_verdict (msm_points.hip: one lane per point)
+//   sums over the public inputs                 the resident short products of msm_resident.hip: the key's points uploaded once per call, one product per proof
+//   Miller loops                                k_miller: one group of 8 lanes per PAIR (pairing_tower.cuh), inversion-free, 63 steps
+//   products + final exponentiations            k_final_exp: one group per PRODUCT multiplies its pairs' Miller values and raises to (p^12 - 1) / r
+//
+// A batch is bound by latency, not by the multipliers: one G2 subgroup check is ~15 k base-field products on one lane, a Miller loop ~2.6 k and a
+// final exponentiation ~7 k per lane of a group, and every pair and product of the batch does them side by side (profiles/verify_many.json).
+#include "pairing_tower.cuh"
+
+#include "msm.cuh"
+#include "pairing_consts.h"
+
+#include <string.h>
+#include <vector>
+
+namespace zk {
+
+static constexpr uint32_t F12_RAW_WORDS = f12::EW;          // a Miller value between the two kernels: 6 coefficients x 28 limbs
+
+// pair g of n: P = g1[g], Q = g2[g] (dense affine, checked); out[g] = the conjugated Miller value, 1 when either point is the identity
+__global__ __launch_bounds__(64) void k_miller(const uint8_t* __restrict__ g1, const uint8_t* __restrict__ g2, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t g = blockIdx.x * f12::GROUPS_PER_WAVE + threadIdx.x / f12::GROUP;
+    const bool live = g < n;
+    const uint32_t gi = live ? g : n - 1;          // the spare groups of the last workgroup walk along: the barriers are the workgroup's
+    const Aff<Fp> P = aff_load<Fp>(g1 + 96 * (size_t)gi);
+    const Aff<Fp2> Q = aff_load<Fp2>(g2 + 192 * (size_t)gi);
+    const bool skip = aff_is_inf(P) || aff_is_inf(Q);          // on (0, 0) the loop computes some value without harm (no inversion, no branch on data)
+    f12::miller(P, Q);
+    const uint32_t k = f12::coef();
+    const f12::F12C one = f12::sel<1>(k == 0, fp2_zero(), fp2_one());
+    const f12::F12C x = f12::sel<256>(skip, f12::ld<256>(f12::reg_cell(0, k)), one);
+    if (live) f12::st(out + (size_t)F12_RAW_WORDS * g + k * f12::CW, x);
+}
+// product q of n: the Miller values [off[q], off[q + 1]) multiplied, then the final exponentiation, then the GT encoding (576 B)
+__global__ __launch_bounds__(64) void k_final_exp(const uint32_t* __restrict__ miller, const uint32_t* __restrict__ off, uint32_t n, uint8_t* __restrict__ gt) {
+    const uint32_t first = blockIdx.x * f12::GROUPS_PER_WAVE, g = first + threadIdx.x / f12::GROUP;
+    const bool live = g < n;
+    const uint32_t gi = live ? g : n - 1;
+    const uint32_t lo = off[gi], len = off[gi + 1] - lo;
+    uint32_t most = 0;                               // the longest product of this workgroup: every group takes that many steps
+    for (uint32_t q = first; q < first + f12::GROUPS_PER_WAVE && q < n; q++) most = max(most, off[q + 1] - off[q]);
+    f12::set_one(0);
+    const uint32_t k = f12::coef();
+    const f12::F12C one = f12::sel<1>(k == 0, fp2_zero(), fp2_one());
+    for (uint32_t j = 0; j < most; j++) {
+        const bool have = j < len;
+        const f12::F12C x = f12::sel<256>(!have, f12::ld<256>(miller + (size_t)F12_RAW_WORDS * (have ? lo + j : 0) + k * f12::CW), one);
+        __syncthreads();
+        f12::st(f12::reg_cell(1, k), x);
+        __syncthreads();
+        f12::mul(0, 0, 1);
+    }
+    f12::final_exp();
+    f12::store_gt(gt + 576 * (size_t)gi, 0, live);
+}
+// zk_selftest_fp12: element g of n through the device functions above
+__global__ __launch_bounds__(64) void k_selftest_fp12(int op, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint32_t n, uint8_t* __restrict__ out, int* flag) {
+    const uint32_t g = blockIdx.x * f12::GROUPS_PER_WAVE + threadIdx.x / f12::GROUP;
+    const bool live = g < n;
+    const uint32_t gi = live ? g : n - 1;
+    bool ok = f12::load_gt(0, a + 576 * (size_t)gi);
+    if (op == 0 || op == 6) ok = f12::load_gt(1, b + 576 * (size_t)gi) && ok;
+    if (!ok) *flag = 1;
+    switch (op) {          // uniform
+    case 0: f12::mul(0, 0, 1); break;
+    case 1: f12::mul(0, 0, 0); break;
+    case 2: f12::inv(5, 0, 2, 3, 4); f12::copy(0, 5); break;
+    case 3: f12::conj(0, 0); break;
+    case 4: f12::frob(0, 0); break;
+    case 5: f12::frob(0, 0); f12::frob(0, 0); break;
+    case 6: {              // b's coefficients of w^0, w^3, w^5 as a line.  The Miller cells overlay registers 1..: take the three out of register 1 first
+        const Fp2B<2> l0 = f12::ld<2>(f12::reg_cell(1, 0)), l3 = f12::ld<2>(f12::reg_cell(1, 3)), l5 = f12::ld<2>(f12::reg_cell(1, 5));
+        __syncthreads();
+        f12::st(f12::cell(f12::C_L0), l0);
+        f12::st(f12::cell(f12::C_L3), l3);
+        f12::st(f12::cell(f12::C_L5), l5);
+        __syncthreads();
+        f12::mul_line(0, 0, f12::C_L0);
+        break;
+    }
+    default: f12::final_exp(); break;
+    }
+    f12::store_gt(out + 576 * (size_t)gi, 0, live);
+}
+
+// ================================================================== host side
+static constexpr uint32_t MAX_PROOFS = 1u << 24;          // 13 pairs each stay inside the 31-bit pair index
+static int verdict_code(uint8_t v) { return v == 0 ? ZK_OK : v == 2 ? ZK_ERR_ARG : ZK_ERR_NOT_ON_CURVE; }
+
+// n1 G1 and n2 G2 points (host bytes) -> one verdict each: encoding, curve, subgroup
+static int check_points(const uint8_t* g1, uint64_t n1, const uint8_t* g2, uint64_t n2, std::vector<uint8_t>& v1, std::vector<uint8_t>& v2, hipStream_t s) {
+    v1.assign(n1, 0);
+    v2.assign(n2, 0);
+    DevBuf b1, b2, a1, a2, dv;
+    ZKCHK(b1.alloc(96 * n1));
+    ZKCHK(b2.alloc(192 * n2));
+    ZKCHK(a1.alloc(96 * n1));
+    ZKCHK(a2.alloc(192 * n2));
+    ZKCHK(dv.alloc(n1 + n2));
+    if (n1) HIPCHK(hipMemcpyAsync(b1.p, g1, 96 * n1, hipMemcpyHostToDevice, s));
+    if (n2) HIPCHK(hipMemcpyAsync(b2.p, g2, 192 * n2, hipMemcpyHostToDevice, s));
+    {
+        ScopedTimer t("pairing_point_checks", s);
+        ZKCHK(points_decode_verdicts(CURVE_G2, a2.p, b2.p, n2, dv.as<uint8_t>() + n1, true, s));
+        ZKCHK(points_decode_verdicts(CURVE_G1, a1.p, b1.p, n1, dv.as<uint8_t>(), true, s));
+    }
+    if (n1) HIPCHK(hipMemcpyAsync(v1.data(), dv.p, n1, hipMemcpyDeviceToHost, s));
+    if (n2) HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + n1, n2, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZK_OK;
+}
+
+// count products over npairs = sum lens pairs (host bytes) -> count GT encodings.  check: every point's subgroup membership too (else encoding and
+// curve only: the caller has checked them).  v1 / v2: the verdicts, one per pair and side; a rejected point counts as the identity.
+static int run_products(const uint8_t* g1, const uint8_t* g2, uint64_t npairs, const uint64_t* lens, uint32_t count, bool check, std::vector<uint8_t>& v1,
+                        std::vector<uint8_t>& v2, uint8_t* gt_out, hipStream_t s) {
+    v1.assign(npairs, 0);
+    v2.assign(npairs, 0);
+    if (npairs >= ((uint64_t)1 << 31)) ZK_FAIL(ZK_ERR_ARG, "pairing products: too many pairs for one call");
+    std::vector<uint32_t> off(count + 1);
+    uint64_t run = 0;
+    for (uint32_t k = 0; k < count; k++) { off[k] = (uint32_t)run; run += lens[k]; }
+    off[count] = (uint32_t)run;
+    DevBuf b1, b2, a1, a2, dv, dm, doff, dgt;
+    ZKCHK(b1.alloc(96 * npairs));
+    ZKCHK(b2.alloc(192 * npairs));
+    ZKCHK(a1.alloc(96 * npairs));
+    ZKCHK(a2.alloc(192 * npairs));
+    ZKCHK(dv.alloc(2 * npairs));
+    ZKCHK(dm.alloc((size_t)F12_RAW_WORDS * 4 * npairs));
+    ZKCHK(doff.alloc(4 * (size_t)(count + 1)));
+    ZKCHK(dgt.alloc(576 * (size_t)count));
+    HIPCHK(hipMemcpyAsync(doff.p, off.data(), 4 * (size_t)(count + 1), hipMemcpyHostToDevice, s));
+    if (npairs) {
+        HIPCHK(hipMemcpyAsync(b1.p, g1, 96 * npairs, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(b2.p, g2, 192 * npairs, hipMemcpyHostToDevice, s));
+        {
+            ScopedTimer t("pairing_point_checks", s);
+            ZKCHK(points_decode_verdicts(CURVE_G2, a2.p, b2.p, npairs, dv.as<uint8_t>() + npairs, check, s));
+            ZKCHK(points_decode_verdicts(CURVE_G1, a1.p, b1.p, npairs, dv.as<uint8_t>(), check, s));
+        }
+        HIPCHK(hipMemcpyAsync(v1.data(), dv.p, npairs, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + npairs, npairs, hipMemcpyDeviceToHost, s));
+        ScopedTimer t("pairing_miller", s);
+        hipLaunchKernelGGL(k_miller, grid_for(npairs, f12::GROUPS_PER_WAVE), dim3(64), 0, s, (const uint8_t*)a1.as<uint8_t>(), (const uint8_t*)a2.as<uint8_t>(),
+                           (uint32_t)npairs, dm.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ScopedTimer t("pairing_final_exp", s);
+        hipLaunchKernelGGL(k_final_exp, grid_for(count, f12::GROUPS_PER_WAVE), dim3(64), 0, s, (const uint32_t*)dm.as<uint32_t>(), (const uint32_t*)doff.as<uint32_t>(),
+                           count, dgt.as<uint8_t>());
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(gt_out, dgt.p, 576 * (size_t)count, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZK_OK;
+}
+
+// ---- byte-level point helpers of the verifiers (the encodings are canonical: they passed the checks or came from the device's encoder)
+static void be48_p(uint8_t out[48]) {
+    for (int i = 0; i < 6; i++)
+        for (int k = 0; k < 8; k++) out[8 * (5 - i) + k] = (uint8_t)(HP_P[i] >> (8 * (7 - k)));
+}
+// -P of a G1 encoding: y -> p - y (the identity, and y = 0, stay)
+static void g1_neg_bytes(uint8_t out[96], const uint8_t in[96]) {
+    memcpy(out, in, 96);
+    if (in[0] & 0x40) return;
+    uint8_t any = 0;
+    for (int i = 48; i < 96; i++) any |= in[i];
+    if (!any) return;
+    uint8_t p[48];
+    be48_p(p);
+    int borrow = 0;
+    for (int i = 47; i >= 0; i--) {
+        const int d = (int)p[i] - (int)in[48 + i] - borrow;
+        out[48 + i] = (uint8_t)(d & 0xff);
+        borrow = d < 0 ? 1 : 0;
+    }
+}
+static void g1_identity(uint8_t out[96]) { memset(out, 0, 96); out[0] = 0x40; }
+static void g2_identity(uint8_t out[192]) { memset(out, 0, 192); out[0] = 0x40; }
+static bool fr_canonical(const uint8_t* b) {          // 32-byte little-endian < r
+    for (int i = 3; i >= 0; i--) {
+        uint64_t w = 0;
+        for (int k = 7; k >= 0; k--) w = (w << 8) | b[8 * i + k];
+        if (w < HP_R[i]) return true;
+        if (w > HP_R[i]) return false;
+    }
+    return false;
+}
+// out[i] = sum_k scalars[i][k] * points[k] for count scalar vectors of n over ONE point list (G.dot, curve.ml:91-103): the list goes up once as
+// resident bases, one product per proof.  live[i] = 0: vector i is not multiplied (its proof is already rejected; it may hold scalars >= r).
+static int dot_many(int group, const uint8_t* points, size_t n, const uint8_t* scalars, uint32_t count, const std::vector<uint8_t>& live, uint8_t* out) {
+    const size_t ab = group ? 192 : 96;
+    if (!n) {
+        for (uint32_t i = 0; i < count; i++) { memset(out + ab * i, 0, ab); out[ab * i] = 0x40; }
+        return ZK_OK;
+    }
+    std::vector<uint8_t> sc(scalars, scalars + 32 * n * (size_t)count);
+    for (uint32_t i = 0; i < count; i++)
+        if (!live[i]) memset(sc.data() + 32 * n * i, 0, 32 * n);
+    const std::vector<uint64_t> lens(count, n);
+    uint64_t h = 0;
+    ZKCHK(zk_bases_upload(group, points, n, &h));
+    const int rc = zk_msm_resident_many(h, sc.data(), lens.data(), count, out);
+    (void)zk_bases_free(h);
+    return rc;
+}
+
+}  // namespace zk
+
+using namespace zk;
+extern "C" {
+
+int zk_pairing_product_many(const uint8_t* g1_points, const uint8_t* g2_points, const uint64_t* lens, uint32_t count, uint8_t* gt_out) {
+    if (!count) return ZK_OK;
+    if (!lens || !gt_out) ZK_FAIL(ZK_ERR_ARG, "zk_pairing_product_many: null argument");
+    uint64_t npairs = 0;
+    for (uint32_t k = 0; k < count; k++) npairs += lens[k];
+    if (npairs && (!g1_points || !g2_points)) ZK_FAIL(ZK_ERR_ARG, "zk_pairing_product_many: null argument");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    std::vector<uint8_t> v1, v2;
+    ZKCHK(run_products(g1_points, g2_points, npairs, lens, count, true, v1, v2, gt_out, ctx().stream));
+    for (uint64_t i = 0; i < npairs; i++) {          // the host's decoding order: G1 of pair i, then G2 of pair i
+        if (v1[i]) ZK_FAIL(verdict_code(v1[i]), "zk_pairing_product_many: bad G1 point (encoding, curve or subgroup)");
+        if (v2[i]) ZK_FAIL(verdict_code(v2[i]), "zk_pairing_product_many: bad G2 point (encoding, curve or subgroup)");
+    }
+    return ZK_OK;
+}
+
+// groth16.ml:163-173:  e(A, B) = ab * e(sum_k w_k ltgm_io_k, gm) * e(C, d), as zk_groth16_verify decides it: e(A, B) e(-acc, gm) e(-C, d) == ab on bytes
+int zk_groth16_verify_many(const uint8_t ab[576], const uint8_t* ltgm_io, size_t n_io, const uint8_t gm[192], const uint8_t d[192], const uint8_t* io_scalars,
+                           const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
+    if (!ab || !gm || !d || (n_io && !ltgm_io)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: null argument");
+    if (!count) return ZK_OK;
+    if (!proofs || !ok || (n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: null argument");
+    if (count > MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: more than 2^24 proofs in one call");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    hipStream_t s = ctx().stream;
+    // every point once: G1 = A[count] | C[count] | ltgm_io[n_io], G2 = B[count] | gm | d
+    std::vector<uint8_t> p1(96 * (2 * (size_t)count + n_io)), p2(192 * ((size_t)count + 2)), v1, v2;
+    for (uint32_t i = 0; i < count; i++) {
+        memcpy(&p1[96 * (size_t)i], proofs + 384 * (size_t)i, 96);
+        memcpy(&p1[96 * ((size_t)count + i)], proofs + 384 * (size_t)i + 288, 96);
+        memcpy(&p2[192 * (size_t)i], proofs + 384 * (size_t)i + 96, 192);
+    }
+    if (n_io) memcpy(&p1[96 * 2 * (size_t)count], ltgm_io, 96 * n_io);
+    memcpy(&p2[192 * (size_t)count], gm, 192);
+    memcpy(&p2[192 * ((size_t)count + 1)], d, 192);
+    ZKCHK(check_points(p1.data(), p1.size() / 96, p2.data(), p2.size() / 192, v1, v2, s));
+    // the key, in the host's order (gm, d, ltgm_io): its defects are the call's
+    if (v2[count]) ZK_FAIL(verdict_code(v2[count]), "verify: bad G2 point");
+    if (v2[count + 1]) ZK_FAIL(verdict_code(v2[count + 1]), "verify: bad G2 point");
+    for (size_t k = 0; k < n_io; k++)
+        if (v1[2 * (size_t)count + k]) ZK_FAIL(verdict_code(v1[2 * (size_t)count + k]), "verify: bad G1 point in the key");
+    // a proof's own: A, B, C in that order, then its public inputs
+    std::vector<int32_t> st(count, ZK_OK);
+    std::vector<uint8_t> live(count, 1);
+    for (uint32_t i = 0; i < count; i++) {
+        const uint8_t v = v1[i] ? v1[i] : v2[i] ? v2[i] : v1[count + i];
+        st[i] = verdict_code(v);
+        for (size_t k = 0; k < n_io && st[i] == ZK_OK; k++)
+            if (!fr_canonical(io_scalars + 32 * (n_io * (size_t)i + k))) st[i] = ZK_ERR_SCALAR_RANGE;
+        live[i] = st[i] == ZK_OK;
+    }
+    std::vector<uint8_t> acc(96 * (size_t)count);
+    ZKCHK(dot_many(0, ltgm_io, n_io, io_scalars, count, live, acc.data()));
+    std::vector<uint8_t> q1(96 * 3 * (size_t)count), q2(192 * 3 * (size_t)count), gt(576 * (size_t)count);
+    for (uint32_t i = 0; i < count; i++) {
+        uint8_t* a = &q1[96 * 3 * (size_t)i];
+        uint8_t* b = &q2[192 * 3 * (size_t)i];
+        if (!live[i]) {          // three pairs that contribute 1
+            for (int k = 0; k < 3; k++) { g1_identity(a + 96 * k); g2_identity(b + 192 * k); }
+            continue;
+        }
+        memcpy(a, proofs + 384 * (size_t)i, 96);
+        g1_neg_bytes(a + 96, &acc[96 * (size_t)i]);
+        g1_neg_bytes(a + 192, proofs + 384 * (size_t)i + 288);
+        memcpy(b, proofs + 384 * (size_t)i + 96, 192);
+        memcpy(b + 192, gm, 192);
+        memcpy(b + 384, d, 192);
+    }
+    const std::vector<uint64_t> lens(count, 3);
+    ZKCHK(run_products(q1.data(), q2.data(), 3 * (uint64_t)count, lens.data(), count, false, v1, v2, gt.data(), s));
+    for (uint32_t i = 0; i < count; i++) {
+        ok[i] = live[i] && memcmp(&gt[576 * (size_t)i], ab, 576) == 0 ? 1 : 0;
+        if (status) status[i] = st[i];
+    }
+    return ZK_OK;
+}
+
+// Verify.f, pinocchio.ml:254-420, as zk_pinocchio_verify decides it: five products of pairings, each equal to 1.
+//   vk_g1 = one | aw | bgm | vv_io[n_io] | yy_io[n_io]      vk_g2 = one2 | av | ay | gm2 | bgm2 | yt | ww_io[n_io]
+//   proof = vv | ww (G2) | yy | h | vavv | waww (G2) | yayy | bvwy
+int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_io, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok,
+                             int32_t* status) {
+    if (!vk_g1 || !vk_g2) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: null argument");
+    if (!count) return ZK_OK;
+    if (!proofs || !ok || (n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: null argument");
+    if (count > MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: more than 2^24 proofs in one call");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    hipStream_t s = ctx().stream;
+    const size_t k1 = 3 + 2 * n_io, k2 = 6 + n_io, c = count;
+    static const size_t P1[6] = {0, 288, 384, 480, 768, 864}, P2[2] = {96, 576};          // a proof's G1 points (vv yy h vavv yayy bvwy) and G2 points (ww waww)
+    std::vector<uint8_t> p1(96 * (k1 + 6 * c)), p2(192 * (k2 + 2 * c)), v1, v2;
+    memcpy(p1.data(), vk_g1, 96 * k1);
+    memcpy(p2.data(), vk_g2, 192 * k2);
+    for (size_t i = 0; i < c; i++) {
+        for (int q = 0; q < 6; q++) memcpy(&p1[96 * (k1 + 6 * i + q)], proofs + 960 * i + P1[q], 96);
+        for (int q = 0; q < 2; q++) memcpy(&p2[192 * (k2 + 2 * i + q)], proofs + 960 * i + P2[q], 192);
+    }
+    ZKCHK(check_points(p1.data(), k1 + 6 * c, p2.data(), k2 + 2 * c, v1, v2, s));
+    // the key in the host's order: one aw bgm | one2 av ay gm2 bgm2 yt | vv_io[k] yy_io[k] ww_io[k] for every k
+    for (size_t k = 0; k < 3; k++)
+        if (v1[k]) ZK_FAIL(verdict_code(v1[k]), "verify: bad G1 point");
+    for (size_t k = 0; k < 6; k++)
+        if (v2[k]) ZK_FAIL(verdict_code(v2[k]), "verify: bad G2 point");
+    for (size_t k = 0; k < n_io; k++) {
+        const uint8_t v = v1[3 + k] ? v1[3 + k] : v1[3 + n_io + k] ? v1[3 + n_io + k] : v2[6 + k];
+        if (v) ZK_FAIL(verdict_code(v), "verify: bad point in the key");
+    }
+    // a proof's own, in the host's order: vv ww yy h vavv waww yayy bvwy, then its public inputs
+    std::vector<int32_t> st(c, ZK_OK);
+    std::vector<uint8_t> live(c, 1);
+    for (size_t i = 0; i < c; i++) {
+        const uint8_t* a = &v1[k1 + 6 * i];
+        const uint8_t* b = &v2[k2 + 2 * i];
+        const uint8_t order[8] = {a[0], b[0], a[1], a[2], a[3], b[1], a[4], a[5]};
+        for (int q = 0; q < 8 && st[i] == ZK_OK; q++) st[i] = verdict_code(order[q]);
+        for (size_t k = 0; k < n_io && st[i] == ZK_OK; k++)
+            if (!fr_canonical(io_scalars + 32 * (n_io * i + k))) st[i] = ZK_ERR_SCALAR_RANGE;
+        live[i] = st[i] == ZK_OK;
+    }
+    // vio, yio, wio (G.dot over the public inputs), then vio + vv, yio + yy, wio + ww
+    std::vector<uint8_t> vio(96 * c), yio(96 * c), wio(192 * c), pv(96 * c), py(96 * c), pw(192 * c);
+    ZKCHK(dot_many(0, vk_g1 + 96 * 3, n_io, io_scalars, count, live, vio.data()));
+    ZKCHK(dot_many(0, vk_g1 + 96 * (3 + n_io), n_io, io_scalars, count, live, yio.data()));
+    ZKCHK(dot_many(1, vk_g2 + 192 * 6, n_io, io_scalars, count, live, wio.data()));
+    for (size_t i = 0; i < c; i++) {
+        if (live[i]) {
+            memcpy(&pv[96 * i], proofs + 960 * i, 96);
+            memcpy(&py[96 * i], proofs + 960 * i + 288, 96);
+            memcpy(&pw[192 * i], proofs + 960 * i + 96, 192);
+        } else {
+            g1_identity(&pv[96 * i]);
+            g1_identity(&py[96 * i]);
+            g2_identity(&pw[192 * i]);
+        }
+    }
+    std::vector<uint8_t> vsum(96 * c), ysum(96 * c), wsum(192 * c);
+    ZKCHK(points_add_pairs(CURVE_G1, vio.data(), pv.data(), c, vsum.data(), s));
+    ZKCHK(points_add_pairs(CURVE_G1, yio.data(), py.data(), c, ysum.data(), s));
+    ZKCHK(points_add_pairs(CURVE_G2, wio.data(), pw.data(), c, wsum.data(), s));
+    // the five equations, 13 pairs per proof
+    const uint8_t *one = vk_g1, *aw = vk_g1 + 96, *bgm = vk_g1 + 192;
+    const uint8_t *one2 = vk_g2, *av = vk_g2 + 192, *ay = vk_g2 + 384, *gm2 = vk_g2 + 576, *bgm2 = vk_g2 + 768, *yt = vk_g2 + 960;
+    std::vector<uint8_t> q1(96 * 13 * c), q2(192 * 13 * c), gt(576 * 5 * c);
+    std::vector<uint64_t> lens(5 * c);
+    for (size_t i = 0; i < c; i++) {
+        uint8_t* a = &q1[96 * 13 * i];
+        uint8_t* b = &q2[192 * 13 * i];
+        static const uint64_t L[5] = {2, 2, 2, 4, 3};
+        for (int q = 0; q < 5; q++) lens[5 * i + q] = L[q];
+        if (!live[i]) {
+            for (int k = 0; k < 13; k++) { g1_identity(a + 96 * k); g2_identity(b + 192 * k); }
+            continue;
+        }
+        const uint8_t* pr = proofs + 960 * i;
+        const uint8_t *vv = pr, *ww = pr + 96, *yy = pr + 288, *h = pr + 384, *vavv = pr + 480, *waww = pr + 576, *yayy = pr + 768, *bvwy = pr + 864;
+        int k = 0;
+        auto pair = [&](const uint8_t* g1p, bool neg, const uint8_t* g2p) {
+            if (neg) g1_neg_bytes(a + 96 * k, g1p);
+            else memcpy(a + 96 * k, g1p, 96);
+            memcpy(b + 192 * k, g2p, 192);
+            k++;
+        };
+        pair(vv, false, av); pair(vavv, true, one2);                                                         // :285
+        pair(aw, false, ww); pair(one, true, waww);                                                          // :298
+        pair(yy, false, ay); pair(yayy, true, one2);                                                         // :311
+        pair(bvwy, false, gm2); pair(vv, true, bgm2); pair(bgm, true, ww); pair(yy, true, bgm2);             // :361-366
+        pair(&vsum[96 * i], false, &wsum[192 * i]); pair(&ysum[96 * i], true, one2); pair(h, true, yt);      // :418-420
+    }
+    ZKCHK(run_products(q1.data(), q2.data(), 13 * (uint64_t)c, lens.data(), 5 * count, false, v1, v2, gt.data(), s));
+    uint8_t gt_one[576];
+    memset(gt_one, 0, 576);
+    gt_one[47] = 1;
+    for (size_t i = 0; i < c; i++) {
+        bool good = live[i] != 0;
+        for (int q = 0; q < 5; q++) good = good && memcmp(&gt[576 * (5 * i + q)], gt_one, 576) == 0;
+        ok[i] = good ? 1 : 0;
+        if (status) status[i] = st[i];
+    }
+    return ZK_OK;
+}
+
+int zk_selftest_fp12(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+    if (!a || !out || !n || op < 0 || op > 7 || ((op == 0 || op == 6) && !b) || n >= ((size_t)1 << 24))
+        ZK_FAIL(ZK_ERR_ARG, "zk_selftest_fp12: null argument, no elements, or an operation outside 0..7");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    hipStream_t s = ctx().stream;
+    DevBuf da, db, dout, flag;
+    ZKCHK(da.alloc(576 * n));
+    ZKCHK(db.alloc(576 * n));
+    ZKCHK(dout.alloc(576 * n));
+    ZKCHK(flag.alloc(4));
+    HIPCHK(hipMemsetAsync(flag.p, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(da.p, a, 576 * n, hipMemcpyHostToDevice, s));
+    if (b) HIPCHK(hipMemcpyAsync(db.p, b, 576 * n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_selftest_fp12, grid_for(n, f12::GROUPS_PER_WAVE), dim3(64), 0, s, op, (const uint8_t*)da.as<uint8_t>(), (const uint8_t*)db.as<uint8_t>(), (uint32_t)n,
+                       dout.as<uint8_t>(), flag.as<int>());
+    HIPCHK(hipGetLastError());
+    int h = 0;
+    HIPCHK(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, dout.p, 576 * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_fp12: a coefficient is >= p");
+    return ZK_OK;
+}
+}

@@ -272,7 +272,8 @@ class GT:
 
 
 class Pairing:
-    """Curve.S.Pairing (src/lib/zk/curve.mli:46-54) on the host: a handful of pairings per verification."""
+    """Curve.S.Pairing (src/lib/zk/curve.mli:46-54).  product / pairing run on the host (csrc/pairing_host.hip): a handful of pairings per
+    verification.  product_many runs on the device (csrc/pairing_dev.hip): many products per call, the same bytes."""
 
     @staticmethod
     def product(g1_points, g2_points):
@@ -288,4 +289,24 @@ class Pairing:
     @staticmethod
     def pairing(p, q):
         return Pairing.product(bytes(p), bytes(q))
+
+    @staticmethod
+    def product_many(g1_points, g2_points, lens):
+        """zk_pairing_product_many, on the DEVICE: product k takes lens[k] pairs, the pairs of all products concatenated in g1_points /
+        g2_points.  Returns one GT encoding per product, each what `product` returns for those pairs; a bad point raises ZkError with the code
+        of the first one.  There is no host fallback: without a GPU the call raises."""
+        g1, g2 = bytes(g1_points), bytes(g2_points)
+        lens = [int(x) for x in lens]
+        n = sum(lens)
+        if min(lens, default=0) < 0 or len(g1) != 96 * n or len(g2) != 192 * n:
+            raise ValueError("pairing products: the lengths must add up to the number of G1 and of G2 points")
+        count = len(lens)
+        out = np.zeros(GT.BYTES * count, dtype=np.uint8)
+        if count:
+            l64 = (C.c_uint64 * count)(*lens)
+            p1, k1 = _lib.u8(g1)
+            p2, k2 = _lib.u8(g2)
+            _lib.check(_lib.lib().zk_pairing_product_many(p1 if n else None, p2 if n else None, l64, C.c_uint32(count), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        raw = out.tobytes()
+        return [raw[GT.BYTES * k:GT.BYTES * (k + 1)] for k in range(count)]
 

@@ -496,7 +496,7 @@ class Groth16:
     def verify(input_output, vkey, proof):
         """Groth16.verify (groth16.ml:163-173): e(A, B) = ab * e(sum_k w_k [L_k(tau)/gamma]_1, gamma) * e(C, delta).
         input_output: the public coefficients in the key's variable order (ints or 32-byte LE blocks).
-        Host work (three pairings), as in the reference."""
+        Host work (three pairings), as in the reference; verify_many checks a batch on the device."""
         io = input_output if isinstance(input_output, (bytes, bytearray, np.ndarray)) else fr_bytes(list(input_output))
         io = np.ascontiguousarray(np.frombuffer(bytes(io), dtype=np.uint8))
         lt = np.ascontiguousarray(vkey.ltgm_io, dtype=np.uint8).reshape(-1)
@@ -508,6 +508,37 @@ class Groth16:
                                                 bytes(vkey.gm), bytes(vkey.d), bytes(proof.a) + bytes(proof.b) + bytes(proof.c), C.byref(ok)))
         return bool(ok.value)
 
+    @staticmethod
+    def verify_many(input_outputs, vkey, proofs, return_status=False):
+        """`verify` for many proofs under one key in ONE call, on the DEVICE (zk_groth16_verify_many, csrc/pairing_dev.hip; no host fallback).
+        input_outputs[i]: the public coefficients of proofs[i].  Returns a list of bool; with return_status also the list of codes the
+        single-proof call would return for each proof (0, ZK_ERR_ARG / ZK_ERR_NOT_ON_CURVE for a bad point of the proof, ZK_ERR_SCALAR_RANGE):
+        a defective proof is False, it does not raise.  A defective KEY raises, as in `verify`."""
+        proofs = list(proofs)
+        input_outputs = list(input_outputs)
+        if len(input_outputs) != len(proofs):
+            raise ValueError("verify_many: need one list of public inputs per proof")
+        lt = np.ascontiguousarray(vkey.ltgm_io, dtype=np.uint8).reshape(-1)
+        n_io = len(lt) // 96
+        ios = []
+        for io in input_outputs:
+            io = io if isinstance(io, (bytes, bytearray, np.ndarray)) else fr_bytes(list(io))
+            io = bytes(io)
+            if len(io) != 32 * n_io:
+                raise AssertionError("Variable not found")          # var.ml:75-77 / curve.ml:96-100: domains must agree
+            ios.append(io)
+        count = len(proofs)
+        ok = np.zeros(max(count, 1), dtype=np.uint8)
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        io_all = np.frombuffer(b"".join(ios), dtype=np.uint8)
+        pr_all = np.frombuffer(b"".join(bytes(p.a) + bytes(p.b) + bytes(p.c) for p in proofs), dtype=np.uint8)
+        if len(pr_all) != 384 * count:
+            raise ValueError("verify_many: a proof is not 96 + 192 + 96 bytes")
+        ab, gm, d = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (vkey.ab, vkey.gm, vkey.d))
+        _lib.check(_lib.lib().zk_groth16_verify_many(_p(ab), _p(lt) if n_io else None, C.c_size_t(n_io), _p(gm), _p(d), _p(io_all) if n_io and count else None,
+                                                     _p(pr_all) if count else None, C.c_uint32(count), _p(ok), status.ctypes.data_as(C.POINTER(C.c_int32))))
+        res = [bool(x) for x in ok[:count]]
+        return (res, [int(x) for x in status[:count]]) if return_status else res
 
 
 class GroupProver:

@@ -215,7 +215,7 @@ class _Prover:
 
 def verify(input_output, vkey: VKey, proof: Proof):
     """Verify.f (pinocchio.ml:254-420): the four knowledge-of-coefficient checks and the divisibility check,
-    13 pairings on the host.  input_output: the public coefficients c_k in the key's variable order."""
+    13 pairings on the host (verify_many checks a batch on the device).  input_output: the public coefficients c_k in the key's variable order."""
     io = input_output if isinstance(input_output, (bytes, bytearray, np.ndarray)) else fr_bytes(list(input_output))
     io = np.ascontiguousarray(np.frombuffer(bytes(io), dtype=np.uint8))
     n_io = len(io) // 32
@@ -228,9 +228,42 @@ def verify(input_output, vkey: VKey, proof: Proof):
     return bool(ok.value)
 
 
+def verify_many(input_outputs, vkey: VKey, proofs, return_status=False):
+    """`verify` for many proofs under one key in ONE call, on the DEVICE (zk_pinocchio_verify_many, csrc/pairing_dev.hip; no host fallback).
+    input_outputs[i]: the public coefficients of proofs[i].  Returns a list of bool; with return_status also the list of codes the single-proof
+    call would return for each proof.  A defective proof is False, it does not raise; a defective KEY raises, as in `verify`."""
+    proofs = list(proofs)
+    input_outputs = list(input_outputs)
+    if len(input_outputs) != len(proofs):
+        raise ValueError("verify_many: need one list of public inputs per proof")
+    g1 = np.ascontiguousarray(vkey.g1, dtype=np.uint8).reshape(-1)
+    g2 = np.ascontiguousarray(vkey.g2, dtype=np.uint8).reshape(-1)
+    n_io = len(g2) // 192 - 6
+    if n_io < 0 or len(g1) != 96 * (3 + 2 * n_io) or len(g2) != 192 * (6 + n_io):
+        raise AssertionError("Variable not found")
+    ios = []
+    for io in input_outputs:
+        io = bytes(io if isinstance(io, (bytes, bytearray, np.ndarray)) else fr_bytes(list(io)))
+        if len(io) != 32 * n_io:
+            raise AssertionError("Variable not found")          # domains of the key maps and of the public inputs must agree
+        ios.append(io)
+    count = len(proofs)
+    ok = np.zeros(max(count, 1), dtype=np.uint8)
+    status = np.zeros(max(count, 1), dtype=np.int32)
+    io_all = np.frombuffer(b"".join(ios), dtype=np.uint8)
+    pr_all = np.frombuffer(b"".join(bytes(p.to_bytes()) for p in proofs), dtype=np.uint8)
+    if len(pr_all) != 960 * count:
+        raise ValueError("verify_many: a proof is not 960 bytes")
+    _lib.check(_lib.lib().zk_pinocchio_verify_many(_p(g1), _p(g2), C.c_size_t(n_io), _p(io_all) if n_io and count else None, _p(pr_all) if count else None,
+                                                   C.c_uint32(count), _p(ok), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    res = [bool(x) for x in ok[:count]]
+    return (res, [int(x) for x in status[:count]]) if return_status else res
+
+
 class ZK(_Prover):
     keygen = staticmethod(keygen)
     verify = staticmethod(verify)
+    verify_many = staticmethod(verify_many)
 
     def prove(self, rng, sol):
         dv = rng() % FR_MODULUS     # pinocchio.ml:428-430: dv, dw, dy in this order
@@ -242,6 +275,7 @@ class ZK(_Prover):
 class NonZK(_Prover):
     keygen = staticmethod(keygen)
     verify = staticmethod(verify)
+    verify_many = staticmethod(verify_many)
 
     def prove(self, _rng, sol):
         return self.prove_with(sol, 0, 0, 0)
