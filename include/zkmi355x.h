@@ -433,6 +433,33 @@ int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t 
                              const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 960 */, uint32_t count,
                              uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
 
+/* ---- verification keys resident on the device (zukelang_amd/csrc/verify_resident.hip) ----------------------
+ * A verifier checks a stream of proofs under ONE key (Groth16.verify, groth16.ml:163-173; Verify.f, pinocchio.ml:254-420), and the key's points pass
+ * of_bytes_exn once when the key is read (curve.ml:199-212), not once per proof.  The _many calls above decode and check the key in every call; a
+ * handle does it once, at upload, and keeps on the device: gm and d (Pinocchio: the nine fixed key points) as decoded points, the IO points as a
+ * narrow window table for one short product per proof, the 576 bytes of ab as given, and workspaces that grow on demand and are reused.  A verify
+ * call then costs one H2D copy (proofs | public inputs), the kernels and one D2H copy (ok | status).
+ *   Upload: the key laid out as for zk_groth16_verify / zk_pinocchio_verify.  Every point is checked (encoding: ZK_ERR_ARG; curve and subgroup:
+ *   ZK_ERR_NOT_ON_CURVE); a bad point fails the upload with the code, and in the order, the _many call reports it (Groth16: gm, d, ltgm_io[k]), and
+ *   no handle is made.  The subgroup test is by endomorphism -- P in G1 <=> [z^2] P = (beta^2 x, -y), Q in G2 <=> psi(Q) = [z] Q: 2 x 63 and 63
+ *   doublings instead of the 254 of [r] P = O -- the same predicate on every point of the curve.  A malformed ab is kept: every ok is then 0, as
+ *   above.  n_io = 0 is legal; n_io > 8192 -> ZK_ERR_ARG (the table of the short products; the _many calls have no such limit).
+ *   Verify: ok and status are byte for byte those of zk_groth16_verify_many / zk_pinocchio_verify_many on the same key and inputs.  An unknown or
+ *   freed handle, or a handle of the other protocol -> ZK_ERR_HANDLE; then count = 0 -> ZK_OK, nothing touched; a null pointer (status excepted;
+ *   io_scalars when n_io = 0) -> ZK_ERR_ARG; count > 2^24 -> ZK_ERR_ARG.  Without a GPU every upload is ZK_ERR_HIP, so no handle exists.
+ *   The handle lives on the first device of the list at upload, is called from one host thread like the key handles, and counts as a live key
+ *   handle for zk_set_devices / zk_set_device_list; zk_shutdown frees it.  Kernel families under zk_profile_get: verify_point_checks, msm_short,
+ *   pairing_miller, pairing_final_exp.  No option is read. */
+int zk_groth16_vk_upload(const uint8_t ab[576], const uint8_t* ltgm_io /* n_io * 96 */, size_t n_io, const uint8_t gm[192], const uint8_t d[192],
+                         uint64_t* handle);
+int zk_pinocchio_vk_upload(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_io, uint64_t* handle);
+int zk_vk_info(uint64_t handle, int* protocol /* 0 Groth16, 1 Pinocchio */, uint64_t* n_io);   /* any out may be NULL */
+int zk_vk_free(uint64_t handle);
+int zk_groth16_verify_resident(uint64_t handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 384 */,
+                               uint32_t count, uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
+int zk_pinocchio_verify_resident(uint64_t handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 960 */,
+                                 uint32_t count, uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------
  * With profiling on, kernel families are bracketed by HIP events on the stream they run on;
  * zk_profile_get returns the summed milliseconds and launch count since the last reset. */
@@ -462,6 +489,11 @@ int zk_selftest_sqrt(int field, const uint8_t* a, size_t n, uint8_t* root, uint8
  * of b's coefficients of w^0, w^3, w^5 (the shape of a Miller line: c0.c0, c1.c1, c1.c2) | 7: a^((p^12 - 1) / r).  b is read by ops 0 and 6.
  * A coefficient >= p -> ZK_ERR_ARG. */
 int zk_selftest_fp12(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
+/* The two subgroup kernels side by side (tests/test_gpu_subgroup_endo.py): n uncompressed points of group 0 (G1, 96 B) or 1 (G2, 192 B) through the
+ * decoder and then method 0: [r] P = O (what the _many verifiers and the key uploads run) | 1: by endomorphism (what the resident verification keys
+ * run).  verdict[i] = 0 good (the identity included) | 2 bad encoding | 1 not on the curve | 4 on the curve, outside the subgroup.  A null pointer,
+ * n = 0, another group or method -> ZK_ERR_ARG before the device is touched. */
+int zk_selftest_subgroup(int group, int method, const uint8_t* points, size_t n, uint8_t* verdict);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

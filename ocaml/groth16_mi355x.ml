@@ -15,6 +15,7 @@
                 the key's bytes and a live handle in Lagrange form come back (a multi-device list: the bytes, then the ordinary upload)
      verify  groth16.ml:163-173 -> unchanged in substance: three pairings of the host's own Pairing
              verify_many (an extra): a list of proofs under one key -> one call zk_groth16_verify_many, the pairings on the device
+             Verifier (an extra): the key resident on the device, create / verify_many / free -> a call moves only proofs and public inputs
    The records and their yojson are the reference's (groth16.ml:24-43,110-114): the JSON of keys and proofs is the wire format. *)
 
 open Zukelang
@@ -296,4 +297,37 @@ module Make (C : Curve.S) = struct
            (bytes_start (G2.to_bytes vkey.d))
            (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
     List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
+
+  (* ---------------------------------------------------------------- Verifier
+     The same for a STREAM of batches under one key: `create` hands the key to the device once (zk_groth16_vk_upload: its points decoded and
+     checked there, a bad key point raises as in `verify`), every `verify_many` then moves only the proofs and their public inputs
+     (zk_groth16_verify_resident), `free` releases the handle.  The lists are those of the function above on the same key. *)
+  module Verifier = struct
+    type t = { handle : Unsigned.UInt64.t; domain : Var.Set.t }
+
+    let create (vkey : vkey) : t =
+      Lazy.force gt_order_checked;
+      let h = Ctypes.allocate Ctypes.uint64_t Unsigned.UInt64.zero in
+      Mi355x.(
+        check
+          (zk_groth16_vk_upload
+             (bytes_start (gt_lib_bytes vkey.ab))
+             (bytes_start (g1_bytes (values vkey.ltgm_io)))
+             (sz (Var.Map.cardinal vkey.ltgm_io))
+             (bytes_start (G2.to_bytes vkey.gm))
+             (bytes_start (G2.to_bytes vkey.d))
+             h));
+      { handle = Ctypes.( !@ ) h; domain = Var.Map.domain vkey.ltgm_io }
+
+    let verify_many (t : t) (jobs : (f Var.Map.t * proof) list) : bool list =
+      List.iter (fun (io, _) -> assert (Var.Set.equal (Var.Map.domain io) t.domain)) jobs;
+      let count = List.length jobs in
+      let ok = Bytes.make (max count 1) (Char.chr 0) in
+      let io_all = fr_bytes (List.concat_map (fun (io, _) -> values io) jobs) in
+      let proofs = Mi355x.cat (List.concat_map (fun (_, (p : proof)) -> [ G1.to_bytes p.a; G2.to_bytes p.b; G1.to_bytes p.c ]) jobs) in
+      Mi355x.(check (zk_groth16_verify_resident t.handle (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
+      List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
+
+    let free (t : t) = Mi355x.vk_free t.handle
+  end
 end

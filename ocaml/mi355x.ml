@@ -286,6 +286,23 @@ let zk_pinocchio_verify_many =
 
 let no_status : int32 ptr = from_voidp int32_t null
 
+(* Verification keys resident on the device (include/zkmi355x.h, "verification keys resident on the device"): the key decoded and checked once,
+   then one call per list of proofs that moves only the proofs and their public inputs.  Same ok / status as the _many calls. *)
+let zk_groth16_vk_upload =
+  fn "zk_groth16_vk_upload" (ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ocaml_bytes @-> ptr uint64_t @-> returning int)
+
+let zk_pinocchio_vk_upload = fn "zk_pinocchio_vk_upload" (ocaml_bytes @-> ocaml_bytes @-> size_t @-> ptr uint64_t @-> returning int)
+let zk_vk_info = fn "zk_vk_info" (uint64_t @-> ptr int @-> ptr uint64_t @-> returning int)
+let zk_vk_free = fn "zk_vk_free" (uint64_t @-> returning int)
+
+let zk_groth16_verify_resident =
+  fn "zk_groth16_verify_resident" (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
+
+let zk_pinocchio_verify_resident =
+  fn "zk_pinocchio_verify_resident" (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
+
+let vk_free (h : Unsigned.UInt64.t) = ignore (zk_vk_free h)
+
 let groth16_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in
   check

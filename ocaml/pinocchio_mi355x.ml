@@ -14,6 +14,7 @@
                   four knowledge-of-coefficient checks and returns the divisibility check, this returns false for any failing
                   check.
      verify_many  (an extra) a list of proofs under one key              -> one call zk_pinocchio_verify_many, the pairings on the device
+     Verifier     (an extra) the key resident on the device: create / verify_many / free -> a call moves only proofs and public inputs
    Records and their yojson are the reference's (pinocchio.ml:37-75,195-208). *)
 
 open Zukelang
@@ -308,6 +309,40 @@ module Make (C : Curve.S) = struct
            (sz (Var.Map.cardinal vk.vv_io))
            (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
     List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
+
+  (* The same for a STREAM of batches under one key: `create` hands the key to the device once (zk_pinocchio_vk_upload: its points decoded and checked
+     there, a bad key point raises as in verify_with), every `verify_many` then moves only the proofs and their public inputs
+     (zk_pinocchio_verify_resident), `free` releases the handle.  Serves NonZK and ZK alike: they share the verifier. *)
+  module Verifier = struct
+    type t = { handle : Unsigned.UInt64.t; domain : Var.Set.t }
+
+    let create (vk : vkey) : t =
+      assert (Var.Set.equal (Var.Map.domain vk.vv_io) (Var.Map.domain vk.ww_io));
+      assert (Var.Set.equal (Var.Map.domain vk.vv_io) (Var.Map.domain vk.yy_io));
+      let vk_g1 = g1_bytes ((vk.one :: vk.aw :: vk.bgm :: values vk.vv_io) @ values vk.yy_io) in
+      let vk_g2 = g2_bytes (vk.one2 :: vk.av :: vk.ay :: vk.gm2 :: vk.bgm2 :: vk.yt :: values vk.ww_io) in
+      let h = Ctypes.allocate Ctypes.uint64_t Unsigned.UInt64.zero in
+      Mi355x.(check (zk_pinocchio_vk_upload (bytes_start vk_g1) (bytes_start vk_g2) (sz (Var.Map.cardinal vk.vv_io)) h));
+      { handle = Ctypes.( !@ ) h; domain = Var.Map.domain vk.vv_io }
+
+    let verify_many (t : t) (jobs : (Fr.t Var.Map.t * proof) list) : bool list =
+      List.iter (fun (ios, _) -> assert (Var.Set.equal (Var.Map.domain ios) t.domain)) jobs;
+      let proofs =
+        Mi355x.cat
+          (List.concat_map
+             (fun (_, (p : proof)) ->
+               [ G1.to_bytes p.vv; G2.to_bytes p.ww; G1.to_bytes p.yy; G1.to_bytes p.h; G1.to_bytes p.vavv; G2.to_bytes p.waww;
+                 G1.to_bytes p.yayy; G1.to_bytes p.bvwy ])
+             jobs)
+      in
+      let count = List.length jobs in
+      let ok = Bytes.make (max count 1) (Char.chr 0) in
+      let io_all = fr_bytes (List.concat_map (fun (ios, _) -> values ios) jobs) in
+      Mi355x.(check (zk_pinocchio_verify_resident t.handle (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
+      List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
+
+    let free (t : t) = Mi355x.vk_free t.handle
+  end
 
   module NonZK = struct
     type f = C.Fr.t

@@ -246,7 +246,8 @@ int groth16_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_cs
 }
 uint64_t pinocchio_live_handles();          // pinocchio.hip
 uint64_t resident_live_handles();           // msm_resident.hip: resident MSM bases count as key handles
-uint64_t live_key_handles() { return g_keys.size() + group_live_handles() + pinocchio_live_handles() + resident_live_handles(); }
+uint64_t vk_live_handles();                 // verify_resident.hip: so do resident verification keys
+uint64_t live_key_handles() { return g_keys.size() + group_live_handles() + pinocchio_live_handles() + resident_live_handles() + vk_live_handles(); }
 
 // First half of a proof: Fr stage -> the three scalar vectors (canonical Fr, FULL pool lengths p1, p1, p2)
 // written to dA / dC / dB (device memory; the slot's own buffers in the single-call path).

@@ -130,6 +130,20 @@ int points_bytes_to_affine(Curve curve, void* d_affine, const void* d_bytes, uin
 int points_affine_to_bytes(Curve curve, void* d_bytes, const void* d_affine, uint64_t n, hipStream_t s);
 // decode + curve check (+ [r] P = O) with one verdict byte per point: 0 good | 2 encoding | 1 curve | 4 subgroup; rejected points become the identity
 int points_decode_verdicts(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, uint8_t* d_verdict, bool check_subgroup, hipStream_t s);
+// the same, the subgroup verdict by the curve's endomorphism (msm_points.hip: k_subgroup_verdict_endo): 2 x 63 doublings in G1, 63 in G2 instead of 254
+int points_decode_verdicts_endo(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, uint8_t* d_verdict, hipStream_t s);
+// ---- what the resident verification keys (verify_resident.hip) take from the other units, all on device buffers
+// the two pairing kernels (pairing_dev.hip): product q = the checked dense affine pairs [d_off[q], d_off[q + 1]) -> 576 B of GT each; enqueues only
+size_t pairing_miller_bytes(uint64_t npairs);
+int pairing_products_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t npairs, const uint32_t* d_off, uint32_t count, uint32_t* d_miller, uint8_t* d_gt, hipStream_t s);
+// the short products of msm_resident.hip over a narrow table of n <= SHORT_BASES_MAX subgroup points: product i = sum_k scalars[i n + k] P_k as dense XYZZ,
+// the identity where d_live[i] == 0 (those scalars are not read).  The scalars must be canonical: the caller has checked them.  Enqueues only.
+struct ShortBases;
+static constexpr uint64_t SHORT_BASES_MAX = 8192;
+int short_bases_create(ShortBases** out, Curve curve, const void* d_affine, uint64_t n, hipStream_t s);
+void short_bases_free(ShortBases* b);
+int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_live, uint32_t count, uint8_t* d_out_xyzz, hipStream_t s);
+int points_selftest_subgroup(Curve curve, int method, const uint8_t* points, uint64_t n, uint8_t* verdict, hipStream_t s);          // zk_selftest_subgroup
 // out[i] = a[i] + b[i] over encoded, already checked points (host bytes in, host bytes out)
 int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, hipStream_t s);
 // n ZCash-COMPRESSED points (host, 48 / 96 B) -> uncompressed (host, 96 / 192 B): square roots, curve and subgroup checks on the device (msm_points.hip)

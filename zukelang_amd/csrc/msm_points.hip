@@ -3,6 +3,7 @@
 // prime-order subgroup), the resident window tables 2^(c j) P_i of a base set, the fixed-base products s_i G of keygen (curve.ml:106-109,180)
 // and the sum of partial results across devices.  Split off msm.hip in round 5 (one translation unit per concern: points / sort / dispatch).
 #include "ec.cuh"
+#include "endo_consts.cuh"
 #include "msm.cuh"
 
 #include <stdlib.h>
@@ -315,6 +316,69 @@ template <class F> __global__ __launch_bounds__(128) void k_subgroup_verdict(con
     if (!xyzz_is_inf(acc)) verdict[i] = 4;
 }
 
+// ------------------------------------------------------------------ the same verdict by the curve's endomorphisms (resident verification keys)
+// [r] P = O costs 254 doublings and 127 additions.  Both groups have an endomorphism that acts on the r-torsion as a SHORT scalar, and the curve
+// points on which it acts as that scalar are exactly the subgroup (z = -0xd201000000010000, r = z^4 - z^2 + 1):
+//   G1:  phi(x, y) = (beta x, y) = [z^2 - 1] P.   phi^2 + phi + 1 = 0 on the whole curve, so phi(P) + P = -phi^2(P) = (beta^2 x, -y):
+//        P in G1  <=>  [z^2] P == (beta^2 x, -y).   Two chains over |z|: 2 x (63 doublings + 5 additions).
+//   G2:  psi(x, y) = (cx conj x, cy conj y) = [z] Q.   Q in G2  <=>  [|z|] Q == -psi(Q): one chain.  (ENDO_PSI_X[0], ENDO_PSI_Y[0]) of
+//        endo_consts.cuh IS -psi: the generator folds the sign of the odd digit terms into the y constant.
+// tests/test_subgroup_criterion.py restates both in integers with these constants and holds them to [r] P = O on points of every prime-power order
+// the cofactors allow.  The chain is short, so it meets what a 255-bit chain over a point of order r never meets: on a point of order 3 the
+// accumulator is +-P at an addition step, on points of order 11, 13 or 23 it passes through the identity mid-chain.  xyzz_dbl and xyzz_madd / xyzz_add
+// are the complete operations of ec.cuh (identity operands, P + P, P - P); neither cofactor is even, so no point has y = 0.
+// The comparison is projective (X == x' ZZ, Y == y' ZZZ): no inversion.
+static constexpr uint64_t BLS_Z_ABS = 0xd201000000010000ull;          // |z|: 64 bits, Hamming weight 6
+FF_INLINE FpB<1> endo_const(const uint32_t* __restrict__ c) {
+    FpB<1> r;
+#pragma unroll
+    for (int i = 0; i < FPL; i++) r.v[i] = c[i];
+    return r;
+}
+// [|z|] p, p affine and not the identity
+template <class F> FF_INLINE Xyzz<F> mul_z_aff(const Aff<F>& p) {
+    Xyzz<F> acc = xyzz_from_aff(p);                      // bit 63
+#pragma unroll 1
+    for (int b = 62; b >= 0; b--) {
+        acc = xyzz_dbl(acc);
+        if ((BLS_Z_ABS >> b) & 1u) xyzz_madd(acc, p);          // a compile-time constant: wave-uniform
+    }
+    return acc;
+}
+// [|z|] q, q in XYZZ (the second chain of G1)
+template <class F> FF_INLINE Xyzz<F> mul_z_xyzz(const Xyzz<F>& q) {
+    Xyzz<F> acc = q;
+#pragma unroll 1
+    for (int b = 62; b >= 0; b--) {
+        acc = xyzz_dbl(acc);
+        if ((BLS_Z_ABS >> b) & 1u) xyzz_add(acc, q);
+    }
+    return acc;
+}
+FF_INLINE bool in_subgroup_endo(const Aff<Fp>& p) {
+    const Xyzz<Fp> t = mul_z_xyzz(mul_z_aff(p));         // [z^2] P
+    if (xyzz_is_inf(t)) return false;                    // (beta^2 x, -y) is a point of the curve, never the identity
+    const FpB<2> beta2 = fe_sqr(endo_const(ENDO_BETA));
+    return fe_eq(t.x, fe_mul(fe_mul(beta2, p.x), t.zz)) && fe_eq(t.y, fe_mul(fe_neg(p.y), t.zzz));
+}
+FF_INLINE bool in_subgroup_endo(const Aff<Fp2>& q) {
+    const Xyzz<Fp2> t = mul_z_aff(q);                    // [|z|] Q
+    if (xyzz_is_inf(t)) return false;
+    const Fp2B<1> cx = {endo_const(ENDO_PSI_X[0][0]), endo_const(ENDO_PSI_X[0][1])}, cy = {endo_const(ENDO_PSI_Y[0][0]), endo_const(ENDO_PSI_Y[0][1])};
+    const Fp2B<128> xc = {q.x.c0, fe_neg(q.x.c1)}, yc = {q.y.c0, fe_neg(q.y.c1)};          // conjugates
+    return fe_eq(t.x, fe_mul(fe_mul(cx, xc), t.zz)) && fe_eq(t.y, fe_mul(fe_mul(cy, yc), t.zzz));
+}
+// verdict[i] = 4 where point i of `dense` (affine, on the curve; a point an earlier kernel rejected is stored as the identity) is outside the subgroup;
+// other verdicts stay.  The meaning of k_subgroup_verdict.
+template <class F> __global__ __launch_bounds__(128) void k_subgroup_verdict_endo(const uint8_t* __restrict__ dense, uint64_t n, uint8_t* verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int B = FieldOps<F>::WORDS * 8;
+    const Aff<F> p = aff_load<F>(dense + B * i);
+    if (aff_is_inf(p)) return;
+    if (!in_subgroup_endo(p)) verdict[i] = 4;
+}
+
 // out[i] = a[i] + b[i] on dense affine points, every case of the group law (an identity operand, P + P, P + (-P)): the verifier's vio + vv and the like
 // (pinocchio.ml:418-420), G.add of curve.ml:159-191
 template <class F> __global__ __launch_bounds__(64) void k_aff_add(uint8_t* __restrict__ out, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n) {
@@ -476,6 +540,33 @@ int points_decode_verdicts(Curve curve, void* d_aff, const void* d_bytes, uint64
         if (check_subgroup) hipLaunchKernelGGL(k_subgroup_verdict<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
     }
     HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// the same with the subgroup verdict by endomorphism (k_subgroup_verdict_endo): the resident verification keys' decoder
+int points_decode_verdicts_endo(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, uint8_t* d_verdict, hipStream_t s) {
+    if (!n) return ZK_OK;
+    if (curve == CURVE_G1) {
+        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
+        hipLaunchKernelGGL(k_subgroup_verdict_endo<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+    } else {
+        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
+        hipLaunchKernelGGL(k_subgroup_verdict_endo<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+    }
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// zk_selftest_subgroup: n encoded points (host) -> n verdicts (host) through either subgroup kernel
+int points_selftest_subgroup(Curve curve, int method, const uint8_t* points, uint64_t n, uint8_t* verdict, hipStream_t s) {
+    const size_t ab = aff_bytes(curve);
+    DevBuf raw, aff, dv;
+    ZKCHK(raw.alloc(ab * n));
+    ZKCHK(aff.alloc(ab * n));
+    ZKCHK(dv.alloc(n));
+    HIPCHK(hipMemcpyAsync(raw.p, points, ab * n, hipMemcpyHostToDevice, s));
+    if (method == 0) ZKCHK(points_decode_verdicts(curve, aff.p, raw.p, n, dv.as<uint8_t>(), true, s));
+    else ZKCHK(points_decode_verdicts_endo(curve, aff.p, raw.p, n, dv.as<uint8_t>(), s));
+    HIPCHK(hipMemcpyAsync(verdict, dv.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return ZK_OK;
 }
 // n sums a[i] + b[i] of encoded points (host bytes, both lists already checked) -> n encoded points (host)

@@ -373,6 +373,63 @@ static int res_run(uint64_t handle, const uint8_t* scalars, const uint64_t* lens
     return ZK_OK;
 }
 
+// ---- the short path alone, on device buffers (verify_resident.hip: a verification key's IO points, one product per proof)
+// A narrow table over ALL n points (n <= SHORT_BASES_MAX), built from dense affine points that are already on the device and already known to lie in the
+// subgroup.  No pinned arena, no chain, no host copy: scalars in, dense XYZZ out, both in device memory; nothing here waits for the stream.
+struct ShortBases {
+    Curve curve = CURVE_G1;
+    uint64_t n = 0;
+    MsmBases small;
+    DigitArgs da{};
+    DevBuf jobs, partial, flag;               // SHORT_BASES_CHUNK jobs at most per launch; grown on demand
+    uint32_t cap_jobs = 0;
+};
+static constexpr uint32_t SHORT_BASES_CHUNK = 4096;          // products per launch (blockIdx.y): 16 / 32 MiB of bucket partials
+// job i of a launch: the scalars [i n, (i + 1) n) of the launch's block, none when live[i] == 0 (the product is then the identity, its scalars unread)
+__global__ void k_short_jobs(ResidentJob* jobs, const uint8_t* __restrict__ live, uint32_t count, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    jobs[i] = ResidentJob{i * n, live[i] ? n : 0u, 0u, 0u};
+}
+int short_bases_create(ShortBases** out, Curve curve, const void* d_affine, uint64_t n, hipStream_t s) {
+    if (n == 0 || n > SHORT_BASES_MAX) ZK_FAIL(ZK_ERR_ARG, "short bases: 1 .. 2^13 points");
+    auto h = std::make_unique<ShortBases>();
+    h->curve = curve;
+    h->n = n;
+    ZKCHK(msm_bases_from_device_affine(h->small, curve, d_affine, n, SHORT_C, true, s, true));
+    h->da = DigitArgs{n, h->small.c, h->small.nw, 1u, SHORT_BUCKETS, {0, 0, 0, 0, 0, 0, 0, 0, 0}, h->small.ident.as<uint8_t>(), 0u, 0u, 0u, h->small.fold ? 1u : 0u};
+    digit_constant(h->small.c, h->small.nw, h->da.K);
+    ZKCHK(h->flag.alloc(16));
+    *out = h.release();
+    return ZK_OK;
+}
+void short_bases_free(ShortBases* b) { delete b; }
+int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_live, uint32_t count, uint8_t* d_out_xyzz, hipStream_t s) {
+    const uint32_t want = count < SHORT_BASES_CHUNK ? count : SHORT_BASES_CHUNK;
+    if (want > b.cap_jobs) {
+        HIPCHK(hipStreamSynchronize(s));          // the buffers about to go may still be read
+        ZKCHK(b.jobs.alloc(sizeof(ResidentJob) * (size_t)want));
+        ZKCHK(b.partial.alloc((size_t)(b.curve == CURVE_G1 ? RawLayout<Fp>::XYZZ : RawLayout<Fp2>::XYZZ) * SHORT_BUCKETS * want));
+        b.cap_jobs = want;
+    }
+    const size_t xb = xyzz_bytes(b.curve);
+    ScopedTimer t("msm_short", s);
+    for (uint32_t k = 0; k < count; k += SHORT_BASES_CHUNK) {
+        const uint32_t cnt = count - k < SHORT_BASES_CHUNK ? count - k : SHORT_BASES_CHUNK;
+        hipLaunchKernelGGL(k_short_jobs, grid_for(cnt, 256), dim3(256), 0, s, b.jobs.as<ResidentJob>(), d_live + k, cnt, (uint32_t)b.n);
+        const dim3 grid(SHORT_BUCKETS, cnt);
+        const uint32_t* sc = d_scalars + 8 * b.n * (uint64_t)k;
+        if (b.curve == CURVE_G1)
+            hipLaunchKernelGGL(k_msm_short<Fp>, grid, dim3(SHORT_THREADS), 0, s, (const uint8_t*)b.small.table.as<uint8_t>(), b.da, b.jobs.as<ResidentJob>(), sc,
+                               b.partial.as<uint8_t>(), d_out_xyzz + xb * k, b.flag.as<int>());
+        else
+            hipLaunchKernelGGL(k_msm_short<Fp2>, grid, dim3(SHORT_THREADS), 0, s, (const uint8_t*)b.small.table.as<uint8_t>(), b.da, b.jobs.as<ResidentJob>(), sc,
+                               b.partial.as<uint8_t>(), d_out_xyzz + xb * k, b.flag.as<int>());
+        HIPCHK(hipGetLastError());
+    }
+    return ZK_OK;
+}
+
 }  // namespace zk
 
 using namespace zk;

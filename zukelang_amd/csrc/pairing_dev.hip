@@ -115,6 +115,24 @@ static int check_points(const uint8_t* g1, uint64_t n1, const uint8_t* g2, uint6
     return ZK_OK;
 }
 
+// The two pairing kernels on buffers that are ALREADY on the device: npairs checked dense affine pairs (d_g1: 96 B each, d_g2: 192 B), product q = the
+// pairs [d_off[q], d_off[q + 1]) -> count GT encodings in d_gt (576 B each).  d_miller: F12_RAW_WORDS words per pair.  Enqueues, does not wait.
+size_t pairing_miller_bytes(uint64_t npairs) { return (size_t)F12_RAW_WORDS * 4 * npairs; }
+int pairing_products_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t npairs, const uint32_t* d_off, uint32_t count, uint32_t* d_miller, uint8_t* d_gt, hipStream_t s) {
+    if (npairs >= ((uint64_t)1 << 31)) ZK_FAIL(ZK_ERR_ARG, "pairing products: too many pairs for one call");
+    if (npairs) {
+        ScopedTimer t("pairing_miller", s);
+        hipLaunchKernelGGL(k_miller, grid_for(npairs, f12::GROUPS_PER_WAVE), dim3(64), 0, s, d_g1, d_g2, (uint32_t)npairs, d_miller);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ScopedTimer t("pairing_final_exp", s);
+        hipLaunchKernelGGL(k_final_exp, grid_for(count, f12::GROUPS_PER_WAVE), dim3(64), 0, s, (const uint32_t*)d_miller, d_off, count, d_gt);
+        HIPCHK(hipGetLastError());
+    }
+    return ZK_OK;
+}
+
 // count products over npairs = sum lens pairs (host bytes) -> count GT encodings.  check: every point's subgroup membership too (else encoding and
 // curve only: the caller has checked them).  v1 / v2: the verdicts, one per pair and side; a rejected point counts as the identity.
 static int run_products(const uint8_t* g1, const uint8_t* g2, uint64_t npairs, const uint64_t* lens, uint32_t count, bool check, std::vector<uint8_t>& v1,
@@ -146,17 +164,8 @@ static int run_products(const uint8_t* g1, const uint8_t* g2, uint64_t npairs, c
         }
         HIPCHK(hipMemcpyAsync(v1.data(), dv.p, npairs, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + npairs, npairs, hipMemcpyDeviceToHost, s));
-        ScopedTimer t("pairing_miller", s);
-        hipLaunchKernelGGL(k_miller, grid_for(npairs, f12::GROUPS_PER_WAVE), dim3(64), 0, s, (const uint8_t*)a1.as<uint8_t>(), (const uint8_t*)a2.as<uint8_t>(),
-                           (uint32_t)npairs, dm.as<uint32_t>());
-        HIPCHK(hipGetLastError());
     }
-    {
-        ScopedTimer t("pairing_final_exp", s);
-        hipLaunchKernelGGL(k_final_exp, grid_for(count, f12::GROUPS_PER_WAVE), dim3(64), 0, s, (const uint32_t*)dm.as<uint32_t>(), (const uint32_t*)doff.as<uint32_t>(),
-                           count, dgt.as<uint8_t>());
-        HIPCHK(hipGetLastError());
-    }
+    ZKCHK(pairing_products_device(a1.as<uint8_t>(), a2.as<uint8_t>(), npairs, doff.as<uint32_t>(), count, dm.as<uint32_t>(), dgt.as<uint8_t>(), s));
     HIPCHK(hipMemcpyAsync(gt_out, dgt.p, 576 * (size_t)count, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return ZK_OK;

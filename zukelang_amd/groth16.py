@@ -54,6 +54,57 @@ class PKey:
     lag_g2: np.ndarray = None
 
 
+class ResidentVKey:
+    """A verification key decoded and checked ONCE and kept on the device (include/zkmi355x.h, "verification keys resident on the device";
+    csrc/verify_resident.hip): what VKey.resident() returns, for Groth16 and Pinocchio alike.  verify_many gives the lists Groth16.verify_many /
+    pinocchio.verify_many give under the same key; a defective KEY raises where this object is made.  One host thread; close() (or `with`) frees it."""
+
+    def __init__(self, handle, n_io, proof_bytes, proof_len, call):
+        self.handle, self.n_io, self._proof_bytes, self._proof_len, self._call = handle, n_io, proof_bytes, proof_len, call
+
+    def verify_many(self, input_outputs, proofs, return_status=False):
+        if not self.handle:
+            raise ValueError("verify_many: the resident key is closed")
+        proofs = list(proofs)
+        input_outputs = list(input_outputs)
+        if len(input_outputs) != len(proofs):
+            raise ValueError("verify_many: need one list of public inputs per proof")
+        ios = []
+        for io in input_outputs:
+            io = bytes(io if isinstance(io, (bytes, bytearray, np.ndarray)) else fr_bytes(list(io)))
+            if len(io) != 32 * self.n_io:
+                raise AssertionError("Variable not found")          # var.ml:75-77 / curve.ml:96-100: domains must agree
+            ios.append(io)
+        count = len(proofs)
+        ok = np.zeros(max(count, 1), dtype=np.uint8)
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        io_all = np.frombuffer(b"".join(ios), dtype=np.uint8)
+        pr_all = np.frombuffer(b"".join(self._proof_bytes(p) for p in proofs), dtype=np.uint8)
+        if len(pr_all) != self._proof_len * count:
+            raise ValueError("verify_many: a proof is not %d bytes" % self._proof_len)
+        _lib.check(getattr(_lib.lib(), self._call)(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
+                                                   C.c_uint32(count), _p(ok), status.ctypes.data_as(C.POINTER(C.c_int32))))
+        res = [bool(x) for x in ok[:count]]
+        return (res, [int(x) for x in status[:count]]) if return_status else res
+
+    def close(self):
+        if self.handle:
+            _lib.lib().zk_vk_free(C.c_uint64(self.handle))
+            self.handle = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class VKey:
     """groth16.ml:36-43.  `ab` = e(alpha, beta) as a GT element (576 B, see curve.GT)."""
@@ -63,6 +114,17 @@ class VKey:
     gm: bytes
     d: bytes
     ab: bytes = b""
+
+    def resident(self):
+        """This key on the device (zk_groth16_vk_upload): its points decoded and checked once, then verify_many(input_outputs, proofs) per batch."""
+        lt = np.ascontiguousarray(self.ltgm_io, dtype=np.uint8).reshape(-1)
+        n_io = len(lt) // 96
+        ab, gm, d = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (self.ab, self.gm, self.d))
+        if len(ab) != 576 or len(gm) != 192 or len(d) != 192 or len(lt) != 96 * n_io:
+            raise ValueError("resident: the key is not 576 + n_io * 96 + 192 + 192 bytes")
+        h = C.c_uint64(0)
+        _lib.check(_lib.lib().zk_groth16_vk_upload(_p(ab), _p(lt) if n_io else None, C.c_size_t(n_io), _p(gm), _p(d), C.byref(h)))
+        return ResidentVKey(h.value, n_io, lambda p: bytes(p.a) + bytes(p.b) + bytes(p.c), 384, "zk_groth16_verify_resident")
 
 
 @dataclass

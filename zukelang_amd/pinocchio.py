@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from .curve import G1, G2
-from .groth16 import _csr, _lagrange_at, _p, columns_at, ZK_ERR_REMAINDER
+from .groth16 import _csr, _lagrange_at, _p, columns_at, ResidentVKey, ZK_ERR_REMAINDER
 from .r1cs import FR_MODULUS, R1CS, fr_bytes
 
 
@@ -30,6 +30,17 @@ class PKey:
 class VKey:
     g1: np.ndarray   # one | aw | bgm | vv_io | yy_io
     g2: np.ndarray   # one2 | av | ay | gm2 | bgm2 | yt | ww_io
+
+    def resident(self):
+        """This key on the device (zk_pinocchio_vk_upload): its points decoded and checked once, then verify_many(input_outputs, proofs) per batch."""
+        g1 = np.ascontiguousarray(self.g1, dtype=np.uint8).reshape(-1)
+        g2 = np.ascontiguousarray(self.g2, dtype=np.uint8).reshape(-1)
+        n_io = len(g2) // 192 - 6
+        if n_io < 0 or len(g1) != 96 * (3 + 2 * n_io) or len(g2) != 192 * (6 + n_io):
+            raise AssertionError("Variable not found")
+        h = C.c_uint64(0)
+        _lib.check(_lib.lib().zk_pinocchio_vk_upload(_p(g1), _p(g2), C.c_size_t(n_io), C.byref(h)))
+        return ResidentVKey(h.value, n_io, lambda p: bytes(p.to_bytes()), 960, "zk_pinocchio_verify_resident")
 
 
 @dataclass
