@@ -3,6 +3,7 @@
 #include "rns_ntt.cuh"
 #include "zk_common.h"
 
+#include <string.h>
 #include <vector>
 
 namespace zk {
@@ -44,6 +45,14 @@ int frstage_scratch_alloc(const FrStage& f, FrScratch& sc);
 // Montgomery form; *sc.flag |= 1 when some gate is violated (QAP.ml:134), |= 2 when a witness
 // value is not canonical.  Everything is enqueued on `s`; nothing synchronizes.
 int frstage_eval(const FrStage& f, FrScratch& sc, const void* d_witness_canonical, hipStream_t s);
+// the flag word, copied to the host, as the status of the proof it belongs to
+static inline int status_of_flags(const void* flag_word, const char* range_text = "witness value >= r") {
+    int hf;
+    memcpy(&hf, flag_word, 4);
+    if (hf & 2) ZK_FAIL(ZK_ERR_SCALAR_RANGE, range_text);
+    if (hf & 1) ZK_FAIL(ZK_ERR_REMAINDER, "p mod Z != 0");
+    return ZK_OK;
+}
 
 // Lagrange-form variant (scope row f4): no basis conversion at all.  Leaves the VALUES a = L w, b = R w in
 // sc.abc[0..n), sc.abc[n..2n) and h(n + t), t < n - 1, in sc.h (Montgomery); flags as above.

@@ -14,17 +14,16 @@
 // The G2 product runs on a second HIP stream beside the two G1 products.
 #include "ec.cuh"
 #include "groth16_key.cuh"
+#include "handle_table.h"
 
-#include <map>
 #include <memory>
 #include <stdlib.h>
 #include <string.h>
 
 namespace zk {
 
-static std::map<uint64_t, std::unique_ptr<Groth16Key>>& g_keys = *new std::map<uint64_t, std::unique_ptr<Groth16Key>>;   // never destroyed (see ntt.hip)
-static uint64_t g_next_handle = 1;
-static void handles_release() { group_release_all(); g_keys.clear(); }
+static HandleTable<Groth16Key>& g_keys = *new HandleTable<Groth16Key>(HANDLES_GROTH16, "unknown Groth16 key handle");
+static void handles_release() { group_release_all(); g_keys.release_all(); }
 static CleanupRegistrar g_key_cleanup(handles_release);
 
 static inline dim3 g1d(uint64_t n, unsigned t = 256) { return dim3((unsigned)((n + t - 1) / t)); }
@@ -92,13 +91,9 @@ void groth16_shard_range(uint64_t points, uint64_t heavy, uint32_t rank, uint32_
 }
 
 static int key_lookup(uint64_t handle, Groth16Key** out) {
-    auto it = g_keys.find(handle);
-    if (it == g_keys.end()) {
-        if (group_lookup(handle)) ZK_FAIL(ZK_ERR_ARG, "multi-device key: this entry point serves the shards of the one-process-per-GPU path");
-        ZK_FAIL(ZK_ERR_HANDLE, "unknown Groth16 key handle");
-    }
-    *out = it->second.get();
-    return ZK_OK;
+    if ((*out = g_keys.find(handle))) return ZK_OK;
+    if (group_lookup(handle)) ZK_FAIL(ZK_ERR_ARG, "multi-device key: this entry point serves the shards of the one-process-per-GPU path");
+    ZK_FAIL(ZK_ERR_HANDLE, g_keys.unknown());
 }
 
 int groth16_slot_get(Groth16Key& k, uint32_t idx, Slot** out) {
@@ -231,8 +226,7 @@ static int upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, cons
     if (whole && ctx_count() > 1) return group_upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, lagrange, handle);
     std::unique_ptr<Groth16Key> key;
     ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, rank, world, lagrange));
-    *handle = g_next_handle++;
-    g_keys[*handle] = std::move(key);
+    *handle = g_keys.add(std::move(key));
     return ZK_OK;
 }
 // a key whose pools the library computed itself (keygen.hip: dense affine points in device memory, pool order) under a handle of its own
@@ -240,14 +234,10 @@ int groth16_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_cs
                             const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle) {
     std::unique_ptr<Groth16Key> key;
     ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, nullptr, g1_points, nullptr, g2_points, 0, 1, lagrange, false, d_g1, d_g2));
-    *handle = g_next_handle++;
-    g_keys[*handle] = std::move(key);
+    *handle = g_keys.add(std::move(key));
     return ZK_OK;
 }
-uint64_t pinocchio_live_handles();          // pinocchio.hip
-uint64_t resident_live_handles();           // msm_resident.hip: resident MSM bases count as key handles
-uint64_t vk_live_handles();                 // verify_resident.hip: so do resident verification keys
-uint64_t live_key_handles() { return g_keys.size() + group_live_handles() + pinocchio_live_handles() + resident_live_handles() + vk_live_handles(); }
+uint64_t live_key_handles() { return HandleTableBase::live_in_all_tables(); }
 
 // First half of a proof: Fr stage -> the three scalar vectors (canonical Fr, FULL pool lengths p1, p1, p2)
 // written to dA / dC / dB (device memory; the slot's own buffers in the single-call path).
@@ -401,11 +391,7 @@ int groth16_prove_finish(Slot& sl) {
     if (!sl.busy) ZK_FAIL(ZK_ERR_ARG, "no proof in flight on this slot");
     HIPCHK(hipEventSynchronize(sl.done));
     sl.busy = false;
-    int hf;
-    memcpy(&hf, sl.host + 384, 4);
-    if (hf & 2) ZK_FAIL(ZK_ERR_SCALAR_RANGE, "an Fr input (witness value, or a scalar of a caller-owned vector) is >= r");
-    if (hf & 1) ZK_FAIL(ZK_ERR_REMAINDER, "p mod Z != 0");
-    return ZK_OK;
+    return status_of_flags(sl.host + 384, "an Fr input (witness value, or a scalar of a caller-owned vector) is >= r");
 }
 
 }  // namespace zk
@@ -580,10 +566,9 @@ int single_pool_points(Groth16Key& key, int group, uint8_t* out, size_t capacity
 extern "C" {
 int zk_groth16_pk_free(uint64_t handle) {
     if (group_lookup(handle)) return group_free(handle);
-    auto it = g_keys.find(handle);
-    if (it == g_keys.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown Groth16 key handle");
+    if (!g_keys.find(handle)) ZK_FAIL(ZK_ERR_HANDLE, g_keys.unknown());
     (void)hipDeviceSynchronize();
-    g_keys.erase(it);
+    g_keys.take(handle);
     return ZK_OK;
 }
 int zk_groth16_reserve_slots(uint64_t handle, uint32_t count) {
@@ -844,8 +829,7 @@ int single_qap_eval(Groth16Key& key, const uint8_t* sol, uint8_t* v_out, uint8_t
     int hf = 0;
     HIPCHK(hipMemcpyAsync(&hf, sl->fs.flag.p, 4, hipMemcpyDeviceToHost, sl->s0));
     HIPCHK(hipStreamSynchronize(sl->s0));
-    if (hf & 2) ZK_FAIL(ZK_ERR_SCALAR_RANGE, "witness value >= r");
-    if (hf & 1) ZK_FAIL(ZK_ERR_REMAINDER, "p mod Z != 0");
+    ZKCHK(status_of_flags(&hf));
     DevBuf tmp;
     ZKCHK(tmp.alloc(32 * (size_t)k->n));
     const char* v = sl->fs.d.as<char>();

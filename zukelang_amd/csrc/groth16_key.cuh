@@ -69,7 +69,7 @@ int groth16_stage_inputs(Groth16Key& k, Slot& sl, const uint8_t* sol, const uint
 int groth16_scalars_enqueue(Groth16Key& k, Slot& sl, const uint8_t* sol, const uint8_t* r, const uint8_t* s, void* dA, void* dC, void* dB, bool staged = false);
 // the three products over this key's slice; dA / dC / dB point at the scalars OF THAT SLICE; raw: XYZZ partial sums stay in sl.results (A | C | B)
 int groth16_msms_enqueue(Groth16Key& k, Slot& sl, const void* dA, const void* dC, const void* dB, bool raw, int force_serial = -1);
-int groth16_prove_finish(Slot& sl);          // waits for sl.done, frees the slot, maps the Fr stage's flags to ZK_ERR_REMAINDER / ZK_ERR_SCALAR_RANGE
+int groth16_prove_finish(Slot& sl);          // waits for sl.done, frees the slot, maps the Fr stage's flags to ZK_ERR_REMAINDER / ZK_ERR_SCALAR_RANGE (status_of_flags)
 // replaces the key's pools by rank's slice of the complete Lagrange-form pools at d_g1 / d_g2 (device memory of the key's device) and flips its Fr stage
 int groth16_install_lagrange(Groth16Key& k, const void* d_g1, const void* d_g2, uint32_t rank, uint32_t world);
 int groth16_derive_lagrange_pools(const FrStage& f, const uint8_t* d_g1, uint64_t n_mid, const uint8_t* d_g2, uint8_t* out_g1, uint8_t* out_g2, uint32_t sets, hipStream_t s);   // lagrange_derive.hip
@@ -78,7 +78,6 @@ void groth16_shard_range(uint64_t points, uint64_t heavy, uint32_t rank, uint32_
 // ---- multi-device keys (groth16_multi.hip): one shard per entry of the device list behind ONE handle
 struct GroupKey;
 GroupKey* group_lookup(uint64_t handle);
-uint64_t group_live_handles();
 void group_release_all();
 int group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
                  const uint8_t* pk_g2, size_t pk_g2_points, bool lagrange, uint64_t* handle);

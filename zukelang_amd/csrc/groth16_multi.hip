@@ -2,23 +2,16 @@
 // shim -- `Groth16.Make(C).prove`, src/groth16/groth16.ml:235-237, is one call on one key and knows nothing of ranks).
 //
 // With a device list of N entries (zk_set_devices / zk_set_device_list), zk_groth16_pk_upload builds one SHARD of the key per entry -- the contiguous
-// slices of both base pools that zk_groth16_shard_range cuts for equal work, each with its own window tables, slots and streams on its device -- and
-// returns one handle.  A proof on slot t then runs
-//   * the Fr stage (QAP.eval, QAP.ml:120-135) ONCE, on the slot's owner device (t mod N: proofs in flight rotate over the devices, as the ranks of
-//     groth16.py's GroupProver do), which leaves the three scalar vectors over the full pools in that device's memory;
-//   * on every device: a device-to-device copy of ITS slices of the three vectors out of the owner's memory (hipMemcpyPeerAsync over xGMI; a plain
-//     device copy where two shards share a card), enqueued on the device's own slot stream behind an event of the owner's stream, then the three
-//     multi-scalar products over the slice (groth16.ml:116-161) and a 768-byte copy of the raw XYZZ partial sums to the list's first device;
-//   * on the first device: the sum of the N blocks per product (EC addition: exact, so the bytes do not depend on N or on the cuts), the affine
-//     conversion and the copy of the proof to pinned host memory.
-// Everything is enqueued by the calling thread and nothing synchronises before zk_groth16_prove_wait: the per-device streams are chained by events
-// only, so up to 15 proofs stay in flight exactly as on one GPU.  No collective library is involved -- the exchange is N - 1 peer copies per vector,
-// the pattern xGMI's point-to-point links serve directly; the one-process-per-GPU path (torch.distributed / RCCL: bench.py --gpus N) is unchanged.
+// slices of both base pools that zk_groth16_shard_range cuts for equal work -- and returns one handle.  How a proof then runs over the devices --
+// the Fr stage (QAP.eval, QAP.ml:120-135) once on the slot's owner, the three products (groth16.ml:116-161) over every device's slices, the sum of the
+// 768-byte blocks on the first device -- is device_group.cuh, shared with Pinocchio; this file holds what is Groth16's own: the upload, the two
+// callables of a proof, the pools' read-back and the derivation.  The one-process-per-GPU path (torch.distributed / RCCL: bench.py --gpus N) is unchanged.
 // The derivation of the key's Lagrange form (zk_groth16_pk_derive_lagrange) gathers the tau-power pools on up to three devices, derives one of
 // the three independent sets on each (one host thread per device), copies every set to every device and installs the shards.
+#include "device_group.cuh"
 #include "groth16_key.cuh"
+#include "handle_table.h"
 
-#include <map>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,53 +21,33 @@
 
 namespace zk {
 
-struct GroupSlot {
-    DevBuf parts, g1p, g2p, sum, out;          // on the list's first device: [device][768] landing area of the partial sums, the combine's scratch
-    uint8_t* host = nullptr;                   // pinned: the proof (384 B)
-    hipEvent_t ev_scal = nullptr;              // the owner's scalar vectors are complete
-    std::vector<hipEvent_t> ev_part;           // per device: its 768-byte block has landed on the first device
-    hipEvent_t done = nullptr;
-    bool busy = false;
-    int owner = 0;
-    ~GroupSlot() {
-        if (ev_scal) (void)hipEventDestroy(ev_scal);
-        for (hipEvent_t e : ev_part)
-            if (e) (void)hipEventDestroy(e);
-        if (done) (void)hipEventDestroy(done);
-        if (host) (void)hipHostFree(host);
-    }
+struct Groth16GroupTraits {
+    using Key = Groth16Key;
+    using Slot = zk::Slot;
+    static constexpr uint32_t MAX_SLOTS = zk::MAX_SLOTS, G1 = 2, G2 = 1, PROOF_BYTES = 384;
+    static constexpr uint32_t OFF1[G1] = {0, 288}, OFF2[G2] = {96};          // sums: A | C | B;  proof: a | b | c
+    static int slot_get(Key& k, uint32_t idx, Slot** out) { return groth16_slot_get(k, idx, out); }
+    static hipStream_t stream(Slot& sl) { return sl.s0; }
+    static void* results(Slot& sl) { return sl.results.p; }
+    static const uint8_t* flags(Slot& sl) { return sl.host + 384; }
+    static constexpr const char* BROKEN = "multi-device key is inconsistent after a failed derivation: free it";
+    static constexpr const char* SLOT_RANGE = "slot index out of range (max 15 proofs in flight)";
+    static constexpr const char* SLOT_BUSY = "slot still has a proof in flight: call the matching _wait first";
+    static constexpr const char* WAIT_NEVER_USED = "zk_groth16_prove_wait: slot never used";
+    static constexpr const char* SET_WITNESS_BUSY = "zk_groth16_set_witness: a proof is in flight on this key";
 };
-
-struct GroupKey {
+struct GroupKey : DeviceGroup<Groth16GroupTraits> {
     uint32_t n = 0, m = 0, n_mid = 0;
     uint64_t p1 = 0, p2 = 0;                   // the whole pools
-    bool lagrange = false, broken = false;
-    std::vector<std::unique_ptr<Groth16Key>> sub;      // sub[v]: the shard on virtual device v (rank v of world N)
-    std::unique_ptr<GroupSlot> slots[MAX_SLOTS];
+    bool lagrange = false;
 };
+static_assert(GroupKey::PARTIAL_BYTES == ZK_GROTH16_PARTIAL_BYTES, "partial block = A | C | B raw XYZZ");
 
-static std::map<uint64_t, std::unique_ptr<GroupKey>>& g_groups = *new std::map<uint64_t, std::unique_ptr<GroupKey>>;   // never destroyed (see ntt.hip)
-static uint64_t g_group_next = 0x6000000001ull;
+static HandleTable<GroupKey>& g_groups = *new HandleTable<GroupKey>(HANDLES_GROTH16_GROUP, "unknown Groth16 key handle");
 
-GroupKey* group_lookup(uint64_t handle) {
-    auto it = g_groups.find(handle);
-    return it == g_groups.end() ? nullptr : it->second.get();
-}
-uint64_t group_live_handles() { return g_groups.size(); }
-static void group_destroy(GroupKey& g) {
-    // slots first (events, pinned memory, buffers of the first device), then the shards, each with its own device current
-    {
-        DeviceScope ds(0);
-        for (auto& sl : g.slots) sl.reset();
-    }
-    for (size_t v = 0; v < g.sub.size(); v++) {
-        DeviceScope ds((int)v);
-        g.sub[v].reset();
-    }
-}
+GroupKey* group_lookup(uint64_t handle) { return g_groups.find(handle); }
 void group_release_all() {
-    for (auto& kv : g_groups) group_destroy(*kv.second);
-    g_groups.clear();
+    g_groups.release_all([](GroupKey& g) { g.destroy(); });
 }
 
 // runs f(v) for every virtual device of the key, one host thread each (the set-up paths synchronise their streams internally); the worst code wins
@@ -135,20 +108,6 @@ static void trace(const char* what) {
         fflush(stderr);
     }
 }
-static int sync_all(GroupKey& g) {
-    for (size_t v = 0; v < g.sub.size(); v++) {
-        DeviceScope ds((int)v);
-        HIPCHK(hipDeviceSynchronize());
-    }
-    return ZK_OK;
-}
-static int check_idle(GroupKey& g, const char* who) {
-    if (g.broken) ZK_FAIL(ZK_ERR_HIP, "multi-device key is inconsistent after a failed derivation: free it");
-    for (auto& sl : g.slots)
-        if (sl && sl->busy) ZK_FAIL(ZK_ERR_ARG, who);
-    return ZK_OK;
-}
-
 int group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
                  const uint8_t* pk_g2, size_t pk_g2_points, bool lagrange, uint64_t* handle) {
     if (!handle || !mid || !pk_g1 || !pk_g2 || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "pk_upload: null argument");
@@ -161,166 +120,49 @@ int group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const
         return groth16_key_build(g.sub[v], n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, (uint32_t)v, (uint32_t)N, lagrange, true);
     });
     if (rc != ZK_OK) {
-        group_destroy(g);
+        g.destroy();
         return rc;
     }
     g.n = n; g.m = m; g.n_mid = g.sub[0]->n_mid; g.p1 = g.sub[0]->p1; g.p2 = g.sub[0]->p2; g.lagrange = lagrange;
-    *handle = g_group_next++;
-    g_groups[*handle] = std::move(key);
+    *handle = g_groups.add(std::move(key));
     return ZK_OK;
 }
 int group_free(uint64_t handle) {
-    auto it = g_groups.find(handle);
-    if (it == g_groups.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown Groth16 key handle");
-    (void)sync_all(*it->second);
-    group_destroy(*it->second);
-    g_groups.erase(it);
+    std::unique_ptr<GroupKey> g = g_groups.take(handle);
+    if (!g) ZK_FAIL(ZK_ERR_HANDLE, g_groups.unknown());
+    (void)g->sync_all();
+    g->destroy();
     return ZK_OK;
 }
 
-static int group_slot_get(GroupKey& g, uint32_t idx, GroupSlot** out) {
-    if (idx >= MAX_SLOTS) ZK_FAIL(ZK_ERR_ARG, "slot index out of range (max 15 proofs in flight)");
-    const size_t N = g.sub.size();
-    if (!g.slots[idx]) {
-        for (size_t v = 0; v < N; v++) {          // the slot's share on every device: Fr scratch, scalar vectors, workspaces, one stream
-            DeviceScope ds((int)v);
-            Slot* sl;
-            ZKCHK(groth16_slot_get(*g.sub[v], idx, &sl));
-        }
-        DeviceScope ds(0);
-        auto gs = std::make_unique<GroupSlot>();
-        const size_t g1b = xyzz_bytes(CURVE_G1), g2b = xyzz_bytes(CURVE_G2), blk = 2 * g1b + g2b;
-        static_assert(ZK_GROTH16_PARTIAL_BYTES == 768, "partial block = A | C | B raw XYZZ");
-        ZKCHK(gs->parts.alloc(blk * N));
-        ZKCHK(gs->g1p.alloc(2 * g1b * N));
-        ZKCHK(gs->g2p.alloc(g2b * N));
-        ZKCHK(gs->sum.alloc(blk));
-        ZKCHK(gs->out.alloc(384));
-        HIPCHK(hipHostMalloc((void**)&gs->host, 384, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&gs->done, hipEventDisableTiming));
-        gs->ev_part.assign(N, nullptr);
-        // the owner records ev_scal, device v records ev_part[v]: events live on the device whose stream records them
-        gs->owner = (int)(idx % N);
-        {
-            DeviceScope dso(gs->owner);
-            HIPCHK(hipEventCreateWithFlags(&gs->ev_scal, hipEventDisableTiming));
-        }
-        for (size_t v = 0; v < N; v++) {
-            DeviceScope dsv((int)v);
-            HIPCHK(hipEventCreateWithFlags(&gs->ev_part[v], hipEventDisableTiming));
-        }
-        g.slots[idx] = std::move(gs);
-    }
-    *out = g.slots[idx].get();
-    return ZK_OK;
-}
 int group_reserve_slots(GroupKey& g, uint32_t count) {
     if (count > MAX_SLOTS) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_reserve_slots: at most 15 slots");
-    if (g.broken) ZK_FAIL(ZK_ERR_HIP, "multi-device key is inconsistent after a failed derivation: free it");
-    for (uint32_t i = 0; i < count; i++) {
-        GroupSlot* gs;
-        ZKCHK(group_slot_get(g, i, &gs));
-    }
-    return ZK_OK;
+    if (g.broken) ZK_FAIL(ZK_ERR_HIP, Groth16GroupTraits::BROKEN);
+    return g.reserve_slots(count);
 }
 int group_set_witness(GroupKey& g, const uint8_t* sol) {
     if (!sol) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_set_witness: null");
-    ZKCHK(check_idle(g, "zk_groth16_set_witness: a proof is in flight on this key"));
-    for (size_t v = 0; v < g.sub.size(); v++) {          // any device may own a proof's Fr stage
-        DeviceScope ds((int)v);
-        Groth16Key& k = *g.sub[v];
-        HIPCHK(hipMemcpyAsync(k.wit_resident.p, sol, 32 * (size_t)k.m, hipMemcpyHostToDevice, ctx().stream));
-        HIPCHK(hipStreamSynchronize(ctx().stream));
-        k.have_witness = true;
-    }
-    return ZK_OK;
+    return g.set_witness(sol);
 }
-
 int group_prove_async(GroupKey& g, const uint8_t* sol, const uint8_t* r, const uint8_t* s, uint32_t slot) {
-    if (g.broken) ZK_FAIL(ZK_ERR_HIP, "multi-device key is inconsistent after a failed derivation: free it");
-    GroupSlot* gsp;
-    ZKCHK(group_slot_get(g, slot, &gsp));
-    GroupSlot& gs = *gsp;
-    if (gs.busy) ZK_FAIL(ZK_ERR_ARG, "slot still has a proof in flight: call the matching _wait first");
-    const int N = (int)g.sub.size(), owner = gs.owner;
-    Slot* so = g.sub[owner]->slots[slot].get();
-    {   // ---- Fr stage on the owner: the three scalar vectors over the FULL pools, in the owner's slot buffers
-        DeviceScope ds(owner);
-        ZKCHK(groth16_scalars_enqueue(*g.sub[owner], *so, sol, r, s, so->scalA.p, so->scalC.p, so->scalB.p));
-        HIPCHK(hipEventRecord(gs.ev_scal, so->s0));
-    }
-    // from here on the slot is in flight whatever happens: a failed enqueue below leaves work on some streams, and _wait drains it
-    gs.busy = true;
-    int rc = ZK_OK;
-    for (int v = 0; v < N && rc == ZK_OK; v++) {
-        DeviceScope ds(v);
-        Groth16Key& k = *g.sub[v];
-        Slot& sv = *k.slots[slot];
-        auto body = [&]() -> int {
+    return g.prove_async(
+        slot,
+        [&](Groth16Key& ko, Slot& so) { return groth16_scalars_enqueue(ko, so, sol, r, s, so.scalA.p, so.scalC.p, so.scalB.p); },
+        [](int v, Groth16Key& k, Slot& sv, int owner, Slot& so) -> int {
             char *a = sv.scalA.as<char>() + 32 * k.lo1, *c = sv.scalC.as<char>() + 32 * k.lo1, *b = sv.scalB.as<char>() + 32 * k.lo2;
             if (v != owner) {
-                // this device's slices out of the owner's memory, on this device's stream, behind the owner's Fr stage.  The A vector is zero
-                // beyond a | d1 | b1 | the tau basis (groth16.ml:128-134 touches no other key point): only that part of the slice travels, the
-                // rest is cleared in place
-                HIPCHK(hipStreamWaitEvent(sv.s0, gs.ev_scal, 0));
+                // The A vector is zero beyond a | d1 | b1 | the tau basis (groth16.ml:128-134 touches no other key point): only that part of the
+                // slice travels, the rest is cleared in place
                 const uint64_t nzA = k.p2 + 1, a_hi = k.hi1 < nzA ? k.hi1 : (k.lo1 > nzA ? k.lo1 : nzA);
-                ZKCHK(copy_between(a, v, so->scalA.as<char>() + 32 * k.lo1, owner, 32 * (a_hi - k.lo1), sv.s0));
+                ZKCHK(copy_between(a, v, so.scalA.as<char>() + 32 * k.lo1, owner, 32 * (a_hi - k.lo1), sv.s0));
                 if (k.hi1 > a_hi) HIPCHK(hipMemsetAsync(a + 32 * (a_hi - k.lo1), 0, 32 * (k.hi1 - a_hi), sv.s0));
-                ZKCHK(copy_between(c, v, so->scalC.as<char>() + 32 * k.lo1, owner, 32 * (k.hi1 - k.lo1), sv.s0));
-                ZKCHK(copy_between(b, v, so->scalB.as<char>() + 32 * k.lo2, owner, 32 * (k.hi2 - k.lo2), sv.s0));
+                ZKCHK(copy_between(c, v, so.scalC.as<char>() + 32 * k.lo1, owner, 32 * (k.hi1 - k.lo1), sv.s0));
+                ZKCHK(copy_between(b, v, so.scalB.as<char>() + 32 * k.lo2, owner, 32 * (k.hi2 - k.lo2), sv.s0));
             }
-            ZKCHK(groth16_msms_enqueue(k, sv, a, c, b, true, 1));          // raw XYZZ partial sums A | C | B in sv.results, one stream
-            ZKCHK(copy_between(gs.parts.as<char>() + ZK_GROTH16_PARTIAL_BYTES * v, 0, sv.results.p, v, ZK_GROTH16_PARTIAL_BYTES, sv.s0));
-            HIPCHK(hipEventRecord(gs.ev_part[v], sv.s0));
-            return ZK_OK;
-        };
-        rc = body();
-    }
-    {   // ---- first device: add the N blocks per product, convert, land the proof in pinned memory.  On ONE stream for all slots (the context's second
-        // stream): the Fp2 column sum carries 3 KiB of private memory per lane, i.e. 1.6 GiB of scratch for every QUEUE it is dispatched on -- on the
-        // slots' own streams a handful of proofs in flight exhausted the device's scratch aperture (HSA_STATUS_ERROR_OUT_OF_RESOURCES, the runtime aborts
-        // the process).  A combine is ~50 us of work behind its N events; the slots' combines queue up in the order the proofs were enqueued.
-        DeviceScope ds(0);
-        hipStream_t cs = ctx().stream2;
-        auto body = [&]() -> int {
-            for (int v = 0; v < N; v++) HIPCHK(hipStreamWaitEvent(cs, gs.ev_part[v], 0));
-            if (rc != ZK_OK) return rc;
-            const size_t g1b = xyzz_bytes(CURVE_G1), g2b = xyzz_bytes(CURVE_G2), blk = 2 * g1b + g2b;
-            HIPCHK(hipMemcpy2DAsync(gs.g1p.p, 2 * g1b, gs.parts.p, blk, 2 * g1b, N, hipMemcpyDeviceToDevice, cs));                      // [device][A, C]
-            HIPCHK(hipMemcpy2DAsync(gs.g2p.p, g2b, gs.parts.as<char>() + 2 * g1b, blk, g2b, N, hipMemcpyDeviceToDevice, cs));        // [device][B]
-            ZKCHK(xyzz_sum_columns(CURVE_G1, gs.sum.p, gs.g1p.p, N, 2, cs));
-            ZKCHK(xyzz_sum_columns(CURVE_G2, gs.sum.as<char>() + 2 * g1b, gs.g2p.p, N, 1, cs));
-            const uint32_t o1[2] = {0, 288}, o2[1] = {96};          // sums: A | C | B;  proof: a | b | c
-            ZKCHK(proof_points_to_bytes_dev(gs.sum.p, 2, o1, gs.sum.as<char>() + 2 * g1b, 1, o2, gs.out.p, cs));
-            HIPCHK(hipMemcpyAsync(gs.host, gs.out.p, 384, hipMemcpyDeviceToHost, cs));
-            return ZK_OK;
-        };
-        const int rc0 = body();
-        if (rc == ZK_OK) rc = rc0;
-        (void)hipEventRecord(gs.done, cs);
-    }
-    if (rc != ZK_OK) {          // nothing of a half-enqueued proof may stay in flight behind the caller's back
-        (void)sync_all(g);
-        gs.busy = false;
-    }
-    return rc;
+            return groth16_msms_enqueue(k, sv, a, c, b, true, 1);          // raw XYZZ partial sums A | C | B in sv.results, one stream
+        });
 }
-int group_prove_wait(GroupKey& g, uint32_t slot, uint8_t proof[384]) {
-    if (slot >= MAX_SLOTS || !g.slots[slot]) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_prove_wait: slot never used");
-    GroupSlot& gs = *g.slots[slot];
-    if (!gs.busy) ZK_FAIL(ZK_ERR_ARG, "no proof in flight on this slot");
-    {
-        DeviceScope ds(0);
-        HIPCHK(hipEventSynchronize(gs.done));          // behind every device's block, which is behind the owner's Fr stage and its flag copy
-    }
-    gs.busy = false;
-    int hf;
-    memcpy(&hf, g.sub[gs.owner]->slots[slot]->host + 384, 4);
-    if (hf & 2) ZK_FAIL(ZK_ERR_SCALAR_RANGE, "witness value >= r");
-    if (hf & 1) ZK_FAIL(ZK_ERR_REMAINDER, "p mod Z != 0");
-    memcpy(proof, gs.host, 384);
-    return ZK_OK;
-}
+int group_prove_wait(GroupKey& g, uint32_t slot, uint8_t proof[384]) { return g.prove_wait(slot, proof); }
 
 int group_lagrange_pool_sizes(GroupKey& g, uint64_t* g1_points, uint64_t* g2_points) {
     if (g1_points) *g1_points = 3 + (uint64_t)g.n + (g.n - 1) + g.n_mid;
@@ -338,7 +180,7 @@ int group_pool_points(GroupKey& g, int group, uint8_t* out, size_t capacity_poin
     if (count) *count = total;
     if (!out) return ZK_OK;
     if (capacity_points < total) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pool_points: buffer too small");
-    ZKCHK(check_idle(g, "zk_groth16_pool_points: a proof is in flight on this key"));
+    ZKCHK(g.check_idle("zk_groth16_pool_points: a proof is in flight on this key"));
     const size_t pb = group == 1 ? 96 : 192;
     for (size_t v = 0; v < g.sub.size(); v++) {          // the shards are the pool in order
         DeviceScope ds((int)v);
@@ -349,7 +191,7 @@ int group_pool_points(GroupKey& g, int group, uint8_t* out, size_t capacity_poin
     return ZK_OK;
 }
 int group_qap_eval(GroupKey& g, const uint8_t* sol, uint8_t* v_out, uint8_t* w_out, uint8_t* h_out) {
-    ZKCHK(check_idle(g, "zk_groth16_qap_eval: a proof is in flight on this key"));
+    ZKCHK(g.check_idle("zk_groth16_qap_eval: a proof is in flight on this key"));
     DeviceScope ds(0);
     return single_qap_eval(*g.sub[0], sol, v_out, w_out, h_out);          // every shard holds the whole circuit and the Fr-stage tables
 }
@@ -359,9 +201,9 @@ int group_qap_eval(GroupKey& g, const uint8_t* sol, uint8_t* v_out, uint8_t* w_o
 // of the shards; every set then travels to every device and each device installs its shard of the Lagrange-form pools (own window tables).
 int group_derive_lagrange(GroupKey& g) {
     if (g.lagrange) return ZK_OK;
-    ZKCHK(check_idle(g, "zk_groth16_pk_derive_lagrange: a proof is in flight on this key"));
+    ZKCHK(g.check_idle("zk_groth16_pk_derive_lagrange: a proof is in flight on this key"));
     trace("derive: sync");
-    ZKCHK(sync_all(g));
+    ZKCHK(g.sync_all());
     trace("derive: synced");
     const int N = (int)g.sub.size();
     const uint64_t n = g.n, p1o = g.p1, p2o = g.p2, p1n = 3 + n + (n - 1) + g.n_mid, p2n = 2 + n;
@@ -427,10 +269,7 @@ int group_derive_lagrange(GroupKey& g) {
     trace("derive: install");
     // ---- install: each device builds the window tables of ITS slice of the new pools and flips its Fr stage.  From the first commit on the key
     // is only consistent once every device has succeeded.
-    for (auto& sl : g.slots) {          // group slots refer to the shards' slots, which the install replaces
-        DeviceScope ds(0);
-        sl.reset();
-    }
+    g.drop_slots();          // group slots refer to the shards' slots, which the install replaces
     rc = on_every_device((size_t)N, [&](int v) { return groth16_install_lagrange(*g.sub[v], full1[v].p, full2[v].p, (uint32_t)v, (uint32_t)N); });
     if (rc != ZK_OK) {
         g.broken = true;

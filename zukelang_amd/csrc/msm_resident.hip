@@ -24,10 +24,10 @@
 // the two-launch path beats the chain on the same handle for K = n products of length n.  It is a build constant (-DZK_RESIDENT_SHORT_MAX=k
 // builds a variant for the sweep: 0 = every product long), reported by zk_bases_info; it is not an option.
 #include "ec.cuh"
+#include "handle_table.h"
 #include "msm.cuh"
 #include "msm_digits.cuh"
 
-#include <map>
 #include <memory>
 #include <stdlib.h>
 #include <string.h>
@@ -193,20 +193,18 @@ struct ResidentBases {
     }
 };
 
-static std::map<uint64_t, std::unique_ptr<ResidentBases>>& g_res = *new std::map<uint64_t, std::unique_ptr<ResidentBases>>;   // never destroyed (see ntt.hip)
-static uint64_t g_res_next = 0x7000000001ull;          // its own range: never the number of a Groth16 (1, 2, ...) or Pinocchio key handle
+// its own range (handle_table.h): never the number of a key handle of either protocol, single- or multi-device, or of a verification key.
+// Resident bases count as key handles: while one lives the device list stays (zk_set_device_list).
+static HandleTable<ResidentBases>& g_res = *new HandleTable<ResidentBases>(HANDLES_RESIDENT_BASES, "unknown resident bases handle");
 static void res_release() {
-    if (g_res.empty()) return;
+    if (!g_res.size()) return;
     DeviceScope ds(0);
-    g_res.clear();
+    g_res.release_all();
 }
 static CleanupRegistrar g_res_cleanup(res_release);
-uint64_t resident_live_handles() { return g_res.size(); }
 
 static int res_lookup(uint64_t handle, ResidentBases** out) {
-    auto it = g_res.find(handle);
-    if (it == g_res.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown resident bases handle");
-    *out = it->second.get();
+    if (!(*out = g_res.find(handle))) ZK_FAIL(ZK_ERR_HANDLE, g_res.unknown());
     return ZK_OK;
 }
 
@@ -252,8 +250,7 @@ static int res_upload(int group, const uint8_t* points, size_t n, uint64_t* hand
     ZKCHK(r.arena.alloc(arena));
     HIPCHK(hipHostMalloc((void**)&r.host, arena, hipHostMallocDefault));
     HIPCHK(hipStreamSynchronize(s));
-    *handle = g_res_next++;
-    g_res[*handle] = std::move(h);
+    *handle = g_res.add(std::move(h));
     return ZK_OK;
 }
 
@@ -444,11 +441,10 @@ int zk_bases_info(uint64_t handle, int* group, uint64_t* n, uint64_t* short_max)
     return ZK_OK;
 }
 int zk_bases_free(uint64_t handle) {
-    auto it = g_res.find(handle);
-    if (it == g_res.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown resident bases handle");
+    if (!g_res.find(handle)) ZK_FAIL(ZK_ERR_HANDLE, g_res.unknown());
     DeviceScope ds(0);
     (void)hipStreamSynchronize(ctx().stream);
-    g_res.erase(it);
+    g_res.take(handle);
     return ZK_OK;
 }
 int zk_msm_resident(uint64_t handle, const uint8_t* scalars, size_t nscalars, uint8_t* out) {

@@ -26,11 +26,10 @@
 // n + 2 points.  Same group element, same bytes -- PROVIDED the key's v_all / w_all are what KeyGen.generate makes them (pinocchio.ml:104-109,
 // 140-147): that is checked at upload on the key's own points (pin_compact_check: <v_all, rho> = <si, coefficients of sum_k rho_k v_k> for a
 // pseudo-random rho, likewise w_all); a key that fails keeps the full pool and is used point by point exactly as the reference uses it.
+#include "device_group.cuh"
 #include "ec.cuh"
-#include "frstage.cuh"
-#include "msm.cuh"
+#include "handle_table.h"
 
-#include <map>
 #include <memory>
 #include <random>
 #include <string.h>
@@ -91,8 +90,7 @@ struct PinKey {
     std::unique_ptr<PinSlot> slots[PIN_MAX_SLOTS];
 };
 int derive_shifted_bases_g1(const FrStage& f, const uint8_t* d_si, uint8_t* d_out, hipStream_t s);   // lagrange_derive.hip
-static std::map<uint64_t, std::unique_ptr<PinKey>>& g_pin = *new std::map<uint64_t, std::unique_ptr<PinKey>>;   // never destroyed (see ntt.hip)
-static uint64_t g_pin_next = 0x5000000001ull;
+static HandleTable<PinKey>& g_pin = *new HandleTable<PinKey>(HANDLES_PINOCCHIO, "unknown Pinocchio key handle");
 
 static inline dim3 g1d(uint64_t n, unsigned t = 256) { return dim3((unsigned)((n + t - 1) / t)); }
 
@@ -274,9 +272,7 @@ static const uint8_t G1_GENERATOR_BYTES[96] = {
     0xfc, 0xf5, 0xe0, 0x95, 0xd5, 0xd0, 0x0a, 0xf6, 0x00, 0xdb, 0x18, 0xcb, 0x2c, 0x04, 0xb3, 0xed,
     0xd0, 0x3c, 0xc7, 0x44, 0xa2, 0x88, 0x8a, 0xe4, 0x0c, 0xaa, 0x23, 0x29, 0x46, 0xc5, 0xe7, 0xe1};
 static int pin_lookup(uint64_t handle, PinKey** out) {
-    auto it = g_pin.find(handle);
-    if (it == g_pin.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown Pinocchio key handle");
-    *out = it->second.get();
+    if (!(*out = g_pin.find(handle))) ZK_FAIL(ZK_ERR_HANDLE, g_pin.unknown());
     return ZK_OK;
 }
 static inline void pin_slice(uint64_t full, uint32_t rank, uint32_t world, uint64_t* lo, uint64_t* hi) {
@@ -495,8 +491,7 @@ int pin_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R
     if (nm) HIPCHK(hipMemcpyAsync(k.mid_idx.p, mids.data(), 4 * nm, hipMemcpyHostToDevice, c.stream));
     ZKCHK(k.wit_resident.alloc(32 * (size_t)m));
     HIPCHK(hipStreamSynchronize(c.stream));
-    *handle = g_pin_next++;
-    g_pin[*handle] = std::move(key);
+    *handle = g_pin.add(std::move(key));
     return ZK_OK;
 }
 static int pin_check_idle(PinKey& k, const char* who) {
@@ -585,8 +580,8 @@ static int pin_scalars_enqueue(PinKey& k, PinSlot& sl, const uint8_t* sol, const
     return ZK_OK;
 }
 // proof byte offsets: vv 0 | ww 96 | yy 288 | h 384 | vavv 480 | waww 576 | yayy 768 | bvwy 864
-static const uint32_t PIN_OFF1[PIN_G1] = {0, 288, 480, 768, 864, 384};
-static const uint32_t PIN_OFF2[PIN_G2] = {96, 576};
+static constexpr uint32_t PIN_OFF1[PIN_G1] = {0, 288, 480, 768, 864, 384};
+static constexpr uint32_t PIN_OFF2[PIN_G2] = {96, 576};
 // Second half: the eight products over this key's slices of the pools, scalars from sl.scal*[i] + lo.  raw: the XYZZ (partial) sums stay in sl.results --
 // six G1 then two G2 points, the identity for an empty slice -- for the first device of a multi-device key to add up; else affine bytes in sl.out_dev.
 static int pin_msms_enqueue(PinKey& k, PinSlot& sl, bool raw) {
@@ -660,74 +655,37 @@ static int pin_msms_enqueue(PinKey& k, PinSlot& sl, bool raw) {
     return ZK_OK;
 }
 
-// ================================================================== multi-device keys: N GPUs behind ONE handle (round 5; groth16_multi.hip is the model)
+// ================================================================== multi-device keys: N GPUs behind ONE handle (round 5; device_group.cuh is the shared part)
 // With a device list of N entries (zk_set_devices / zk_set_device_list) zk_pinocchio_pk_upload builds one SHARD per entry -- 1/N of the points of each
-// of the eight pools, with its own window tables, slots and streams on its device -- and returns one handle.  A proof on slot t runs the Fr stage and
-// the eight scalar vectors ONCE, on the slot's owner device (t mod N); every device copies its slices of the vectors out of the owner's memory
-// (hipMemcpyPeerAsync over xGMI; a plain device copy where two shards share a card) behind an event of the owner's stream, runs the eight products over
-// its slices (pinocchio.ml:438-505: each is a sum over key points, so it splits by points) and sends 1 920 bytes of XYZZ partial sums to the first
-// device, which adds the N blocks per product (exact group additions: the bytes do not depend on N), converts and lands the proof in pinned memory.
+// of the eight pools -- and returns one handle.  A proof runs over the devices as device_group.cuh describes: the Fr stage and the eight scalar vectors
+// once on the slot's owner, the eight products over every device's slices (pinocchio.ml:438-505: each is a sum over key points, so it splits by points),
+// 1 920 bytes of XYZZ partial sums per device to the first one.
 // The consistency check behind the compact h pool runs on the first device (it needs the whole h pool), and so does the derivation of the h bases; the
 // derived pool then travels to every device, which installs its slice.
-struct PinGroupSlot {
-    DevBuf parts, g1p, g2p, sum, out;          // on the first device: [device][1920] landing area, the combine's scratch
-    uint8_t* host = nullptr;                   // pinned: the proof (960 B)
-    hipEvent_t ev_scal = nullptr;              // the owner's scalar vectors are complete
-    std::vector<hipEvent_t> ev_part;           // per device: its block has landed on the first device
-    hipEvent_t done = nullptr;
-    bool busy = false;
-    int owner = 0;
-    ~PinGroupSlot() {
-        if (ev_scal) (void)hipEventDestroy(ev_scal);
-        for (hipEvent_t e : ev_part)
-            if (e) (void)hipEventDestroy(e);
-        if (done) (void)hipEventDestroy(done);
-        if (host) (void)hipHostFree(host);
-    }
+struct PinGroupTraits {
+    using Key = PinKey;
+    using Slot = PinSlot;
+    static constexpr uint32_t MAX_SLOTS = PIN_MAX_SLOTS, G1 = PIN_G1, G2 = PIN_G2, PROOF_BYTES = 960;
+    static constexpr const uint32_t *OFF1 = PIN_OFF1, *OFF2 = PIN_OFF2;
+    static int slot_get(Key& k, uint32_t idx, Slot** out) { return pin_slot_get(k, idx, out); }
+    static hipStream_t stream(Slot& sl) { return sl.st; }
+    static void* results(Slot& sl) { return sl.results.p; }
+    static const uint8_t* flags(Slot& sl) { return sl.host + 960; }
+    static constexpr const char* BROKEN = "multi-device Pinocchio key is inconsistent after a failed derivation: free it";
+    static constexpr const char* SLOT_RANGE = "pinocchio: slot index out of range (max 15 proofs in flight)";
+    static constexpr const char* SLOT_BUSY = "slot still has a proof in flight: call zk_pinocchio_prove_wait first";
+    static constexpr const char* WAIT_NEVER_USED = "zk_pinocchio_prove_wait: slot never used";
+    static constexpr const char* SET_WITNESS_BUSY = "zk_pinocchio_set_witness: a proof is in flight on this key";
 };
-struct PinGroup {
+struct PinGroup : DeviceGroup<PinGroupTraits> {
     uint32_t n = 0, m = 0;
-    bool broken = false;
-    std::vector<std::unique_ptr<PinKey>> sub;
-    std::unique_ptr<PinGroupSlot> slots[PIN_MAX_SLOTS];
 };
-static constexpr size_t PIN_PARTIAL_BYTES = PIN_G1 * 192 + PIN_G2 * 384;
-static std::map<uint64_t, std::unique_ptr<PinGroup>>& g_pin_groups = *new std::map<uint64_t, std::unique_ptr<PinGroup>>;
-static uint64_t g_pin_group_next = 0x7000000001ull;
-static PinGroup* pin_group_lookup(uint64_t handle) {
-    auto it = g_pin_groups.find(handle);
-    return it == g_pin_groups.end() ? nullptr : it->second.get();
-}
-static void pin_group_destroy(PinGroup& g) {
-    {
-        DeviceScope ds(0);
-        for (auto& sl : g.slots) sl.reset();
-    }
-    for (size_t v = 0; v < g.sub.size(); v++) {
-        DeviceScope ds((int)v);
-        g.sub[v].reset();
-    }
-}
+static HandleTable<PinGroup>& g_pin_groups = *new HandleTable<PinGroup>(HANDLES_PINOCCHIO_GROUP, "unknown Pinocchio key handle");
 static void pin_release() {
-    g_pin.clear();
-    for (auto& kv : g_pin_groups) pin_group_destroy(*kv.second);
-    g_pin_groups.clear();
+    g_pin.release_all();
+    g_pin_groups.release_all([](PinGroup& g) { g.destroy(); });
 }
-uint64_t pinocchio_live_handles() { return g_pin.size() + g_pin_groups.size(); }
 static CleanupRegistrar g_pin_cleanup(pin_release);
-static int pin_group_sync(PinGroup& g) {
-    for (size_t v = 0; v < g.sub.size(); v++) {
-        DeviceScope ds((int)v);
-        HIPCHK(hipDeviceSynchronize());
-    }
-    return ZK_OK;
-}
-static int pin_group_check_idle(PinGroup& g, const char* who) {
-    if (g.broken) ZK_FAIL(ZK_ERR_HIP, "multi-device Pinocchio key is inconsistent after a failed derivation: free it");
-    for (auto& sl : g.slots)
-        if (sl && sl->busy) ZK_FAIL(ZK_ERR_ARG, who);
-    return ZK_OK;
-}
 static int pin_group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
                             const uint8_t* pk_g2, size_t pk_g2_points, uint64_t* handle) {
     const int N = ctx_count();
@@ -748,128 +706,32 @@ static int pin_group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_cs
         if (rc == ZK_OK && v == 0) compact = g.sub[0]->compact ? 1 : 0;
     }
     if (rc != ZK_OK) {
-        pin_group_destroy(g);
+        g.destroy();
         return rc;
     }
-    *handle = g_pin_group_next++;
-    g_pin_groups[*handle] = std::move(grp);
-    return ZK_OK;
-}
-static int pin_group_slot_get(PinGroup& g, uint32_t idx, PinGroupSlot** out) {
-    if (idx >= PIN_MAX_SLOTS) ZK_FAIL(ZK_ERR_ARG, "pinocchio: slot index out of range (max 15 proofs in flight)");
-    const size_t N = g.sub.size();
-    if (!g.slots[idx]) {
-        for (size_t v = 0; v < N; v++) {
-            DeviceScope ds((int)v);
-            PinSlot* sl;
-            ZKCHK(pin_slot_get(*g.sub[v], idx, &sl));
-        }
-        DeviceScope ds(0);
-        auto gs = std::make_unique<PinGroupSlot>();
-        ZKCHK(gs->parts.alloc(PIN_PARTIAL_BYTES * N));
-        ZKCHK(gs->g1p.alloc(PIN_G1 * 192 * N));
-        ZKCHK(gs->g2p.alloc(PIN_G2 * 384 * N));
-        ZKCHK(gs->sum.alloc(PIN_PARTIAL_BYTES));
-        ZKCHK(gs->out.alloc(960));
-        HIPCHK(hipHostMalloc((void**)&gs->host, 960, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&gs->done, hipEventDisableTiming));
-        gs->ev_part.assign(N, nullptr);
-        gs->owner = (int)(idx % N);
-        {
-            DeviceScope dso(gs->owner);
-            HIPCHK(hipEventCreateWithFlags(&gs->ev_scal, hipEventDisableTiming));
-        }
-        for (size_t v = 0; v < N; v++) {
-            DeviceScope dsv((int)v);
-            HIPCHK(hipEventCreateWithFlags(&gs->ev_part[v], hipEventDisableTiming));
-        }
-        g.slots[idx] = std::move(gs);
-    }
-    *out = g.slots[idx].get();
+    *handle = g_pin_groups.add(std::move(grp));
     return ZK_OK;
 }
 static int pin_group_prove_async(PinGroup& g, const uint8_t* sol, const uint8_t dv[32], const uint8_t dw[32], const uint8_t dy[32], uint32_t slot) {
-    if (g.broken) ZK_FAIL(ZK_ERR_HIP, "multi-device Pinocchio key is inconsistent after a failed derivation: free it");
-    PinGroupSlot* gsp;
-    ZKCHK(pin_group_slot_get(g, slot, &gsp));
-    PinGroupSlot& gs = *gsp;
-    if (gs.busy) ZK_FAIL(ZK_ERR_ARG, "slot still has a proof in flight: call zk_pinocchio_prove_wait first");
-    const int N = (int)g.sub.size(), owner = gs.owner;
-    PinSlot* so = g.sub[owner]->slots[slot].get();
-    {   // ---- the Fr stage and the eight scalar vectors over the FULL pools, on the owner
-        DeviceScope ds(owner);
-        ZKCHK(pin_scalars_enqueue(*g.sub[owner], *so, sol, dv, dw, dy, true));
-        HIPCHK(hipEventRecord(gs.ev_scal, so->st));
-    }
-    gs.busy = true;          // from here on the slot is in flight whatever happens: _wait (or the failure path below) drains it
-    int rc = ZK_OK;
-    for (int v = 0; v < N && rc == ZK_OK; v++) {
-        DeviceScope ds(v);
-        PinKey& k = *g.sub[v];
-        PinSlot& sv = *k.slots[slot];
-        auto body = [&]() -> int {
+    return g.prove_async(
+        slot, [&](PinKey& ko, PinSlot& so) { return pin_scalars_enqueue(ko, so, sol, dv, dw, dy, true); },
+        [](int v, PinKey& k, PinSlot& sv, int owner, PinSlot& so) -> int {
             if (v != owner) {
-                HIPCHK(hipStreamWaitEvent(sv.st, gs.ev_scal, 0));
                 // this device's slices of the vectors it sorts itself (a pool that reads another pool's sort on THIS shard needs none)
                 for (int i = 0; i < PIN_G1; i++)
                     if (k.g1[i].n && k.share1[i] < 0)
-                        ZKCHK(copy_between(sv.scal1[i].as<char>() + 32 * k.lo1[i], v, so->scal1[i].as<char>() + 32 * k.lo1[i], owner, 32 * (k.hi1[i] - k.lo1[i]), sv.st));
+                        ZKCHK(copy_between(sv.scal1[i].as<char>() + 32 * k.lo1[i], v, so.scal1[i].as<char>() + 32 * k.lo1[i], owner, 32 * (k.hi1[i] - k.lo1[i]), sv.st));
                 for (int i = 0; i < PIN_G2; i++)
                     if (k.g2[i].n && k.share2[i] < 0)
-                        ZKCHK(copy_between(sv.scal2[i].as<char>() + 32 * k.lo2[i], v, so->scal2[i].as<char>() + 32 * k.lo2[i], owner, 32 * (k.hi2[i] - k.lo2[i]), sv.st));
+                        ZKCHK(copy_between(sv.scal2[i].as<char>() + 32 * k.lo2[i], v, so.scal2[i].as<char>() + 32 * k.lo2[i], owner, 32 * (k.hi2[i] - k.lo2[i]), sv.st));
             }
-            ZKCHK(pin_msms_enqueue(k, sv, true));
-            ZKCHK(copy_between(gs.parts.as<char>() + PIN_PARTIAL_BYTES * v, 0, sv.results.p, v, PIN_PARTIAL_BYTES, sv.st));
-            HIPCHK(hipEventRecord(gs.ev_part[v], sv.st));
-            return ZK_OK;
-        };
-        rc = body();
-    }
-    {   // ---- first device: add the N blocks per product, convert, land the proof (one stream for all slots: groth16_multi.hip says why)
-        DeviceScope ds(0);
-        hipStream_t cs = ctx().stream2;
-        auto body = [&]() -> int {
-            for (int v = 0; v < N; v++) HIPCHK(hipStreamWaitEvent(cs, gs.ev_part[v], 0));
-            if (rc != ZK_OK) return rc;
-            const size_t b1 = PIN_G1 * 192, b2 = PIN_G2 * 384;
-            HIPCHK(hipMemcpy2DAsync(gs.g1p.p, b1, gs.parts.p, PIN_PARTIAL_BYTES, b1, N, hipMemcpyDeviceToDevice, cs));                      // [device][six G1 sums]
-            HIPCHK(hipMemcpy2DAsync(gs.g2p.p, b2, gs.parts.as<char>() + b1, PIN_PARTIAL_BYTES, b2, N, hipMemcpyDeviceToDevice, cs));        // [device][two G2 sums]
-            ZKCHK(xyzz_sum_columns(CURVE_G1, gs.sum.p, gs.g1p.p, N, PIN_G1, cs));
-            ZKCHK(xyzz_sum_columns(CURVE_G2, gs.sum.as<char>() + b1, gs.g2p.p, N, PIN_G2, cs));
-            ZKCHK(proof_points_to_bytes_dev(gs.sum.p, PIN_G1, PIN_OFF1, gs.sum.as<char>() + b1, PIN_G2, PIN_OFF2, gs.out.p, cs));
-            HIPCHK(hipMemcpyAsync(gs.host, gs.out.p, 960, hipMemcpyDeviceToHost, cs));
-            return ZK_OK;
-        };
-        const int rc0 = body();
-        if (rc == ZK_OK) rc = rc0;
-        (void)hipEventRecord(gs.done, cs);
-    }
-    if (rc != ZK_OK) {
-        (void)pin_group_sync(g);
-        gs.busy = false;
-    }
-    return rc;
-}
-static int pin_group_prove_wait(PinGroup& g, uint32_t slot, uint8_t proof[960]) {
-    if (slot >= PIN_MAX_SLOTS || !g.slots[slot]) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_prove_wait: slot never used");
-    PinGroupSlot& gs = *g.slots[slot];
-    if (!gs.busy) ZK_FAIL(ZK_ERR_ARG, "no proof in flight on this slot");
-    {
-        DeviceScope ds(0);
-        HIPCHK(hipEventSynchronize(gs.done));          // behind every device's block, which is behind the owner's Fr stage and its flag copy
-    }
-    gs.busy = false;
-    int hf;
-    memcpy(&hf, g.sub[gs.owner]->slots[slot]->host + 960, 4);
-    if (hf & 2) ZK_FAIL(ZK_ERR_SCALAR_RANGE, "witness value >= r");
-    if (hf & 1) ZK_FAIL(ZK_ERR_REMAINDER, "p mod Z != 0");
-    memcpy(proof, gs.host, 960);
-    return ZK_OK;
+            return pin_msms_enqueue(k, sv, true);
+        });
 }
 static int pin_group_derive(PinGroup& g) {
     if (g.sub[0]->lagrange) return ZK_OK;
-    ZKCHK(pin_group_check_idle(g, "zk_pinocchio_pk_derive_lagrange: a proof is in flight on this key"));
-    ZKCHK(pin_group_sync(g));
+    ZKCHK(g.check_idle("zk_pinocchio_pk_derive_lagrange: a proof is in flight on this key"));
+    ZKCHK(g.sync_all());
     const int N = (int)g.sub.size();
     PinKey& k0 = *g.sub[0];
     const uint64_t ph_old = k0.full1[5], ph = pin_h_points(k0.n, k0.m, true, k0.compact);
@@ -903,10 +765,7 @@ static int pin_group_derive(PinGroup& g) {
         HIPCHK(hipStreamSynchronize(ctx().stream));
     }
     // ---- install: from the first commit on the key is only consistent once every device has succeeded
-    {
-        DeviceScope ds(0);
-        for (auto& sl : g.slots) sl.reset();          // group slots refer to the shards' slots, which the install replaces
-    }
+    g.drop_slots();          // group slots refer to the shards' slots, which the install replaces
     for (int v = 0; v < N; v++) {
         DeviceScope ds(v);
         const int rc = pin_install_derived(*g.sub[v], pool[v].as<uint8_t>(), ctx().stream);
@@ -930,8 +789,7 @@ int zk_pinocchio_pk_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr
     if (ctx_count() > 1) return pin_group_upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, handle);
     std::unique_ptr<PinKey> key;
     ZKCHK(pin_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, -1));
-    *handle = g_pin_next++;
-    g_pin[*handle] = std::move(key);
+    *handle = g_pin.add(std::move(key));
     return ZK_OK;
 }
 // zk_pinocchio_pk_upload plus the derived h bases handed in by the caller: the ordinary upload (every check, the compact check included), then
@@ -957,15 +815,14 @@ int zk_pinocchio_pk_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, con
     if (k.compact) ZKCHK(msm_bases_dense(k.g1[5], n - 1, 1, p + 96 * ((uint64_t)n + 1), c.stream));                         // [s^(n-1)]
     else ZKCHK(msm_bases_dense(k.g1[5], (uint64_t)n + 1, 2 * (uint64_t)m, p + 96 * ((uint64_t)n + 1), c.stream));           // v_all | w_all
     ZKCHK(pin_install_derived(k, p, c.stream));
-    *handle = g_pin_next++;
-    g_pin[*handle] = std::move(key);
+    *handle = g_pin.add(std::move(key));
     return ZK_OK;
 }
 // The h pool of an uploaded key (si | v_all | w_all, or si alone: compact) rewritten for the VALUES of h: [lambda_t(s)]_1 derived from the powers si in the
 // exponent (lagrange_derive.hip: the transposed interpolation over the points n .. 2n-2), [Z(s)]_1 = <si, Z> once, [1] = si[0], and for the compact form
 // [s^(n-1)] = si[n-1].  Same proofs; the per-proof basis conversion disappears (only h ever needed coefficients: v(s), w(s) come from the per-variable pools).
 int zk_pinocchio_pk_derive_lagrange(uint64_t handle) {
-    if (PinGroup* g = pin_group_lookup(handle)) return pin_group_derive(*g);
+    if (PinGroup* g = g_pin_groups.find(handle)) return pin_group_derive(*g);
     PinKey* kp;
     ZKCHK(pin_lookup(handle, &kp));
     PinKey& k = *kp;
@@ -983,13 +840,13 @@ int zk_pinocchio_pk_derive_lagrange(uint64_t handle) {
 }
 int zk_pinocchio_pool_points(uint64_t handle, int pool, uint8_t* out, size_t capacity_points, size_t* count) {
     if (pool < 0 || pool >= PIN_G1 + PIN_G2) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_pool_points: pool 0..5 (G1) or 6..7 (G2)");
-    if (PinGroup* g = pin_group_lookup(handle)) {          // the handle holds the whole pools (its devices' slices are an internal matter)
+    if (PinGroup* g = g_pin_groups.find(handle)) {          // the handle holds the whole pools (its devices' slices are an internal matter)
         PinKey& k0 = *g->sub[0];
         const uint64_t total = pool < PIN_G1 ? k0.full1[pool] : k0.full2[pool - PIN_G1];
         if (count) *count = total;
         if (!out) return ZK_OK;
         if (capacity_points < total) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_pool_points: buffer too small");
-        ZKCHK(pin_group_check_idle(*g, "zk_pinocchio_pool_points: a proof is in flight on this key"));
+        ZKCHK(g->check_idle("zk_pinocchio_pool_points: a proof is in flight on this key"));
         const size_t pb = pool < PIN_G1 ? 96 : 192;
         for (size_t v = 0; v < g->sub.size(); v++) {
             DeviceScope ds((int)v);
@@ -1007,28 +864,19 @@ int zk_pinocchio_pool_points(uint64_t handle, int pool, uint8_t* out, size_t cap
     return pin_slice_points(*kp, pool, out);
 }
 int zk_pinocchio_pk_free(uint64_t handle) {
-    auto ig = g_pin_groups.find(handle);
-    if (ig != g_pin_groups.end()) {
-        (void)pin_group_sync(*ig->second);
-        pin_group_destroy(*ig->second);
-        g_pin_groups.erase(ig);
+    if (std::unique_ptr<PinGroup> g = g_pin_groups.take(handle)) {
+        (void)g->sync_all();
+        g->destroy();
         return ZK_OK;
     }
-    auto it = g_pin.find(handle);
-    if (it == g_pin.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown Pinocchio key handle");
+    if (!g_pin.find(handle)) ZK_FAIL(ZK_ERR_HANDLE, g_pin.unknown());
     (void)hipDeviceSynchronize();
-    g_pin.erase(it);
+    g_pin.take(handle);
     return ZK_OK;
 }
 int zk_pinocchio_reserve_slots(uint64_t handle, uint32_t count) {
     if (count > PIN_MAX_SLOTS) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_reserve_slots: at most 15 slots");
-    if (PinGroup* g = pin_group_lookup(handle)) {
-        for (uint32_t i = 0; i < count; i++) {
-            PinGroupSlot* gs;
-            ZKCHK(pin_group_slot_get(*g, i, &gs));
-        }
-        return ZK_OK;
-    }
+    if (PinGroup* g = g_pin_groups.find(handle)) return g->reserve_slots(count);
     PinKey* kp;
     ZKCHK(pin_lookup(handle, &kp));
     for (uint32_t i = 0; i < count; i++) {
@@ -1039,17 +887,7 @@ int zk_pinocchio_reserve_slots(uint64_t handle, uint32_t count) {
 }
 int zk_pinocchio_set_witness(uint64_t handle, const uint8_t* sol) {
     if (!sol) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_set_witness: null");
-    if (PinGroup* g = pin_group_lookup(handle)) {
-        ZKCHK(pin_group_check_idle(*g, "zk_pinocchio_set_witness: a proof is in flight on this key"));
-        for (size_t v = 0; v < g->sub.size(); v++) {          // any device may own a proof's Fr stage
-            DeviceScope ds((int)v);
-            PinKey& k = *g->sub[v];
-            HIPCHK(hipMemcpyAsync(k.wit_resident.p, sol, 32 * (size_t)k.m, hipMemcpyHostToDevice, ctx().stream));
-            HIPCHK(hipStreamSynchronize(ctx().stream));
-            k.have_witness = true;
-        }
-        return ZK_OK;
-    }
+    if (PinGroup* g = g_pin_groups.find(handle)) return g->set_witness(sol);
     PinKey* kp;
     ZKCHK(pin_lookup(handle, &kp));
     Ctx& c = ctx();
@@ -1063,7 +901,7 @@ int zk_pinocchio_set_witness(uint64_t handle, const uint8_t* sol) {
 // Fr stage -> the eight scalar vectors -> eight MSMs -> affine bytes -> pinned host buffer.
 int zk_pinocchio_prove_async(uint64_t handle, const uint8_t* sol, const uint8_t dv[32], const uint8_t dw[32], const uint8_t dy[32], uint32_t slot) {
     if (!dv || !dw || !dy) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_prove_async: null argument");
-    if (PinGroup* g = pin_group_lookup(handle)) return pin_group_prove_async(*g, sol, dv, dw, dy, slot);
+    if (PinGroup* g = g_pin_groups.find(handle)) return pin_group_prove_async(*g, sol, dv, dw, dy, slot);
     PinKey* kp;
     ZKCHK(pin_lookup(handle, &kp));
     PinKey& k = *kp;
@@ -1080,7 +918,7 @@ int zk_pinocchio_prove_async(uint64_t handle, const uint8_t* sol, const uint8_t 
 }
 int zk_pinocchio_prove_wait(uint64_t handle, uint32_t slot, uint8_t proof[960]) {
     if (!proof) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_prove_wait: null proof");
-    if (PinGroup* g = pin_group_lookup(handle)) return pin_group_prove_wait(*g, slot, proof);
+    if (PinGroup* g = g_pin_groups.find(handle)) return g->prove_wait(slot, proof);
     PinKey* kp;
     ZKCHK(pin_lookup(handle, &kp));
     if (slot >= PIN_MAX_SLOTS || !kp->slots[slot]) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_prove_wait: slot never used");
@@ -1088,10 +926,7 @@ int zk_pinocchio_prove_wait(uint64_t handle, uint32_t slot, uint8_t proof[960]) 
     if (!sl.busy) ZK_FAIL(ZK_ERR_ARG, "no proof in flight on this slot");
     HIPCHK(hipEventSynchronize(sl.done));
     sl.busy = false;
-    int hf;
-    memcpy(&hf, sl.host + 960, 4);
-    if (hf & 2) ZK_FAIL(ZK_ERR_SCALAR_RANGE, "witness value >= r");
-    if (hf & 1) ZK_FAIL(ZK_ERR_REMAINDER, "p mod Z != 0");
+    ZKCHK(status_of_flags(sl.host + 960));
     memcpy(proof, sl.host, 960);
     return ZK_OK;
 }

@@ -19,9 +19,9 @@
 // The verdicts are those of zk_*_verify_many byte for byte: the same decoder, the same order of checks, the same pairs into the same two kernels, and
 // a subgroup verdict that is the same predicate (tests/test_subgroup_criterion.py, tests/test_gpu_subgroup_endo.py).  Nothing here reads an option.
 #include "ec.cuh"
+#include "handle_table.h"
 #include "msm.cuh"
 
-#include <map>
 #include <memory>
 #include <string.h>
 
@@ -197,21 +197,18 @@ struct ResidentVk {
 };
 static const VkPlan& plan_of(const ResidentVk& k) { return k.protocol == 0 ? PLAN_GROTH16 : PLAN_PINOCCHIO; }
 
-static std::map<uint64_t, std::unique_ptr<ResidentVk>>& g_vk = *new std::map<uint64_t, std::unique_ptr<ResidentVk>>;   // never destroyed (see ntt.hip)
-static uint64_t g_vk_next = 0x7100000001ull;          // a range of its own, next to the resident bases'
+// a range of its own (handle_table.h); like resident bases, a live verification key pins the device list
+static HandleTable<ResidentVk>& g_vk = *new HandleTable<ResidentVk>(HANDLES_VERIFICATION_KEY, "unknown verification key handle");
 static void vk_release() {
-    if (g_vk.empty()) return;
+    if (!g_vk.size()) return;
     DeviceScope ds(0);
-    g_vk.clear();
+    g_vk.release_all();
 }
 static CleanupRegistrar g_vk_cleanup(vk_release);
-uint64_t vk_live_handles() { return g_vk.size(); }
 
 static int vk_lookup(uint64_t handle, int protocol, ResidentVk** out) {
-    auto it = g_vk.find(handle);
-    if (it == g_vk.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown verification key handle");
-    if (protocol >= 0 && it->second->protocol != protocol) ZK_FAIL(ZK_ERR_HANDLE, "the verification key handle belongs to the other protocol");
-    *out = it->second.get();
+    if (!(*out = g_vk.find(handle))) ZK_FAIL(ZK_ERR_HANDLE, g_vk.unknown());
+    if (protocol >= 0 && (*out)->protocol != protocol) ZK_FAIL(ZK_ERR_HANDLE, "the verification key handle belongs to the other protocol");
     return ZK_OK;
 }
 static int verdict_code(uint8_t v) { return v == 0 ? ZK_OK : v == 2 ? ZK_ERR_ARG : v == VK_CODE_SCALAR ? ZK_ERR_SCALAR_RANGE : ZK_ERR_NOT_ON_CURVE; }
@@ -242,8 +239,7 @@ static int vk_install(std::unique_ptr<ResidentVk>& k, const uint8_t want[576], h
     ZKCHK(k->want.alloc(576));
     HIPCHK(hipMemcpyAsync(k->want.p, want, 576, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));          // the tables are built, the caller's bytes are read
-    *handle = g_vk_next++;
-    g_vk[*handle] = std::move(k);
+    *handle = g_vk.add(std::move(k));
     return ZK_OK;
 }
 
@@ -409,11 +405,10 @@ int zk_vk_info(uint64_t handle, int* protocol, uint64_t* n_io) {
 }
 
 int zk_vk_free(uint64_t handle) {
-    auto it = g_vk.find(handle);
-    if (it == g_vk.end()) ZK_FAIL(ZK_ERR_HANDLE, "unknown verification key handle");
+    if (!g_vk.find(handle)) ZK_FAIL(ZK_ERR_HANDLE, g_vk.unknown());
     DeviceScope ds(0);
     (void)hipStreamSynchronize(ctx().stream);
-    g_vk.erase(it);
+    g_vk.take(handle);
     return ZK_OK;
 }
 

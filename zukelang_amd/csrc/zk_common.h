@@ -51,7 +51,7 @@ struct DeviceScope {
     DeviceScope& operator=(const DeviceScope&) = delete;
 };
 int ensure_init();
-uint64_t live_key_handles();             // Groth16 + Pinocchio key handles alive (groth16.hip / pinocchio.hip): the device list may only change at 0
+uint64_t live_key_handles();             // handles of every kind alive (handle_table.h: the sum over all tables): the device list may only change at 0
 std::vector<void (*)()>& cleanup_hooks();   // run by zk_shutdown once per context (that context current), before its streams die
 struct CleanupRegistrar { explicit CleanupRegistrar(void (*f)()) { cleanup_hooks().push_back(f); } };
 // device -> device copy between two virtual devices on `s` -- a stream of the CALLING thread's current device, which may be the source's or the
