@@ -10,4 +10,4 @@ for o in ${@:-*.o}; do
     /\.agpr_count:/ {agpr=$2} /\.group_segment_fixed_size:/ {lds=$2} /\.name:/ {name=$2} /\.private_segment_fixed_size:/ {scr=$2}
     /\.sgpr_count:/ {sgpr=$2} /\.vgpr_count:/ {vgpr=$2} /\.vgpr_spill_count:/ {spill=$2; printf "%-14s vgpr %3d agpr %3d sgpr %3d spill %3d scratch %5d lds %6d  %s\n", obj, vgpr, agpr, sgpr, spill, scr, lds, name}'
   rm -f /tmp/kr_$$.co /tmp/kr_$$.fb
-done | c++filt | sed 's/zk:://g; s/(.*//'
+done | c++filt | sed 's/zk:://g; s/([^()]*)$//'

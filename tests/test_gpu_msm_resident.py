@@ -193,6 +193,55 @@ def test_resident_upload_checks_and_the_subgroup_option():
             assert got == bytes(G1.apply_powers(c, bases[:max(k, 1) * 96] if k else bases)), k
 
 
+_FROM_BYTES = {G1: P.g1_from_bytes, G2: P.g2_from_bytes}
+_TO_BYTES = {G1: P.g1_to_bytes, G2: P.g2_to_bytes}
+
+
+@pytest.mark.parametrize("n", [2, 129])
+@pytest.mark.parametrize("G", [G1, G2])
+def test_zero_bytes_without_the_infinity_bit_are_the_identity_on_the_base_path(G, n):
+    """96 / 192 zero bytes, the infinity bit NOT set, as the last base of a list: the decoder of key lists and MSM bases takes the string for the identity
+    (it is how the library's own affine format spells it), where the verifiers' decoder calls it a point off the curve (tests/test_gpu_pairing.py,
+    tests/test_gpu_subgroup_endo.py).  129 = one lane past a full 128-lane block of the decoder.  A product with a non-zero scalar on EVERY base is the
+    product without that base, in oracle/pyref.py's integers (small scalars keep the Python fold short)."""
+    pts = np.array(G.of_Fr(RC.random_fr_bytes(n, 60 + n)), dtype=np.uint8).reshape(n, G.POINT_BYTES)
+    pts[n - 1] = 0
+    scalars = [3 + 5 * i for i in range(n)]
+    sc = np.frombuffer(b"".join(frb(s) for s in scalars), dtype=np.uint8)
+    want = _TO_BYTES[G](P.msm([_FROM_BYTES[G](bytes(p)) for p in pts[:n - 1]], scalars[:n - 1]))
+    with G.resident(pts.reshape(-1)) as rb:          # zk_bases_upload succeeds
+        assert rb.n == n
+        assert bytes(rb.apply_powers(sc)) == want
+
+
+def _torsion_point(G):
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "torsion_points.json")) as f:
+        recs = json.load(f)["points"]
+    return next(bytes.fromhex(r["hex"]) for r in recs if r["group"] == (0 if G is G1 else 1) and r["verdict"] == 4)
+
+
+@pytest.mark.parametrize("G", [G1, G2])
+def test_bases_upload_reports_by_kind_priority_not_by_position(G):
+    """zk_bases_upload reads one flag word per list: a bad encoding beats a point off the curve, and that beats a point outside the subgroup, wherever
+    they sit (zk_g1/g2_decompress_batch reports the FIRST bad element instead: tests/test_gpu_decompress.py)."""
+    B = G.POINT_BYTES
+    good = np.array(G.of_Fr(RC.random_fr_bytes(3, 77)), dtype=np.uint8).reshape(3, B)
+    off_curve = np.array(good[0], copy=True)
+    off_curve[B - 1] ^= 1
+    bad_encoding = np.array(good[2], copy=True)
+    bad_encoding[0] |= 0x80                                            # the compression bit on an uncompressed point
+    outside = np.frombuffer(_torsion_point(G), dtype=np.uint8)
+    assert P.on_curve(_FROM_BYTES[G](bytes(outside)), P.B1 if G is G1 else P.B2) and not P._in_subgroup(_FROM_BYTES[G](bytes(outside)))
+    with pytest.raises(_lib.ZkError) as e:
+        G.resident(np.concatenate([off_curve, good[1], bad_encoding]))
+    assert e.value.code == -1 and "encoding" in str(e.value), str(e.value)
+    with pytest.raises(_lib.ZkError) as e:
+        G.resident(np.concatenate([outside, good[1], off_curve]))
+    assert e.value.code == -2 and "not on the curve" in str(e.value) and "subgroup" not in str(e.value), str(e.value)
+
+
 def test_interleaved_handles_and_many_random_prefixes():
     sm = _short_max(G1)
     b1, b2, b3 = _bases(G1, 300, 41), _bases(G2, 50, 42), _bases(G1, sm + 8, 43)

@@ -1,4 +1,4 @@
-"""k_subgroup_verdict_endo (csrc/msm_points.hip) through zk_selftest_subgroup: the subgroup verdict by endomorphism (method 1) against [r] P = O on the
+"""k_subgroup_verdict (csrc/msm_points.hip) through zk_selftest_subgroup: the subgroup verdict by endomorphism (method 1) against [r] P = O on the
 device (method 0) and against the verdicts tests/golden/torsion_points.json records from Python integers -- points of every prime-power order the
 cofactors allow, where the short chains meet P + P, P - P and an identity accumulator (orders 3, 11, 13, 23), those points added to subgroup points,
 random curve points, subgroup points and the identity."""

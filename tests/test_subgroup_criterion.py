@@ -1,4 +1,4 @@
-"""The two subgroup criteria of k_subgroup_verdict_endo (zukelang_amd/csrc/msm_points.hip) restated in Python integers, with the constants the kernel
+"""The two subgroup criteria of in_subgroup_endo (zukelang_amd/csrc/msm_points.hip) restated in Python integers, with the constants the kernel
 reads (endo_consts.cuh, decoded from their Montgomery limbs), and held to [r] P = O (pyref._in_subgroup):
 
   G1:  P in G1  <=>  [z^2] P == (beta^2 x, -y)            G2:  Q in G2  <=>  [|z|] Q == (cx conj x, cy' conj y),  (cx, cy') = -psi as stored

@@ -125,13 +125,19 @@ int points_xyzz_to_bytes(Curve curve, const void* d_xyzz, uint64_t count, uint8_
 int points_xyzz_to_bytes_dev(Curve curve, const void* d_xyzz, uint64_t count, void* d_bytes, hipStream_t s);
 // the points of a proof (n1 <= 8 dense XYZZ in G1, n2 <= 4 in G2) -> uncompressed bytes at d_out + off[i], in one launch
 int proof_points_to_bytes_dev(const void* d_g1, uint32_t n1, const uint32_t* off1, const void* d_g2, uint32_t n2, const uint32_t* off2, void* d_out, hipStream_t s);
-// bytes (device copy of host encoding) -> affine Montgomery; *d_flag |= 1 not on curve, |= 2 bad encoding
+// bytes (device copy of host encoding) -> affine Montgomery; *d_flag |= 1 not on curve, |= 2 bad encoding.  The decoder of key lists and MSM bases: zero
+// bytes without the infinity bit are the identity here (msm_points.hip: point_decode)
 int points_bytes_to_affine(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, int* d_flag, hipStream_t s);
 int points_affine_to_bytes(Curve curve, void* d_bytes, const void* d_affine, uint64_t n, hipStream_t s);
-// decode + curve check (+ [r] P = O) with one verdict byte per point: 0 good | 2 encoding | 1 curve | 4 subgroup; rejected points become the identity
-int points_decode_verdicts(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, uint8_t* d_verdict, bool check_subgroup, hipStream_t s);
-// the same, the subgroup verdict by the curve's endomorphism (msm_points.hip: k_subgroup_verdict_endo): 2 x 63 doublings in G1, 63 in G2 instead of 254
-int points_decode_verdicts_endo(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, uint8_t* d_verdict, hipStream_t s);
+// the subgroup tests of msm_points.hip (same answer on every point of the curve): none | [r] P = O, 254 doublings | by the curve's endomorphism, 2 x 63 in G1, 63 in G2
+enum SubgroupTest { SUBGROUP_NONE, SUBGROUP_ORDER, SUBGROUP_ENDO };
+// decode + curve check + `test` with one verdict byte per point (verdict_order.h: 0 good | 2 encoding | 1 curve | 4 subgroup); rejected points become the
+// identity.  The verifiers' decoder: zero bytes without the infinity bit are off the curve here (msm_points.hip: point_decode)
+int points_decode_verdicts(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, uint8_t* d_verdict, SubgroupTest test, hipStream_t s);
+// n1 G1 and n2 G2 points (host bytes) through it under the timer family `family`: dense affine points on the device in a1 / a2 (allocated here: the caller
+// keeps them or lets them go) and one verdict per point on the host.  Waits for the stream.
+int points_decode_two_lists(const uint8_t* g1, uint64_t n1, const uint8_t* g2, uint64_t n2, const char* family, SubgroupTest test, DevBuf& a1, DevBuf& a2,
+                            std::vector<uint8_t>& v1, std::vector<uint8_t>& v2, hipStream_t s);
 // ---- what the resident verification keys (verify_resident.hip) take from the other units, all on device buffers
 // the two pairing kernels (pairing_dev.hip): product q = the checked dense affine pairs [d_off[q], d_off[q + 1]) -> 576 B of GT each; enqueues only
 size_t pairing_miller_bytes(uint64_t npairs);
@@ -143,7 +149,7 @@ static constexpr uint64_t SHORT_BASES_MAX = 8192;
 int short_bases_create(ShortBases** out, Curve curve, const void* d_affine, uint64_t n, hipStream_t s);
 void short_bases_free(ShortBases* b);
 int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_live, uint32_t count, uint8_t* d_out_xyzz, hipStream_t s);
-int points_selftest_subgroup(Curve curve, int method, const uint8_t* points, uint64_t n, uint8_t* verdict, hipStream_t s);          // zk_selftest_subgroup
+int points_selftest_subgroup(Curve curve, SubgroupTest test, const uint8_t* points, uint64_t n, uint8_t* verdict, hipStream_t s);          // zk_selftest_subgroup
 // out[i] = a[i] + b[i] over encoded, already checked points (host bytes in, host bytes out)
 int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, hipStream_t s);
 // n ZCash-COMPRESSED points (host, 48 / 96 B) -> uncompressed (host, 96 / 192 B): square roots, curve and subgroup checks on the device (msm_points.hip)

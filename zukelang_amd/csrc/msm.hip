@@ -440,13 +440,13 @@ int zk_selftest_sqrt(int field, const uint8_t* a, size_t n, uint8_t* root, uint8
     ZKCHK(ensure_init());
     return points_selftest_sqrt(field, a, n, root, is_square, ctx().stream);
 }
-// the two subgroup kernels side by side on encoded points: method 0 = [r] P = O (k_subgroup_verdict), 1 = by endomorphism (k_subgroup_verdict_endo)
+// the two subgroup tests side by side on encoded points (k_subgroup_verdict of msm_points.hip): method 0 = [r] P = O, 1 = by endomorphism
 int zk_selftest_subgroup(int group, int method, const uint8_t* points, size_t n, uint8_t* verdict) {
     if (!points || !verdict || !n || (group != 0 && group != 1) || (method != 0 && method != 1))
         ZK_FAIL(ZK_ERR_ARG, "zk_selftest_subgroup: null argument, no points, a group other than 0 (G1) / 1 (G2), or a method other than 0 / 1");
     ZKCHK(ensure_init());
     DeviceScope ds(0);
-    return points_selftest_subgroup(group ? CURVE_G2 : CURVE_G1, method, points, n, verdict, ctx().stream);
+    return points_selftest_subgroup(group ? CURVE_G2 : CURVE_G1, method ? SUBGROUP_ENDO : SUBGROUP_ORDER, points, n, verdict, ctx().stream);
 }
 int zk_g1_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G1, scalars, n, out); }
 int zk_g2_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G2, scalars, n, out); }

@@ -75,15 +75,36 @@ FF_INLINE void aff_encode(uint8_t* p, const Aff<Fp2>& a) {
     fpw_to_be(p + 144, fp_from_mont(a.y.c0));
 }
 
+// THE decoder: the bytes of one uncompressed point -> the checked dense affine point at dst (the identity when rejected) and its kind, 0 good | 2 bad
+// encoding | 1 not on the curve; `bad(kind)` is called where a defect is found (the flag kernel files its bit there).  One input divides the callers:
+// 96 / 192 ZERO bytes, the infinity bit NOT set.  (0, 0) is how this library's own affine format spells the identity, and aff_on_curve passes it.
+//   ZERO_IS_IDENTITY   key lists and MSM bases (k_bytes_to_affine: msm_bases_from_bytes, the pool point of pinocchio.hip) accept the string as the
+//                      identity: buffers that went through the library's affine format arrive that way.
+//   ZERO_IS_OFF_CURVE  the verifiers' wire points (k_bytes_to_affine_verdict: points_decode_verdicts) call it a point that fails the curve equation, as
+//                      g1_decode / g2_decode of pairing_host.hip do.
+enum ZeroString { ZERO_IS_IDENTITY, ZERO_IS_OFF_CURVE };
+template <ZeroString Z, class F, class Bad> FF_INLINE uint8_t point_decode(uint8_t* dst, const uint8_t* src, Bad&& bad) {
+    Aff<F> a;
+    uint8_t kind = 0;
+    if (aff_decode(a, src)) { kind = 2; bad(2); }
+    else if ((Z == ZERO_IS_OFF_CURVE && !(src[0] & 0x40) && aff_is_inf(a)) || !aff_on_curve(a)) { kind = 1; bad(1); }
+    if (kind) a = aff_inf<F>();
+    aff_store<F>(dst, a);
+    return kind;
+}
+// one flag word per list: bit 1 = some point is not on the curve, bit 2 = some encoding is bad (msm_bases_from_bytes reads them by kind priority)
 template <class F> __global__ void k_bytes_to_affine(uint8_t* dst, const uint8_t* src, uint64_t n, int* flag) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     constexpr int B = FieldOps<F>::WORDS * 8;
-    Aff<F> a;
-    int rc = aff_decode(a, src + B * i);
-    if (rc) { atomicOr(flag, 2); a = aff_inf<F>(); }
-    else if (!aff_on_curve(a)) { atomicOr(flag, 1); a = aff_inf<F>(); }
-    aff_store<F>(dst + B * i, a);
+    point_decode<ZERO_IS_IDENTITY, F>(dst + B * i, src + B * i, [&](int kind) { atomicOr(flag, kind); });
+}
+// one verdict byte per point (the verifiers: a proof's bad point is that proof's status, not the call's)
+template <class F> __global__ void k_bytes_to_affine_verdict(uint8_t* dst, const uint8_t* src, uint64_t n, uint8_t* verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int B = FieldOps<F>::WORDS * 8;
+    verdict[i] = point_decode<ZERO_IS_OFF_CURVE, F>(dst + B * i, src + B * i, [](int) {});
 }
 template <class F> __global__ void k_affine_to_bytes(uint8_t* dst, const uint8_t* src, uint64_t n) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -263,60 +284,23 @@ __global__ __launch_bounds__(128) void k_selftest_sqrt(uint8_t* __restrict__ roo
     is_square[i] = sq ? 1 : 0;
 }
 
-// ------------------------------------------------------------------ prime-order subgroup check of uploaded KEY points: [r] P = O
+// ------------------------------------------------------------------ prime-order subgroup membership: two tests, one answer
 // The reference's points come from Bls12_381.G1/G2.of_bytes_exn / of_compressed_bytes_exn (curve.ml:199-212), which raise on a point of the curve
-// that lies outside the r-torsion; a key uploaded to the library as raw bytes gets the same treatment here.  Plain double-and-add over the bits of r
-// (a compile-time constant: the branch is wave-uniform), out-of-line group operations: ~255 doublings + 127 additions per point, 0.3 s of a 2^20 key.
+// that lies outside the r-torsion; a point uploaded to the library as raw bytes gets the same treatment here.  Each test (SubgroupTest, msm.cuh) is ONE
+// device function that takes an affine point of the curve that is not the identity and answers "in the subgroup"; the kernels below add only their way
+// of reporting.
+// ---- SUBGROUP_ORDER: [r] P = O.  Plain double-and-add over the bits of r (a compile-time constant: the branch is wave-uniform), out-of-line group
+// operations: ~255 doublings + 127 additions per point, 0.3 s of a 2^20 key.
 __device__ static const uint32_t FR_ORDER_BITS[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-// `first` (may be null): the list readers' first-failure word of k_decompress_*, filed next to the flag.
-template <class F> __global__ __launch_bounds__(128) void k_subgroup_check(const uint8_t* __restrict__ dense, uint64_t n, int* flag, unsigned long long* first) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    constexpr int B = FieldOps<F>::WORDS * 8;
-    const Aff<F> p = aff_load<F>(dense + B * i);
-    if (aff_is_inf(p)) return;
+template <class F> FF_INLINE bool in_subgroup_order(const Aff<F>& p) {
     Xyzz<F> acc = xyzz_from_aff(p);                      // the top bit (254) of r
     for (int b = 253; b >= 0; b--) {
         acc = xyzz_dbl(acc);
         if ((FR_ORDER_BITS[b >> 5] >> (b & 31)) & 1u) xyzz_madd(acc, p);
     }
-    if (!xyzz_is_inf(acc)) {
-        atomicOr(flag, 4);
-        if (first) atomicMin(first, (unsigned long long)(i << 3) | 4ull);
-    }
+    return xyzz_is_inf(acc);
 }
-
-// The two checks above with ONE VERDICT PER POINT instead of one flag per list (the batched verifiers of pairing_dev.hip: a proof's bad point is that
-// proof's status, not the call's): 0 good, 2 bad encoding, 1 not on the curve, 4 on the curve but outside the subgroup -- the kinds of the list readers.
-// A rejected point is stored as the identity.  (0, 0) WITHOUT the infinity bit is how this library's affine format spells the identity, but on the wire
-// it is a point that fails the curve equation, as it does in g1_decode / g2_decode of pairing_host.hip.
-template <class F> __global__ void k_bytes_to_affine_verdict(uint8_t* dst, const uint8_t* src, uint64_t n, uint8_t* verdict) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    constexpr int B = FieldOps<F>::WORDS * 8;
-    Aff<F> a;
-    uint8_t v = 0;
-    if (aff_decode(a, src + B * i)) v = 2;
-    else if ((!(src[B * i] & 0x40) && aff_is_inf(a)) || !aff_on_curve(a)) v = 1;
-    if (v) a = aff_inf<F>();
-    aff_store<F>(dst + B * i, a);
-    verdict[i] = v;
-}
-template <class F> __global__ __launch_bounds__(128) void k_subgroup_verdict(const uint8_t* __restrict__ dense, uint64_t n, uint8_t* verdict) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    constexpr int B = FieldOps<F>::WORDS * 8;
-    const Aff<F> p = aff_load<F>(dense + B * i);
-    if (aff_is_inf(p)) return;
-    Xyzz<F> acc = xyzz_from_aff(p);                      // the top bit (254) of r
-    for (int b = 253; b >= 0; b--) {
-        acc = xyzz_dbl(acc);
-        if ((FR_ORDER_BITS[b >> 5] >> (b & 31)) & 1u) xyzz_madd(acc, p);
-    }
-    if (!xyzz_is_inf(acc)) verdict[i] = 4;
-}
-
-// ------------------------------------------------------------------ the same verdict by the curve's endomorphisms (resident verification keys)
+// ---- SUBGROUP_ENDO: the same answer by the curve's endomorphisms (the resident verification keys of verify_resident.hip)
 // [r] P = O costs 254 doublings and 127 additions.  Both groups have an endomorphism that acts on the r-torsion as a SHORT scalar, and the curve
 // points on which it acts as that scalar are exactly the subgroup (z = -0xd201000000010000, r = z^4 - z^2 + 1):
 //   G1:  phi(x, y) = (beta x, y) = [z^2 - 1] P.   phi^2 + phi + 1 = 0 on the whole curve, so phi(P) + P = -phi^2(P) = (beta^2 x, -y):
@@ -368,15 +352,32 @@ FF_INLINE bool in_subgroup_endo(const Aff<Fp2>& q) {
     const Fp2B<128> xc = {q.x.c0, fe_neg(q.x.c1)}, yc = {q.y.c0, fe_neg(q.y.c1)};          // conjugates
     return fe_eq(t.x, fe_mul(fe_mul(cx, xc), t.zz)) && fe_eq(t.y, fe_mul(fe_mul(cy, yc), t.zzz));
 }
-// verdict[i] = 4 where point i of `dense` (affine, on the curve; a point an earlier kernel rejected is stored as the identity) is outside the subgroup;
-// other verdicts stay.  The meaning of k_subgroup_verdict.
-template <class F> __global__ __launch_bounds__(128) void k_subgroup_verdict_endo(const uint8_t* __restrict__ dense, uint64_t n, uint8_t* verdict) {
+template <SubgroupTest T, class F> FF_INLINE bool in_subgroup(const Aff<F>& p) {
+    static_assert(T == SUBGROUP_ORDER || T == SUBGROUP_ENDO, "SUBGROUP_NONE launches no kernel");
+    if constexpr (T == SUBGROUP_ENDO) return in_subgroup_endo(p);
+    else return in_subgroup_order(p);
+}
+// The kernels read `dense` (affine, on the curve; a point the decoder rejected is stored as the identity and skipped) and report in their caller's way:
+// one flag word per list, bit 4, plus -- `first` may be null -- the list readers' first-failure word of k_decompress_* ...
+template <class F> __global__ __launch_bounds__(128) void k_subgroup_check(const uint8_t* __restrict__ dense, uint64_t n, int* flag, unsigned long long* first) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     constexpr int B = FieldOps<F>::WORDS * 8;
     const Aff<F> p = aff_load<F>(dense + B * i);
     if (aff_is_inf(p)) return;
-    if (!in_subgroup_endo(p)) verdict[i] = 4;
+    if (!in_subgroup_order(p)) {
+        atomicOr(flag, 4);
+        if (first) atomicMin(first, (unsigned long long)(i << 3) | 4ull);
+    }
+}
+// ... or verdict[i] = 4 next to the decoder's verdict bytes; other verdicts stay
+template <class F, SubgroupTest T> __global__ __launch_bounds__(128) void k_subgroup_verdict(const uint8_t* __restrict__ dense, uint64_t n, uint8_t* verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int B = FieldOps<F>::WORDS * 8;
+    const Aff<F> p = aff_load<F>(dense + B * i);
+    if (aff_is_inf(p)) return;
+    if (!in_subgroup<T>(p)) verdict[i] = 4;
 }
 
 // out[i] = a[i] + b[i] on dense affine points, every case of the group law (an identity operand, P + P, P + (-P)): the verifier's vio + vv and the like
@@ -492,6 +493,13 @@ __global__ __launch_bounds__(128) void k_fixed_base_mul(uint8_t* __restrict__ ou
     aff_store<F>(out + AB * i, xyzz_to_aff(acc));
 }
 // ================================================================== host side
+// THE place a Curve becomes a field type: fn(FieldTag<Fp>{}) for G1, fn(FieldTag<Fp2>{}) for G2, for launches whose two arms differ in the field alone
+template <class F> struct FieldTag { using type = F; };
+template <class Fn> static void for_curve(Curve curve, Fn&& fn) {
+    if (curve == CURVE_G1) fn(FieldTag<Fp>{});
+    else fn(FieldTag<Fp2>{});
+}
+#define FIELD_OF(tag) typename decltype(tag)::type
 template <class F> static int bases_finish(MsmBases& b, const void* d_dense, hipStream_t s) {
     // every base set carries its identity flags: the sort never files an identity base into a bucket, so the accumulate loop can take table
     // entries for genuine points (no identity test per addition) in BOTH table modes
@@ -507,8 +515,7 @@ int msm_bases_dense(const MsmBases& b, uint64_t lo, uint64_t count, void* d_dens
     if (lo + count > b.n) ZK_FAIL(ZK_ERR_ARG, "msm_bases_dense: range outside the base set");
     if (!count) return ZK_OK;
     const uint8_t* src = b.table.as<uint8_t>() + table_entry_bytes(b.curve) * lo;
-    if (b.curve == CURVE_G1) hipLaunchKernelGGL(k_table_to_dense<Fp>, grid_for(count, 128), dim3(128), 0, s, (uint8_t*)d_dense, src, count);
-    else hipLaunchKernelGGL(k_table_to_dense<Fp2>, grid_for(count, 128), dim3(128), 0, s, (uint8_t*)d_dense, src, count);
+    for_curve(b.curve, [&](auto f) { hipLaunchKernelGGL(k_table_to_dense<FIELD_OF(f)>, grid_for(count, 128), dim3(128), 0, s, (uint8_t*)d_dense, src, count); });
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
@@ -525,46 +532,54 @@ static int bases_setup(MsmBases& b, Curve curve, uint64_t n, uint32_t c, bool pr
 }
 int points_bytes_to_affine(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, int* d_flag, hipStream_t s) {
     if (!n) return ZK_OK;
-    if (curve == CURVE_G1) hipLaunchKernelGGL(k_bytes_to_affine<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_flag);
-    else hipLaunchKernelGGL(k_bytes_to_affine<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_flag);
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_bytes_to_affine<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_flag); });
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
-int points_decode_verdicts(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, uint8_t* d_verdict, bool check_subgroup, hipStream_t s) {
+int points_decode_verdicts(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, uint8_t* d_verdict, SubgroupTest test, hipStream_t s) {
     if (!n) return ZK_OK;
-    if (curve == CURVE_G1) {
-        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
-        if (check_subgroup) hipLaunchKernelGGL(k_subgroup_verdict<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
-    } else {
-        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
-        if (check_subgroup) hipLaunchKernelGGL(k_subgroup_verdict<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
-    }
+    for_curve(curve, [&](auto f) {
+        using F = FIELD_OF(f);
+        const dim3 grid = grid_for(n, 128);
+        hipLaunchKernelGGL(k_bytes_to_affine_verdict<F>, grid, dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
+        if (test == SUBGROUP_ORDER) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_verdict<F, SUBGROUP_ORDER>), grid, dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+        if (test == SUBGROUP_ENDO) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_verdict<F, SUBGROUP_ENDO>), grid, dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+    });
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
-// the same with the subgroup verdict by endomorphism (k_subgroup_verdict_endo): the resident verification keys' decoder
-int points_decode_verdicts_endo(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, uint8_t* d_verdict, hipStream_t s) {
-    if (!n) return ZK_OK;
-    if (curve == CURVE_G1) {
-        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
-        hipLaunchKernelGGL(k_subgroup_verdict_endo<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
-    } else {
-        hipLaunchKernelGGL(k_bytes_to_affine_verdict<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
-        hipLaunchKernelGGL(k_subgroup_verdict_endo<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+// n1 G1 and n2 G2 points (host bytes) -> dense affine on the device (a1, a2: kept by the caller or dropped) + one verdict each on the host
+int points_decode_two_lists(const uint8_t* g1, uint64_t n1, const uint8_t* g2, uint64_t n2, const char* family, SubgroupTest test, DevBuf& a1, DevBuf& a2,
+                            std::vector<uint8_t>& v1, std::vector<uint8_t>& v2, hipStream_t s) {
+    v1.assign(n1, 0);
+    v2.assign(n2, 0);
+    DevBuf b1, b2, dv;
+    ZKCHK(b1.alloc(96 * n1));
+    ZKCHK(b2.alloc(192 * n2));
+    ZKCHK(a1.alloc(96 * n1));
+    ZKCHK(a2.alloc(192 * n2));
+    ZKCHK(dv.alloc(n1 + n2));
+    if (n1) HIPCHK(hipMemcpyAsync(b1.p, g1, 96 * n1, hipMemcpyHostToDevice, s));
+    if (n2) HIPCHK(hipMemcpyAsync(b2.p, g2, 192 * n2, hipMemcpyHostToDevice, s));
+    {
+        ScopedTimer t(family, s);
+        ZKCHK(points_decode_verdicts(CURVE_G2, a2.p, b2.p, n2, dv.as<uint8_t>() + n1, test, s));
+        ZKCHK(points_decode_verdicts(CURVE_G1, a1.p, b1.p, n1, dv.as<uint8_t>(), test, s));
     }
-    HIPCHK(hipGetLastError());
+    if (n1) HIPCHK(hipMemcpyAsync(v1.data(), dv.p, n1, hipMemcpyDeviceToHost, s));
+    if (n2) HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + n1, n2, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return ZK_OK;
 }
-// zk_selftest_subgroup: n encoded points (host) -> n verdicts (host) through either subgroup kernel
-int points_selftest_subgroup(Curve curve, int method, const uint8_t* points, uint64_t n, uint8_t* verdict, hipStream_t s) {
+// zk_selftest_subgroup: n encoded points (host) -> n verdicts (host) through the subgroup test asked for
+int points_selftest_subgroup(Curve curve, SubgroupTest test, const uint8_t* points, uint64_t n, uint8_t* verdict, hipStream_t s) {
     const size_t ab = aff_bytes(curve);
     DevBuf raw, aff, dv;
     ZKCHK(raw.alloc(ab * n));
     ZKCHK(aff.alloc(ab * n));
     ZKCHK(dv.alloc(n));
     HIPCHK(hipMemcpyAsync(raw.p, points, ab * n, hipMemcpyHostToDevice, s));
-    if (method == 0) ZKCHK(points_decode_verdicts(curve, aff.p, raw.p, n, dv.as<uint8_t>(), true, s));
-    else ZKCHK(points_decode_verdicts_endo(curve, aff.p, raw.p, n, dv.as<uint8_t>(), s));
+    ZKCHK(points_decode_verdicts(curve, aff.p, raw.p, n, dv.as<uint8_t>(), test, s));
     HIPCHK(hipMemcpyAsync(verdict, dv.p, n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return ZK_OK;
@@ -580,9 +595,9 @@ int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n
     ZKCHK(dv.alloc(2 * n));
     HIPCHK(hipMemcpyAsync(raw.p, a, ab * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(raw.as<uint8_t>() + ab * n, b, ab * n, hipMemcpyHostToDevice, s));
-    ZKCHK(points_decode_verdicts(curve, da.p, raw.p, 2 * n, dv.as<uint8_t>(), false, s));
-    if (curve == CURVE_G1) hipLaunchKernelGGL(k_aff_add<Fp>, grid_for(n, 64), dim3(64), 0, s, db.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>() + ab * n, n);
-    else hipLaunchKernelGGL(k_aff_add<Fp2>, grid_for(n, 64), dim3(64), 0, s, db.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>(), (const uint8_t*)da.as<uint8_t>() + ab * n, n);
+    ZKCHK(points_decode_verdicts(curve, da.p, raw.p, 2 * n, dv.as<uint8_t>(), SUBGROUP_NONE, s));
+    const uint8_t* sum_a = da.as<uint8_t>();
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_aff_add<FIELD_OF(f)>, grid_for(n, 64), dim3(64), 0, s, db.as<uint8_t>(), sum_a, sum_a + ab * n, n); });
     HIPCHK(hipGetLastError());
     ZKCHK(points_affine_to_bytes(curve, raw.p, db.p, n, s));
     HIPCHK(hipMemcpyAsync(out, raw.p, ab * n, hipMemcpyDeviceToHost, s));
@@ -591,14 +606,12 @@ int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n
 }
 int points_affine_to_bytes(Curve curve, void* d_bytes, const void* d_aff, uint64_t n, hipStream_t s) {
     if (!n) return ZK_OK;
-    if (curve == CURVE_G1) hipLaunchKernelGGL(k_affine_to_bytes<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_bytes, (const uint8_t*)d_aff, n);
-    else hipLaunchKernelGGL(k_affine_to_bytes<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_bytes, (const uint8_t*)d_aff, n);
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_affine_to_bytes<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_bytes, (const uint8_t*)d_aff, n); });
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
 int points_xyzz_to_bytes_dev(Curve curve, const void* d_xyzz, uint64_t count, void* d_bytes, hipStream_t s) {
-    if (curve == CURVE_G1) hipLaunchKernelGGL(k_xyzz_to_bytes<Fp>, grid_for(count, 64), dim3(64), 0, s, (uint8_t*)d_bytes, (const uint8_t*)d_xyzz, count);
-    else hipLaunchKernelGGL(k_xyzz_to_bytes<Fp2>, grid_for(count, 64), dim3(64), 0, s, (uint8_t*)d_bytes, (const uint8_t*)d_xyzz, count);
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_xyzz_to_bytes<FIELD_OF(f)>, grid_for(count, 64), dim3(64), 0, s, (uint8_t*)d_bytes, (const uint8_t*)d_xyzz, count); });
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
@@ -624,6 +637,9 @@ int msm_bases_from_device_affine(MsmBases& b, Curve curve, const void* d_affine,
     ZKCHK(bases_setup(b, curve, n, c, precomp, in_subgroup));
     return curve == CURVE_G1 ? bases_finish<Fp>(b, d_affine, s) : bases_finish<Fp2>(b, d_affine, s);
 }
+static void launch_subgroup_check(Curve curve, const void* d_dense, uint64_t n, int* d_flag, unsigned long long* d_first, hipStream_t s) {
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_subgroup_check<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_dense, n, d_flag, d_first); });
+}
 int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, uint64_t n, uint32_t c, bool precomp, hipStream_t s, bool check_subgroup) {
     ZKCHK(bases_setup(b, curve, n, c, precomp, check_subgroup));      // folded digits only for points the [r] P = O test below has passed
     DevBuf raw, dense, flag;
@@ -635,8 +651,7 @@ int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, ui
     ZKCHK(points_bytes_to_affine(curve, dense.p, raw.p, n, flag.as<int>(), s));
     if (check_subgroup) {
         ScopedTimer t("subgroup_check", s);
-        if (curve == CURVE_G1) hipLaunchKernelGGL(k_subgroup_check<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), (unsigned long long*)nullptr);
-        else hipLaunchKernelGGL(k_subgroup_check<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), (unsigned long long*)nullptr);
+        launch_subgroup_check(curve, dense.p, n, flag.as<int>(), nullptr, s);
     }
     int h = 0;
     HIPCHK(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, s));
@@ -663,14 +678,13 @@ int fixed_base_mul(Curve curve, void* d_out, const void* d_scalars, uint64_t n, 
     DevBuf& tab = ctx().bufs->pow2[curve];
     if (!tab.p) {
         ZKCHK(tab.alloc(aff_bytes(curve) * 256));
-        if (curve == CURVE_G1) hipLaunchKernelGGL(k_gen_pow2_table<Fp>, dim3(4), dim3(64), 0, s, tab.as<uint8_t>());
-        else hipLaunchKernelGGL(k_gen_pow2_table<Fp2>, dim3(4), dim3(64), 0, s, tab.as<uint8_t>());
+        for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_gen_pow2_table<FIELD_OF(f)>, dim3(4), dim3(64), 0, s, tab.as<uint8_t>()); });
         HIPCHK(hipGetLastError());
     }
     if (!n) return ZK_OK;
     ScopedTimer t("fixed_base_mul", s);
-    if (curve == CURVE_G1) hipLaunchKernelGGL(k_fixed_base_mul<Fp>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_out, (const uint32_t*)d_scalars, n, tab.as<uint8_t>());
-    else hipLaunchKernelGGL(k_fixed_base_mul<Fp2>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_out, (const uint32_t*)d_scalars, n, tab.as<uint8_t>());
+    const uint8_t* pow2 = tab.as<uint8_t>();
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_fixed_base_mul<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_out, (const uint32_t*)d_scalars, n, pow2); });
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
@@ -687,13 +701,8 @@ int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, 
     HIPCHK(hipMemsetAsync(flag.as<uint8_t>() + 8, 0xFF, 8, s));
     unsigned long long* first = (unsigned long long*)(flag.as<uint8_t>() + 8);
     HIPCHK(hipMemcpyAsync(din.p, in, cb * n, hipMemcpyHostToDevice, s));
-    if (curve == CURVE_G1) {
-        hipLaunchKernelGGL(k_decompress_g1, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, first);
-        hipLaunchKernelGGL(k_subgroup_check<Fp>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), first);
-    } else {
-        hipLaunchKernelGGL(k_decompress_g2, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, first);
-        hipLaunchKernelGGL(k_subgroup_check<Fp2>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)dense.as<uint8_t>(), n, flag.as<int>(), first);
-    }
+    hipLaunchKernelGGL(curve == CURVE_G1 ? k_decompress_g1 : k_decompress_g2, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, first);
+    launch_subgroup_check(curve, dense.p, n, flag.as<int>(), first, s);
     HIPCHK(hipGetLastError());
     ZKCHK(points_affine_to_bytes(curve, dout.p, dense.p, n, s));
     unsigned long long h = 0;

@@ -3,7 +3,8 @@
 // file does not touch: the host-only sanitizer library is built from it alone); a stream of proofs is checked here.  Same definitions, same bytes:
 // Pairing.pairing of curve.mli:46-54, Groth16.verify of groth16.ml:163-173, Verify.f of pinocchio.ml:254-420.
 //
-//   bytes -> affine + one verdict per point    k_bytes_to_affine_verdict, k_subgroup_verdict (msm_points.hip: one lane per point)
+//   bytes -> affine + one verdict per point    k_bytes_to_affine_verdict, k_subgroup_verdict by [r] P = O (msm_points.hip: one lane per point); which
+//                                               bad point decides a proof's or the call's status: verdict_order.h
 //   sums over the public inputs                 the resident short products of msm_resident.hip: the key's points uploaded once per call, one product per proof
 //   Miller loops                                k_miller: one group of 8 lanes per PAIR (pairing_tower.cuh), inversion-free, 63 steps
 //   products + final exponentiations            k_final_exp: one group per PRODUCT multiplies its pairs' Miller values and raises to (p^12 - 1) / r
@@ -14,6 +15,7 @@
 
 #include "msm.cuh"
 #include "pairing_consts.h"
+#include "verdict_order.h"
 
 #include <string.h>
 #include <vector>
@@ -90,30 +92,6 @@ __global__ __launch_bounds__(64) void k_selftest_fp12(int op, const uint8_t* __r
 
 // ================================================================== host side
 static constexpr uint32_t MAX_PROOFS = 1u << 24;          // 13 pairs each stay inside the 31-bit pair index
-static int verdict_code(uint8_t v) { return v == 0 ? ZK_OK : v == 2 ? ZK_ERR_ARG : ZK_ERR_NOT_ON_CURVE; }
-
-// n1 G1 and n2 G2 points (host bytes) -> one verdict each: encoding, curve, subgroup
-static int check_points(const uint8_t* g1, uint64_t n1, const uint8_t* g2, uint64_t n2, std::vector<uint8_t>& v1, std::vector<uint8_t>& v2, hipStream_t s) {
-    v1.assign(n1, 0);
-    v2.assign(n2, 0);
-    DevBuf b1, b2, a1, a2, dv;
-    ZKCHK(b1.alloc(96 * n1));
-    ZKCHK(b2.alloc(192 * n2));
-    ZKCHK(a1.alloc(96 * n1));
-    ZKCHK(a2.alloc(192 * n2));
-    ZKCHK(dv.alloc(n1 + n2));
-    if (n1) HIPCHK(hipMemcpyAsync(b1.p, g1, 96 * n1, hipMemcpyHostToDevice, s));
-    if (n2) HIPCHK(hipMemcpyAsync(b2.p, g2, 192 * n2, hipMemcpyHostToDevice, s));
-    {
-        ScopedTimer t("pairing_point_checks", s);
-        ZKCHK(points_decode_verdicts(CURVE_G2, a2.p, b2.p, n2, dv.as<uint8_t>() + n1, true, s));
-        ZKCHK(points_decode_verdicts(CURVE_G1, a1.p, b1.p, n1, dv.as<uint8_t>(), true, s));
-    }
-    if (n1) HIPCHK(hipMemcpyAsync(v1.data(), dv.p, n1, hipMemcpyDeviceToHost, s));
-    if (n2) HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + n1, n2, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return ZK_OK;
-}
 
 // The two pairing kernels on buffers that are ALREADY on the device: npairs checked dense affine pairs (d_g1: 96 B each, d_g2: 192 B), product q = the
 // pairs [d_off[q], d_off[q + 1]) -> count GT encodings in d_gt (576 B each).  d_miller: F12_RAW_WORDS words per pair.  Enqueues, does not wait.
@@ -133,9 +111,9 @@ int pairing_products_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t n
     return ZK_OK;
 }
 
-// count products over npairs = sum lens pairs (host bytes) -> count GT encodings.  check: every point's subgroup membership too (else encoding and
-// curve only: the caller has checked them).  v1 / v2: the verdicts, one per pair and side; a rejected point counts as the identity.
-static int run_products(const uint8_t* g1, const uint8_t* g2, uint64_t npairs, const uint64_t* lens, uint32_t count, bool check, std::vector<uint8_t>& v1,
+// count products over npairs = sum lens pairs (host bytes) -> count GT encodings.  test: every point's subgroup membership too (SUBGROUP_NONE: encoding
+// and curve only, the caller has checked them).  v1 / v2: the verdicts, one per pair and side; a rejected point counts as the identity.
+static int run_products(const uint8_t* g1, const uint8_t* g2, uint64_t npairs, const uint64_t* lens, uint32_t count, SubgroupTest test, std::vector<uint8_t>& v1,
                         std::vector<uint8_t>& v2, uint8_t* gt_out, hipStream_t s) {
     v1.assign(npairs, 0);
     v2.assign(npairs, 0);
@@ -159,8 +137,8 @@ static int run_products(const uint8_t* g1, const uint8_t* g2, uint64_t npairs, c
         HIPCHK(hipMemcpyAsync(b2.p, g2, 192 * npairs, hipMemcpyHostToDevice, s));
         {
             ScopedTimer t("pairing_point_checks", s);
-            ZKCHK(points_decode_verdicts(CURVE_G2, a2.p, b2.p, npairs, dv.as<uint8_t>() + npairs, check, s));
-            ZKCHK(points_decode_verdicts(CURVE_G1, a1.p, b1.p, npairs, dv.as<uint8_t>(), check, s));
+            ZKCHK(points_decode_verdicts(CURVE_G2, a2.p, b2.p, npairs, dv.as<uint8_t>() + npairs, test, s));
+            ZKCHK(points_decode_verdicts(CURVE_G1, a1.p, b1.p, npairs, dv.as<uint8_t>(), test, s));
         }
         HIPCHK(hipMemcpyAsync(v1.data(), dv.p, npairs, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + npairs, npairs, hipMemcpyDeviceToHost, s));
@@ -221,6 +199,31 @@ static int dot_many(int group, const uint8_t* points, size_t n, const uint8_t* s
     (void)zk_bases_free(h);
     return rc;
 }
+// The front half of both verifiers.  Every point of the call through the decoder and [r] P = O, once: the proofs' points laid out per proof as the plan
+// says (G1 point q of proof i at n1 i + q: the layout of k_vk_gather), the key's k1 / k2 points behind them.  A defect of the key is the call's; else
+// st[i] = proof i's status (its first bad point in the host's order, then its public inputs: verdict_order.h), live[i] = its pairings are still to be taken.
+static int check_call(const VkPlan& p, const uint8_t* proofs, uint32_t count, const uint8_t* key1, size_t k1, const uint8_t* key2, size_t k2,
+                      KeyDefect (*key_defect)(const uint8_t*, const uint8_t*, size_t), size_t n_io, const uint8_t* io_scalars, std::vector<int32_t>& st,
+                      std::vector<uint8_t>& live, hipStream_t s) {
+    const size_t c = count;
+    std::vector<uint8_t> p1(96 * (p.n1 * c + k1)), p2(192 * (p.n2 * c + k2)), v1, v2, bad(c, 0);
+    for (size_t i = 0; i < c; i++) {
+        for (uint32_t q = 0; q < p.n1; q++) memcpy(&p1[96 * (p.n1 * i + q)], proofs + p.stride * i + p.off1[q], 96);
+        for (uint32_t q = 0; q < p.n2; q++) memcpy(&p2[192 * (p.n2 * i + q)], proofs + p.stride * i + p.off2[q], 192);
+        for (size_t k = 0; k < n_io && !bad[i]; k++) bad[i] = !fr_canonical(io_scalars + 32 * (n_io * i + k));
+    }
+    if (k1) memcpy(&p1[96 * p.n1 * c], key1, 96 * k1);
+    memcpy(&p2[192 * p.n2 * c], key2, 192 * k2);
+    DevBuf a1, a2;          // the decoded points are not kept: the pairs go up as bytes again
+    ZKCHK(points_decode_two_lists(p1.data(), p.n1 * c + k1, p2.data(), p.n2 * c + k2, "pairing_point_checks", SUBGROUP_ORDER, a1, a2, v1, v2, s));
+    const KeyDefect kd = key_defect(v1.data() + p.n1 * c, v2.data() + p.n2 * c, n_io);
+    if (kd.verdict) ZK_FAIL(verdict_code(kd.verdict), kd.what);
+    for (uint32_t i = 0; i < count; i++) {
+        st[i] = verdict_code(proof_code(p, v1.data(), v2.data(), bad.data(), i));
+        live[i] = st[i] == ZK_OK;
+    }
+    return ZK_OK;
+}
 
 }  // namespace zk
 
@@ -236,7 +239,7 @@ int zk_pairing_product_many(const uint8_t* g1_points, const uint8_t* g2_points, 
     ZKCHK(ensure_init());
     DeviceScope ds(0);
     std::vector<uint8_t> v1, v2;
-    ZKCHK(run_products(g1_points, g2_points, npairs, lens, count, true, v1, v2, gt_out, ctx().stream));
+    ZKCHK(run_products(g1_points, g2_points, npairs, lens, count, SUBGROUP_ORDER, v1, v2, gt_out, ctx().stream));
     for (uint64_t i = 0; i < npairs; i++) {          // the host's decoding order: G1 of pair i, then G2 of pair i
         if (v1[i]) ZK_FAIL(verdict_code(v1[i]), "zk_pairing_product_many: bad G1 point (encoding, curve or subgroup)");
         if (v2[i]) ZK_FAIL(verdict_code(v2[i]), "zk_pairing_product_many: bad G2 point (encoding, curve or subgroup)");
@@ -254,32 +257,12 @@ int zk_groth16_verify_many(const uint8_t ab[576], const uint8_t* ltgm_io, size_t
     ZKCHK(ensure_init());
     DeviceScope ds(0);
     hipStream_t s = ctx().stream;
-    // every point once: G1 = A[count] | C[count] | ltgm_io[n_io], G2 = B[count] | gm | d
-    std::vector<uint8_t> p1(96 * (2 * (size_t)count + n_io)), p2(192 * ((size_t)count + 2)), v1, v2;
-    for (uint32_t i = 0; i < count; i++) {
-        memcpy(&p1[96 * (size_t)i], proofs + 384 * (size_t)i, 96);
-        memcpy(&p1[96 * ((size_t)count + i)], proofs + 384 * (size_t)i + 288, 96);
-        memcpy(&p2[192 * (size_t)i], proofs + 384 * (size_t)i + 96, 192);
-    }
-    if (n_io) memcpy(&p1[96 * 2 * (size_t)count], ltgm_io, 96 * n_io);
-    memcpy(&p2[192 * (size_t)count], gm, 192);
-    memcpy(&p2[192 * ((size_t)count + 1)], d, 192);
-    ZKCHK(check_points(p1.data(), p1.size() / 96, p2.data(), p2.size() / 192, v1, v2, s));
-    // the key, in the host's order (gm, d, ltgm_io): its defects are the call's
-    if (v2[count]) ZK_FAIL(verdict_code(v2[count]), "verify: bad G2 point");
-    if (v2[count + 1]) ZK_FAIL(verdict_code(v2[count + 1]), "verify: bad G2 point");
-    for (size_t k = 0; k < n_io; k++)
-        if (v1[2 * (size_t)count + k]) ZK_FAIL(verdict_code(v1[2 * (size_t)count + k]), "verify: bad G1 point in the key");
-    // a proof's own: A, B, C in that order, then its public inputs
-    std::vector<int32_t> st(count, ZK_OK);
-    std::vector<uint8_t> live(count, 1);
-    for (uint32_t i = 0; i < count; i++) {
-        const uint8_t v = v1[i] ? v1[i] : v2[i] ? v2[i] : v1[count + i];
-        st[i] = verdict_code(v);
-        for (size_t k = 0; k < n_io && st[i] == ZK_OK; k++)
-            if (!fr_canonical(io_scalars + 32 * (n_io * (size_t)i + k))) st[i] = ZK_ERR_SCALAR_RANGE;
-        live[i] = st[i] == ZK_OK;
-    }
+    uint8_t key2[384];
+    memcpy(key2, gm, 192);
+    memcpy(key2 + 192, d, 192);
+    std::vector<int32_t> st(count);
+    std::vector<uint8_t> live(count), v1, v2;
+    ZKCHK(check_call(PLAN_GROTH16, proofs, count, ltgm_io, n_io, key2, 2, groth16_key_defect, n_io, io_scalars, st, live, s));
     std::vector<uint8_t> acc(96 * (size_t)count);
     ZKCHK(dot_many(0, ltgm_io, n_io, io_scalars, count, live, acc.data()));
     std::vector<uint8_t> q1(96 * 3 * (size_t)count), q2(192 * 3 * (size_t)count), gt(576 * (size_t)count);
@@ -298,7 +281,7 @@ int zk_groth16_verify_many(const uint8_t ab[576], const uint8_t* ltgm_io, size_t
         memcpy(b + 384, d, 192);
     }
     const std::vector<uint64_t> lens(count, 3);
-    ZKCHK(run_products(q1.data(), q2.data(), 3 * (uint64_t)count, lens.data(), count, false, v1, v2, gt.data(), s));
+    ZKCHK(run_products(q1.data(), q2.data(), 3 * (uint64_t)count, lens.data(), count, SUBGROUP_NONE, v1, v2, gt.data(), s));
     for (uint32_t i = 0; i < count; i++) {
         ok[i] = live[i] && memcmp(&gt[576 * (size_t)i], ab, 576) == 0 ? 1 : 0;
         if (status) status[i] = st[i];
@@ -318,37 +301,10 @@ int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t 
     ZKCHK(ensure_init());
     DeviceScope ds(0);
     hipStream_t s = ctx().stream;
-    const size_t k1 = 3 + 2 * n_io, k2 = 6 + n_io, c = count;
-    static const size_t P1[6] = {0, 288, 384, 480, 768, 864}, P2[2] = {96, 576};          // a proof's G1 points (vv yy h vavv yayy bvwy) and G2 points (ww waww)
-    std::vector<uint8_t> p1(96 * (k1 + 6 * c)), p2(192 * (k2 + 2 * c)), v1, v2;
-    memcpy(p1.data(), vk_g1, 96 * k1);
-    memcpy(p2.data(), vk_g2, 192 * k2);
-    for (size_t i = 0; i < c; i++) {
-        for (int q = 0; q < 6; q++) memcpy(&p1[96 * (k1 + 6 * i + q)], proofs + 960 * i + P1[q], 96);
-        for (int q = 0; q < 2; q++) memcpy(&p2[192 * (k2 + 2 * i + q)], proofs + 960 * i + P2[q], 192);
-    }
-    ZKCHK(check_points(p1.data(), k1 + 6 * c, p2.data(), k2 + 2 * c, v1, v2, s));
-    // the key in the host's order: one aw bgm | one2 av ay gm2 bgm2 yt | vv_io[k] yy_io[k] ww_io[k] for every k
-    for (size_t k = 0; k < 3; k++)
-        if (v1[k]) ZK_FAIL(verdict_code(v1[k]), "verify: bad G1 point");
-    for (size_t k = 0; k < 6; k++)
-        if (v2[k]) ZK_FAIL(verdict_code(v2[k]), "verify: bad G2 point");
-    for (size_t k = 0; k < n_io; k++) {
-        const uint8_t v = v1[3 + k] ? v1[3 + k] : v1[3 + n_io + k] ? v1[3 + n_io + k] : v2[6 + k];
-        if (v) ZK_FAIL(verdict_code(v), "verify: bad point in the key");
-    }
-    // a proof's own, in the host's order: vv ww yy h vavv waww yayy bvwy, then its public inputs
-    std::vector<int32_t> st(c, ZK_OK);
-    std::vector<uint8_t> live(c, 1);
-    for (size_t i = 0; i < c; i++) {
-        const uint8_t* a = &v1[k1 + 6 * i];
-        const uint8_t* b = &v2[k2 + 2 * i];
-        const uint8_t order[8] = {a[0], b[0], a[1], a[2], a[3], b[1], a[4], a[5]};
-        for (int q = 0; q < 8 && st[i] == ZK_OK; q++) st[i] = verdict_code(order[q]);
-        for (size_t k = 0; k < n_io && st[i] == ZK_OK; k++)
-            if (!fr_canonical(io_scalars + 32 * (n_io * i + k))) st[i] = ZK_ERR_SCALAR_RANGE;
-        live[i] = st[i] == ZK_OK;
-    }
+    const size_t c = count;
+    std::vector<int32_t> st(count);
+    std::vector<uint8_t> live(count), v1, v2;
+    ZKCHK(check_call(PLAN_PINOCCHIO, proofs, count, vk_g1, 3 + 2 * n_io, vk_g2, 6 + n_io, pinocchio_key_defect, n_io, io_scalars, st, live, s));
     // vio, yio, wio (G.dot over the public inputs), then vio + vv, yio + yy, wio + ww
     std::vector<uint8_t> vio(96 * c), yio(96 * c), wio(192 * c), pv(96 * c), py(96 * c), pw(192 * c);
     ZKCHK(dot_many(0, vk_g1 + 96 * 3, n_io, io_scalars, count, live, vio.data()));
@@ -398,10 +354,9 @@ int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t 
         pair(bvwy, false, gm2); pair(vv, true, bgm2); pair(bgm, true, ww); pair(yy, true, bgm2);             // :361-366
         pair(&vsum[96 * i], false, &wsum[192 * i]); pair(&ysum[96 * i], true, one2); pair(h, true, yt);      // :418-420
     }
-    ZKCHK(run_products(q1.data(), q2.data(), 13 * (uint64_t)c, lens.data(), 5 * count, false, v1, v2, gt.data(), s));
+    ZKCHK(run_products(q1.data(), q2.data(), 13 * (uint64_t)c, lens.data(), 5 * count, SUBGROUP_NONE, v1, v2, gt.data(), s));
     uint8_t gt_one[576];
-    memset(gt_one, 0, 576);
-    gt_one[47] = 1;
+    gt_one_bytes(gt_one);
     for (size_t i = 0; i < c; i++) {
         bool good = live[i] != 0;
         for (int q = 0; q < 5; q++) good = good && memcmp(&gt[576 * (5 * i + q)], gt_one, 576) == 0;

@@ -5,12 +5,12 @@
 // public zk_bases_upload (a second decode and check, window tables, a pinned arena), and a dozen buffers are allocated and freed.  Here the key is
 // decoded and checked ONCE, and a call moves only what belongs to its proofs:
 //
-//   upload   key bytes -> dense affine points on the device, every one checked (encoding, curve, subgroup by endomorphism: k_subgroup_verdict_endo of
+//   upload   key bytes -> dense affine points on the device, every one checked (encoding, curve, subgroup by endomorphism: SUBGROUP_ENDO of
 //            msm_points.hip); the IO points also as a narrow table for the short products of msm_resident.hip; `ab` kept as its 576 bytes.
 //   verify   per slab of up to VK_SLAB proofs, on workspaces the handle keeps and grows on demand:
 //              1 one H2D copy: proofs | public inputs
-//              2 k_vk_gather + k_bytes_to_affine_verdict + k_subgroup_verdict_endo: every proof point decoded once, one verdict byte each
-//              3 k_vk_scalar_range, k_vk_status: a public input >= r, then the proof's first failure in the host's order -> one code byte per proof
+//              2 k_vk_gather + k_bytes_to_affine_verdict + k_subgroup_verdict: every proof point decoded once, one verdict byte each
+//              3 k_vk_scalar_range, k_vk_status: a public input >= r, then the proof's first failure in the host's order (verdict_order.h) -> one code byte per proof
 //              4 one short product per IO sum and proof (k_msm_short; a rejected proof's product has no scalars), results stay on the device
 //              5 k_vk_pairs_*: the pair lists assembled on the device -- G1 points negated as points (y -> p - y), Pinocchio's vio + vv, yio + yy,
 //                wio + ww added here; a rejected proof gets identity pairs
@@ -21,6 +21,7 @@
 #include "ec.cuh"
 #include "handle_table.h"
 #include "msm.cuh"
+#include "verdict_order.h"
 
 #include <memory>
 #include <string.h>
@@ -29,17 +30,6 @@ namespace zk {
 
 static constexpr uint32_t VK_MAX_PROOFS = 1u << 24;
 static constexpr uint32_t VK_SLAB = 8192;          // proofs per pass: bounds the workspaces (Pinocchio: 20 KiB per proof) whatever the call's count
-enum : uint8_t { VK_CODE_SCALAR = 8 };             // next to the point verdicts 1, 2, 4
-
-// where a proof's points lie in its bytes, and the order in which the host verifier meets them (bit 7: a G2 point)
-struct VkPlan {
-    uint32_t stride, n1, n2, pairs, products;
-    uint32_t off1[6], off2[2];
-    uint32_t norder;
-    uint8_t order[8];
-};
-static const VkPlan PLAN_GROTH16 = {384, 2, 1, 3, 1, {0, 288, 0, 0, 0, 0}, {96, 0}, 3, {0, 0x80, 1, 0, 0, 0, 0, 0}};                          // A | B | C
-static const VkPlan PLAN_PINOCCHIO = {960, 6, 2, 13, 5, {0, 288, 384, 480, 768, 864}, {96, 576}, 8, {0, 0x80, 1, 2, 3, 0x81, 4, 5}};         // vv ww yy h vavv waww yayy bvwy
 
 // 16-byte units of every proof's points -> the dense lists the decoder reads: G1 point q of proof i at g1[(n1 i + q) 96], G2 at g2[(n2 i + q) 192]
 __global__ void k_vk_gather(const uint8_t* __restrict__ proofs, uint32_t count, VkPlan p, uint8_t* __restrict__ g1, uint8_t* __restrict__ g2) {
@@ -62,17 +52,12 @@ __global__ void k_vk_scalar_range(const uint32_t* __restrict__ scalars, uint64_t
     if (t >= total) return;
     if (!fe_is_canonical(fe_load<FrParams>(scalars + 8 * t))) bad[t / n_io] = 1;
 }
-// code[i] = the proof's first bad point's verdict in the host's order, else 8 for a public input >= r, else 0; live[i] = 1 iff code[i] == 0
+// code[i] = proof_code of verdict_order.h; live[i] = 1 iff code[i] == 0
 __global__ void k_vk_status(const uint8_t* __restrict__ v1, const uint8_t* __restrict__ v2, const uint8_t* __restrict__ bad, uint32_t count, VkPlan p,
                             uint8_t* __restrict__ code, uint8_t* __restrict__ live) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    uint8_t c = 0;
-    for (uint32_t k = 0; k < p.norder && !c; k++) {
-        const uint8_t o = p.order[k];
-        c = o & 0x80 ? v2[(size_t)p.n2 * i + (o & 0x7f)] : v1[(size_t)p.n1 * i + o];
-    }
-    if (!c && bad[i]) c = VK_CODE_SCALAR;
+    const uint8_t c = proof_code(p, v1, v2, bad, i);
     code[i] = c;
     live[i] = c == 0 ? 1 : 0;
 }
@@ -211,30 +196,6 @@ static int vk_lookup(uint64_t handle, int protocol, ResidentVk** out) {
     if (protocol >= 0 && (*out)->protocol != protocol) ZK_FAIL(ZK_ERR_HANDLE, "the verification key handle belongs to the other protocol");
     return ZK_OK;
 }
-static int verdict_code(uint8_t v) { return v == 0 ? ZK_OK : v == 2 ? ZK_ERR_ARG : v == VK_CODE_SCALAR ? ZK_ERR_SCALAR_RANGE : ZK_ERR_NOT_ON_CURVE; }
-
-// n1 G1 and n2 G2 key points (host bytes) -> dense affine on the device + one verdict each (host)
-static int vk_decode_key(ResidentVk& k, const uint8_t* g1, uint64_t n1, const uint8_t* g2, uint64_t n2, std::vector<uint8_t>& v1, std::vector<uint8_t>& v2, hipStream_t s) {
-    v1.assign(n1, 0);
-    v2.assign(n2, 0);
-    DevBuf b1, b2, dv;
-    ZKCHK(b1.alloc(96 * n1));
-    ZKCHK(b2.alloc(192 * n2));
-    ZKCHK(k.key1.alloc(96 * n1));
-    ZKCHK(k.key2.alloc(192 * n2));
-    ZKCHK(dv.alloc(n1 + n2));
-    if (n1) HIPCHK(hipMemcpyAsync(b1.p, g1, 96 * n1, hipMemcpyHostToDevice, s));
-    if (n2) HIPCHK(hipMemcpyAsync(b2.p, g2, 192 * n2, hipMemcpyHostToDevice, s));
-    {
-        ScopedTimer t("verify_point_checks", s);
-        ZKCHK(points_decode_verdicts_endo(CURVE_G2, k.key2.p, b2.p, n2, dv.as<uint8_t>() + n1, s));
-        ZKCHK(points_decode_verdicts_endo(CURVE_G1, k.key1.p, b1.p, n1, dv.as<uint8_t>(), s));
-    }
-    if (n1) HIPCHK(hipMemcpyAsync(v1.data(), dv.p, n1, hipMemcpyDeviceToHost, s));
-    if (n2) HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + n1, n2, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return ZK_OK;
-}
 static int vk_install(std::unique_ptr<ResidentVk>& k, const uint8_t want[576], hipStream_t s, uint64_t* handle) {
     ZKCHK(k->want.alloc(576));
     HIPCHK(hipMemcpyAsync(k->want.p, want, 576, hipMemcpyHostToDevice, s));
@@ -285,8 +246,8 @@ static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proo
     hipLaunchKernelGGL(k_vk_gather, grid_for(n * (6 * p.n1 + 12 * p.n2), 256), dim3(256), 0, s, (const uint8_t*)d_in, c, p, k.b1.as<uint8_t>(), k.b2.as<uint8_t>());
     {
         ScopedTimer t("verify_point_checks", s);
-        ZKCHK(points_decode_verdicts_endo(CURVE_G2, k.a2.p, k.b2.p, p.n2 * n, v2, s));
-        ZKCHK(points_decode_verdicts_endo(CURVE_G1, k.a1.p, k.b1.p, p.n1 * n, v1, s));
+        ZKCHK(points_decode_verdicts(CURVE_G2, k.a2.p, k.b2.p, p.n2 * n, v2, SUBGROUP_ENDO, s));
+        ZKCHK(points_decode_verdicts(CURVE_G1, k.a1.p, k.b1.p, p.n1 * n, v1, SUBGROUP_ENDO, s));
     }
     if (sb) hipLaunchKernelGGL(k_vk_scalar_range, grid_for(k.n_io * n, 256), dim3(256), 0, s, d_sc, k.n_io * n, (uint32_t)k.n_io, bad);
     hipLaunchKernelGGL(k_vk_status, grid_for(n, 256), dim3(256), 0, s, (const uint8_t*)v1, (const uint8_t*)v2, (const uint8_t*)bad, c, p, code, live);
@@ -355,12 +316,9 @@ int zk_groth16_vk_upload(const uint8_t ab[576], const uint8_t* ltgm_io, size_t n
     memcpy(g2, gm, 192);
     memcpy(g2 + 192, d, 192);
     std::vector<uint8_t> v1, v2;
-    ZKCHK(vk_decode_key(*k, ltgm_io, n_io, g2, 2, v1, v2, s));
-    // the host's order (gm, d, ltgm_io), as zk_groth16_verify_many reports a key's defects
-    if (v2[0]) ZK_FAIL(verdict_code(v2[0]), "verify: bad G2 point");
-    if (v2[1]) ZK_FAIL(verdict_code(v2[1]), "verify: bad G2 point");
-    for (size_t q = 0; q < n_io; q++)
-        if (v1[q]) ZK_FAIL(verdict_code(v1[q]), "verify: bad G1 point in the key");
+    ZKCHK(points_decode_two_lists(ltgm_io, n_io, g2, 2, "verify_point_checks", SUBGROUP_ENDO, k->key1, k->key2, v1, v2, s));
+    const KeyDefect bad = groth16_key_defect(v1.data(), v2.data(), n_io);
+    if (bad.verdict) ZK_FAIL(verdict_code(bad.verdict), bad.what);
     if (n_io) ZKCHK(short_bases_create(&k->io[0], CURVE_G1, k->key1.p, n_io, s));
     return vk_install(k, ab, s, handle);
 }
@@ -375,24 +333,16 @@ int zk_pinocchio_vk_upload(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_
     k->protocol = 1;
     k->n_io = n_io;
     std::vector<uint8_t> v1, v2;
-    ZKCHK(vk_decode_key(*k, vk_g1, 3 + 2 * n_io, vk_g2, 6 + n_io, v1, v2, s));
-    // the host's order: one aw bgm | one2 av ay gm2 bgm2 yt | vv_io[k] yy_io[k] ww_io[k] for every k
-    for (size_t q = 0; q < 3; q++)
-        if (v1[q]) ZK_FAIL(verdict_code(v1[q]), "verify: bad G1 point");
-    for (size_t q = 0; q < 6; q++)
-        if (v2[q]) ZK_FAIL(verdict_code(v2[q]), "verify: bad G2 point");
-    for (size_t q = 0; q < n_io; q++) {
-        const uint8_t v = v1[3 + q] ? v1[3 + q] : v1[3 + n_io + q] ? v1[3 + n_io + q] : v2[6 + q];
-        if (v) ZK_FAIL(verdict_code(v), "verify: bad point in the key");
-    }
+    ZKCHK(points_decode_two_lists(vk_g1, 3 + 2 * n_io, vk_g2, 6 + n_io, "verify_point_checks", SUBGROUP_ENDO, k->key1, k->key2, v1, v2, s));
+    const KeyDefect bad = pinocchio_key_defect(v1.data(), v2.data(), n_io);
+    if (bad.verdict) ZK_FAIL(verdict_code(bad.verdict), bad.what);
     if (n_io) {
         ZKCHK(short_bases_create(&k->io[0], CURVE_G1, k->key1.as<uint8_t>() + 96 * 3, n_io, s));
         ZKCHK(short_bases_create(&k->io[1], CURVE_G1, k->key1.as<uint8_t>() + 96 * (3 + n_io), n_io, s));
         ZKCHK(short_bases_create(&k->io[2], CURVE_G2, k->key2.as<uint8_t>() + 192 * 6, n_io, s));
     }
     uint8_t gt_one[576];
-    memset(gt_one, 0, 576);
-    gt_one[47] = 1;
+    gt_one_bytes(gt_one);
     return vk_install(k, gt_one, s, handle);
 }
 
