@@ -459,6 +459,24 @@ int zk_groth16_verify_resident(uint64_t handle, const uint8_t* io_scalars /* cou
                                uint32_t count, uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
 int zk_pinocchio_verify_resident(uint64_t handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 960 */,
                                  uint32_t count, uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
+/* One answer for a whole batch under a resident Groth16 key: are ALL of these proofs good?  Instead of one pairing equation per proof (Groth16.verify,
+ * groth16.ml:163-173, as the reference's harness loops over it, test.ml:107-179) the equations are raised to coefficients rho_i and multiplied:
+ *     prod_i e([rho_i] A_i, B_i) . e(-sum_k t_k ltgm_io_k, gm) . e(-sum_i [rho_i] C_i, d) = ab^S,   t_k = sum_i rho_i w_ik (mod r),  S = sum_i rho_i
+ * -- per batch one final exponentiation, one product over the public inputs and two Miller loops; per proof one Miller loop, two 128-bit multiples in
+ * G1 and n_io multiply-adds in Fr.  status[i] is byte for byte what zk_groth16_verify_resident reports for proof i (the same decoder, subgroup and
+ * range tests, the same order); a proof with a non-zero status does not enter the fold (identity pairs, no rho).  *all_ok = 1 if and only if every
+ * status is 0 and the folded equation holds.  The per-proof call stays the way to learn WHICH proof is bad once this one has said that one is.
+ *   THE CONTRACT FOR rho.  The caller draws every rho_i (16 bytes, little-endian like the ABI's scalars, non-zero) from a cryptographic generator
+ *   AFTER the proofs are fixed, and keeps them unpredictable to whoever made the proofs.  A batch that holds a bad proof then passes with probability
+ *   at most 2^-128.  With rho known or chosen in advance a bad batch CAN pass: two proofs whose C are shifted by +D and -D cancel under equal
+ *   coefficients (tests/test_gpu_verify_folded.py shows it).  The library draws nothing itself: it has no generator to vouch for.
+ *   vk_handle: from zk_groth16_vk_upload.  Refused before the device is touched, with ZK_ERR_ARG: all_ok, proofs or rho null (count > 0), a zero
+ *   rho_i, count > 2^24.  Then a Pinocchio, freed or unknown handle -> ZK_ERR_HANDLE (a non-zero handle without a usable GPU: ZK_ERR_HIP, no handle
+ *   can exist); count = 0 -> ZK_OK, *all_ok = 1, nothing else touched; io_scalars null with n_io > 0 -> ZK_ERR_ARG.  More than 8192 proofs are
+ *   folded slab by slab into state kept on the device; the equation is decided once.  Kernel families: verify_point_checks, verify_fold_scale,
+ *   pairing_miller, verify_fold_tree, msm_short, pairing_final_exp, verify_fold_pow. */
+int zk_groth16_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 384 */,
+                             const uint8_t* rho /* count * 16 */, uint32_t count, int* all_ok, int32_t* status /* count, may be NULL */);
 
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------
  * With profiling on, kernel families are bracketed by HIP events on the stream they run on;
@@ -494,6 +512,12 @@ int zk_selftest_fp12(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8
  * run).  verdict[i] = 0 good (the identity included) | 2 bad encoding | 1 not on the curve | 4 on the curve, outside the subgroup.  A null pointer,
  * n = 0, another group or method -> ZK_ERR_ARG before the device is touched. */
 int zk_selftest_subgroup(int group, int method, const uint8_t* points, size_t n, uint8_t* verdict);
+/* zk_groth16_verify_folded stopped before the comparison (tests/test_gpu_verify_folded.py): both sides of the folded equation as GT encodings --
+ * lhs_gt the final exponentiation of the product of the count + 2 Miller values, rhs_gt = ab^S -- and the two sums that enter the key's pairs,
+ * sum_c = sum_i [rho_i] C_i and sum_io = sum_k t_k ltgm_io_k, un-negated, uncompressed (the identity as the library encodes it).  Same arguments and
+ * refusals as the call itself; count = 0 or a null output -> ZK_ERR_ARG. */
+int zk_selftest_groth16_fold(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count,
+                             uint8_t lhs_gt[576], uint8_t rhs_gt[576], uint8_t sum_c[96], uint8_t sum_io[96], int32_t* status);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -15,7 +15,8 @@
                 the key's bytes and a live handle in Lagrange form come back (a multi-device list: the bytes, then the ordinary upload)
      verify  groth16.ml:163-173 -> unchanged in substance: three pairings of the host's own Pairing
              verify_many (an extra): a list of proofs under one key -> one call zk_groth16_verify_many, the pairings on the device
-             Verifier (an extra): the key resident on the device, create / verify_many / free -> a call moves only proofs and public inputs
+             Verifier (an extra): the key resident on the device, create / verify_many / verify_all / free -> a call moves only proofs and public inputs;
+                       verify_all asks one folded pairing equation about the whole list
    The records and their yojson are the reference's (groth16.ml:24-43,110-114): the JSON of keys and proofs is the wire format. *)
 
 open Zukelang
@@ -327,6 +328,25 @@ module Make (C : Curve.S) = struct
       let proofs = Mi355x.cat (List.concat_map (fun (_, (p : proof)) -> [ G1.to_bytes p.a; G2.to_bytes p.b; G1.to_bytes p.c ]) jobs) in
       Mi355x.(check (zk_groth16_verify_resident t.handle (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
       List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
+
+    (* Are ALL of these proofs good?  One folded pairing equation for the list (zk_groth16_verify_folded) instead of one per proof: the loop of
+       test.ml:107-179 as one question.  The coefficients are drawn HERE, from `rng`, after the proofs are in hand: 16 bytes per proof, the low half of
+       an Fr.gen (uniform up to 2^-127), a zero drawn again.  `rng` must be unpredictable to whoever made the proofs -- a seeded test generator is
+       not; with known coefficients a bad list can be made to pass.  false: some proof is bad, and verify_many says which. *)
+    let verify_all rng (t : t) (jobs : (f Var.Map.t * proof) list) : bool =
+      List.iter (fun (io, _) -> assert (Var.Set.equal (Var.Map.domain io) t.domain)) jobs;
+      let count = List.length jobs in
+      let rec draw () =
+        let b = Bytes.sub (Fr.to_bytes (Fr.gen rng)) 0 16 in
+        if Bytes.equal b (Bytes.make 16 (Char.chr 0)) then draw () else b
+      in
+      let rho = Mi355x.cat (List.init count (fun _ -> draw ())) in
+      let io_all = fr_bytes (List.concat_map (fun (io, _) -> values io) jobs) in
+      let proofs = Mi355x.cat (List.concat_map (fun (_, (p : proof)) -> [ G1.to_bytes p.a; G2.to_bytes p.b; G1.to_bytes p.c ]) jobs) in
+      let all_ok = Ctypes.allocate Ctypes.int 0 in
+      Mi355x.(
+        check (zk_groth16_verify_folded t.handle (bytes_start io_all) (bytes_start proofs) (bytes_start rho) (u32 count) all_ok no_status));
+      Ctypes.( !@ ) all_ok <> 0
 
     let free (t : t) = Mi355x.vk_free t.handle
   end

@@ -301,6 +301,18 @@ let zk_groth16_verify_resident =
 let zk_pinocchio_verify_resident =
   fn "zk_pinocchio_verify_resident" (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
 
+(* One folded pairing equation for a whole list of proofs under a resident Groth16 key (include/zkmi355x.h, zk_groth16_verify_folded): rho holds 16
+   bytes per proof, non-zero, drawn AFTER the proofs are fixed and unpredictable to whoever made them.  all_ok: 1 iff every proof is good. *)
+let zk_groth16_verify_folded =
+  fn "zk_groth16_verify_folded"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ptr int @-> ptr int32_t @-> returning int)
+
+(* the same stopped before the comparison: both sides as GT bytes and the two sums as points (the test suite's hook) *)
+let zk_selftest_groth16_fold =
+  fn "zk_selftest_groth16_fold"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes
+   @-> ptr int32_t @-> returning int)
+
 let vk_free (h : Unsigned.UInt64.t) = ignore (zk_vk_free h)
 
 let groth16_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =

@@ -140,8 +140,17 @@ int points_decode_two_lists(const uint8_t* g1, uint64_t n1, const uint8_t* g2, u
                             std::vector<uint8_t>& v1, std::vector<uint8_t>& v2, hipStream_t s);
 // ---- what the resident verification keys (verify_resident.hip) take from the other units, all on device buffers
 // the two pairing kernels (pairing_dev.hip): product q = the checked dense affine pairs [d_off[q], d_off[q + 1]) -> 576 B of GT each; enqueues only
+static constexpr size_t PAIRING_RAW_BYTES = 672;          // one raw Miller value: 6 coefficients x 28 limbs (pairing_dev.hip holds it to f12::EW)
 size_t pairing_miller_bytes(uint64_t npairs);
 int pairing_products_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t npairs, const uint32_t* d_off, uint32_t count, uint32_t* d_miller, uint8_t* d_gt, hipStream_t s);
+// its two halves, and what the folded verifier adds between them: the product of n raw Miller values by a tree (d_a is overwritten, d_b holds
+// pairing_tree_scratch(n) values of pairing_miller_bytes(1) each; the one value left goes to d_out), and d_out = d_base^e for a GT encoding and the low
+// `bits` bits of the words at d_exp (*d_bad = 1: d_base is no element of Fp12).  Timer families pairing_miller, pairing_final_exp, verify_fold_tree, verify_fold_pow
+int pairing_miller_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t npairs, uint32_t* d_miller, hipStream_t s);
+int pairing_final_exp_device(const uint32_t* d_miller, const uint32_t* d_off, uint32_t count, uint8_t* d_gt, hipStream_t s);
+uint64_t pairing_tree_scratch(uint64_t n);
+int pairing_tree_product_device(uint32_t* d_a, uint32_t n, uint32_t* d_b, uint32_t* d_out, hipStream_t s);
+int pairing_gt_pow_device(const uint8_t* d_base, const uint32_t* d_exp, uint32_t bits, uint8_t* d_out, uint32_t* d_bad, hipStream_t s);
 // the short products of msm_resident.hip over a narrow table of n <= SHORT_BASES_MAX subgroup points: product i = sum_k scalars[i n + k] P_k as dense XYZZ,
 // the identity where d_live[i] == 0 (those scalars are not read).  The scalars must be canonical: the caller has checked them.  Enqueues only.
 struct ShortBases;

@@ -8,6 +8,8 @@
 //   sums over the public inputs                 the resident short products of msm_resident.hip: the key's points uploaded once per call, one product per proof
 //   Miller loops                                k_miller: one group of 8 lanes per PAIR (pairing_tower.cuh), inversion-free, 63 steps
 //   products + final exponentiations            k_final_exp: one group per PRODUCT multiplies its pairs' Miller values and raises to (p^12 - 1) / r
+//   one long product (the folded verifier)      k_gt_tree_mul: one group per RUN of GT_TREE_RUN raw Miller values, level after level until one is left;
+//                                               k_gt_pow: a GT encoding raised to an exponent read from device memory (square and multiply, both every bit)
 //
 // A batch is bound by latency, not by the multipliers: one G2 subgroup check is ~15 k base-field products on one lane, a Miller loop ~2.6 k and a
 // final exponentiation ~7 k per lane of a group, and every pair and product of the batch does them side by side (profiles/verify_many.json).
@@ -23,6 +25,7 @@
 namespace zk {
 
 static constexpr uint32_t F12_RAW_WORDS = f12::EW;          // a Miller value between the two kernels: 6 coefficients x 28 limbs
+static_assert(F12_RAW_WORDS * 4 == PAIRING_RAW_BYTES, "msm.cuh: the size of a raw Miller value");
 
 // pair g of n: P = g1[g], Q = g2[g] (dense affine, checked); out[g] = the conjugated Miller value, 1 when either point is the identity
 __global__ __launch_bounds__(64) void k_miller(const uint8_t* __restrict__ g1, const uint8_t* __restrict__ g2, uint32_t n, uint32_t* __restrict__ out) {
@@ -60,6 +63,49 @@ __global__ __launch_bounds__(64) void k_final_exp(const uint32_t* __restrict__ m
     f12::final_exp();
     f12::store_gt(gt + 576 * (size_t)gi, 0, live);
 }
+// One level of the product tree over raw Miller values: out[g] = in[R g] in[R g + 1] ... (a ragged last run is shorter), R = GT_TREE_RUN.  k_final_exp
+// multiplies a product's values in ONE group, serially: for thousands of values that loop would be the call; here every level is R - 1 dependent
+// products whatever n is.  Every group takes R - 1 steps (a short run multiplies by 1: chosen by sel, the barriers are the workgroup's).
+static constexpr uint32_t GT_TREE_RUN = 4;
+__global__ __launch_bounds__(64) void k_gt_tree_mul(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t nout = (n + GT_TREE_RUN - 1) / GT_TREE_RUN;
+    const uint32_t g = blockIdx.x * f12::GROUPS_PER_WAVE + threadIdx.x / f12::GROUP;
+    const bool live = g < nout;
+    const uint32_t gi = live ? g : nout - 1;
+    const uint32_t lo = gi * GT_TREE_RUN, len = n - lo < GT_TREE_RUN ? n - lo : GT_TREE_RUN;          // 1 <= len
+    const uint32_t k = f12::coef();
+    const f12::F12C one = f12::sel<1>(k == 0, fp2_zero(), fp2_one());
+    f12::load_raw(0, in + (size_t)F12_RAW_WORDS * lo);
+    for (uint32_t j = 1; j < GT_TREE_RUN; j++) {
+        const bool have = j < len;
+        const f12::F12C x = f12::sel<256>(!have, f12::ld<256>(in + (size_t)F12_RAW_WORDS * (have ? lo + j : lo) + k * f12::CW), one);
+        __syncthreads();
+        f12::st(f12::reg_cell(1, k), x);
+        __syncthreads();
+        f12::mul(0, 0, 1);
+    }
+    f12::store_raw(out + (size_t)F12_RAW_WORDS * gi, 0, live);
+}
+// out = base^e: base a GT encoding (576 B), e the low `bits` bits of the little-endian words at `e`, out a GT encoding.  Square and multiply from the top
+// bit; BOTH products are taken at every bit and the result is chosen by sel -- no branch on a bit of e (the rule of pairing_tower.cuh; the eight groups
+// of the one workgroup all compute the same power, group 0 writes it).  *bad |= 1 when a coefficient of base is >= p (the power is then of no use).
+__global__ __launch_bounds__(64) void k_gt_pow(const uint8_t* __restrict__ base, const uint32_t* __restrict__ e, uint32_t bits, uint8_t* __restrict__ out,
+                                               uint32_t* __restrict__ bad) {
+    const bool ok = f12::load_gt(2, base);
+    if (!ok) *bad = 1;                               // no barrier inside; every writer stores the same word
+    f12::set_one(0);
+    const uint32_t k = f12::coef();
+    for (uint32_t i = bits; i-- > 0;) {
+        const bool bit = (e[i >> 5] >> (i & 31)) & 1;
+        f12::mul(0, 0, 0);
+        f12::mul(1, 0, 2);
+        const f12::F12C x = f12::sel<256>(bit, f12::ld<256>(f12::reg_cell(0, k)), f12::ld<256>(f12::reg_cell(1, k)));
+        __syncthreads();
+        f12::st(f12::reg_cell(0, k), x);
+        __syncthreads();
+    }
+    f12::store_gt(out, 0, threadIdx.x / f12::GROUP == 0);
+}
 // zk_selftest_fp12: element g of n through the device functions above
 __global__ __launch_bounds__(64) void k_selftest_fp12(int op, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint32_t n, uint8_t* __restrict__ out, int* flag) {
     const uint32_t g = blockIdx.x * f12::GROUPS_PER_WAVE + threadIdx.x / f12::GROUP;
@@ -96,18 +142,46 @@ static constexpr uint32_t MAX_PROOFS = 1u << 24;          // 13 pairs each stay 
 // The two pairing kernels on buffers that are ALREADY on the device: npairs checked dense affine pairs (d_g1: 96 B each, d_g2: 192 B), product q = the
 // pairs [d_off[q], d_off[q + 1]) -> count GT encodings in d_gt (576 B each).  d_miller: F12_RAW_WORDS words per pair.  Enqueues, does not wait.
 size_t pairing_miller_bytes(uint64_t npairs) { return (size_t)F12_RAW_WORDS * 4 * npairs; }
-int pairing_products_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t npairs, const uint32_t* d_off, uint32_t count, uint32_t* d_miller, uint8_t* d_gt, hipStream_t s) {
+int pairing_miller_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t npairs, uint32_t* d_miller, hipStream_t s) {
     if (npairs >= ((uint64_t)1 << 31)) ZK_FAIL(ZK_ERR_ARG, "pairing products: too many pairs for one call");
-    if (npairs) {
-        ScopedTimer t("pairing_miller", s);
-        hipLaunchKernelGGL(k_miller, grid_for(npairs, f12::GROUPS_PER_WAVE), dim3(64), 0, s, d_g1, d_g2, (uint32_t)npairs, d_miller);
+    if (!npairs) return ZK_OK;
+    ScopedTimer t("pairing_miller", s);
+    hipLaunchKernelGGL(k_miller, grid_for(npairs, f12::GROUPS_PER_WAVE), dim3(64), 0, s, d_g1, d_g2, (uint32_t)npairs, d_miller);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+int pairing_final_exp_device(const uint32_t* d_miller, const uint32_t* d_off, uint32_t count, uint8_t* d_gt, hipStream_t s) {
+    ScopedTimer t("pairing_final_exp", s);
+    hipLaunchKernelGGL(k_final_exp, grid_for(count, f12::GROUPS_PER_WAVE), dim3(64), 0, s, d_miller, d_off, count, d_gt);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+int pairing_products_device(const uint8_t* d_g1, const uint8_t* d_g2, uint64_t npairs, const uint32_t* d_off, uint32_t count, uint32_t* d_miller, uint8_t* d_gt, hipStream_t s) {
+    ZKCHK(pairing_miller_device(d_g1, d_g2, npairs, d_miller, s));
+    return pairing_final_exp_device(d_miller, d_off, count, d_gt, s);
+}
+// The n >= 1 raw Miller values of d_a multiplied to ONE, written to d_out: levels of k_gt_tree_mul that alternate between d_a (overwritten) and d_b
+// (room for pairing_tree_scratch(n) values).  d_out may lie in neither.
+uint64_t pairing_tree_scratch(uint64_t n) { return (n + GT_TREE_RUN - 1) / GT_TREE_RUN; }
+int pairing_tree_product_device(uint32_t* d_a, uint32_t n, uint32_t* d_b, uint32_t* d_out, hipStream_t s) {
+    ScopedTimer t("verify_fold_tree", s);
+    const uint32_t* src = d_a;
+    bool into_b = true;
+    do {
+        const uint32_t nout = (n + GT_TREE_RUN - 1) / GT_TREE_RUN;
+        uint32_t* dst = nout == 1 ? d_out : into_b ? d_b : d_a;
+        hipLaunchKernelGGL(k_gt_tree_mul, grid_for(nout, f12::GROUPS_PER_WAVE), dim3(64), 0, s, src, n, dst);
         HIPCHK(hipGetLastError());
-    }
-    {
-        ScopedTimer t("pairing_final_exp", s);
-        hipLaunchKernelGGL(k_final_exp, grid_for(count, f12::GROUPS_PER_WAVE), dim3(64), 0, s, (const uint32_t*)d_miller, d_off, count, d_gt);
-        HIPCHK(hipGetLastError());
-    }
+        src = dst;
+        n = nout;
+        into_b = !into_b;
+    } while (n > 1);
+    return ZK_OK;
+}
+int pairing_gt_pow_device(const uint8_t* d_base, const uint32_t* d_exp, uint32_t bits, uint8_t* d_out, uint32_t* d_bad, hipStream_t s) {
+    ScopedTimer t("verify_fold_pow", s);
+    hipLaunchKernelGGL(k_gt_pow, dim3(1), dim3(64), 0, s, d_base, d_exp, bits, d_out, d_bad);
+    HIPCHK(hipGetLastError());
     return ZK_OK;
 }
 

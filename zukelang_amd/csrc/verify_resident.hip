@@ -18,6 +18,18 @@
 //              7 one D2H copy: ok | code
 // The verdicts are those of zk_*_verify_many byte for byte: the same decoder, the same order of checks, the same pairs into the same two kernels, and
 // a subgroup verdict that is the same predicate (tests/test_subgroup_criterion.py, tests/test_gpu_subgroup_endo.py).  Nothing here reads an option.
+//
+// zk_groth16_verify_folded answers ONE question about a batch -- are all of these proofs good? -- with one pairing equation instead of one per proof:
+// with a secret random rho_i per proof,
+//     prod_i e([rho_i] A_i, B_i) . e(-sum_k t_k ltgm_io_k, gm) . e(-sum_i [rho_i] C_i, d) = ab^S,    t_k = sum_i rho_i w_ik (mod r),  S = sum_i rho_i
+// Steps 1-3 above are shared (vk_slab_front: the statuses are those of the per-proof call); then, per slab, on proofs that are still live:
+//   k_fold_scale   [rho_i] A_i -> dense affine, [rho_i] C_i -> XYZZ: 128-bit double-and-add on the complete group law, one lane per point
+//   k_fold_sum     the [rho_i] C_i and the running sum -> one point, by trees of complete additions in LDS, level after level
+//   k_fold_fr      t_k += sum_i rho_i w_ik, S += sum_i rho_i, and the count of rejected proofs: one workgroup per k
+//   k_miller over the pairs ([rho_i] A_i, B_i), pairing_tree_product_device over their values and the running product
+// and once, after the last slab: one short product sum_k t_k ltgm_io_k, k_fold_key_pairs, k_miller on the two key pairs, k_final_exp on the product of
+// the three values, pairing_gt_pow_device for ab^S, k_fold_verdict, and one D2H copy (codes | all_ok).  The kernels know nothing of Groth16: they scale
+// and sum points, fold scalars and multiply Miller values; which points and which key pairs is decided in vk_fold.
 #include "ec.cuh"
 #include "handle_table.h"
 #include "msm.cuh"
@@ -163,6 +175,106 @@ __global__ void k_vk_compare(const uint8_t* __restrict__ gt, const uint8_t* __re
     ok[i] = diff ? 0 : 1;
 }
 
+// ------------------------------------------------------------------ the folded verifier's kernels
+// Lane j < count: point `pa` of item j -> [rho_j] P as dense affine in out_aff[j]; lane count + j: point `px` of item j -> [rho_j] P as dense XYZZ in
+// out_xyzz[j].  pts: per_item dense affine points per item; rho: four little-endian words per item.  Items that are not live give the identity (zero
+// bytes) and their points are not read.  xyzz_dbl / xyzz_madd are the complete ones: P may be the identity, and nothing is assumed of rho.
+__global__ __launch_bounds__(64) void k_fold_scale(const uint8_t* __restrict__ pts, uint32_t per_item, uint32_t pa, uint32_t px, const uint32_t* __restrict__ rho,
+                                                   const uint8_t* __restrict__ live, uint32_t count, uint8_t* __restrict__ out_aff, uint8_t* __restrict__ out_xyzz) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 2 * count) return;
+    const bool second = j >= count;
+    const uint32_t i = second ? j - count : j;
+    Xyzz<Fp> acc = xyzz_inf<Fp>();
+    if (live[i]) {
+        const Aff<Fp> P = aff_load<Fp>(pts + 96 * ((size_t)per_item * i + (second ? px : pa)));
+        const uint4 e = reinterpret_cast<const uint4*>(rho)[i];
+        const uint32_t w[4] = {e.x, e.y, e.z, e.w};
+        for (int b = 127; b >= 0; b--) {
+            acc = xyzz_dbl(acc);
+            if ((w[b >> 5] >> (b & 31)) & 1) xyzz_madd(acc, P);
+        }
+    }
+    if (second) xyzz_store<Fp>(out_xyzz + 192 * (size_t)i, acc);
+    else aff_store<Fp>(out_aff + 96 * (size_t)i, xyzz_to_aff(acc));
+}
+// out[blockIdx.x] = the sum of in[64 blockIdx.x ...] (dense XYZZ, at most 64 of the n): every lane takes one point (the identity past the end), then
+// the wave halves them in LDS.  The additions are the complete xyzz_add: equal summands (a proof repeated with the same rho) and opposite ones occur.
+static constexpr uint32_t FOLD_SUM_THREADS = 64;
+__global__ __launch_bounds__(FOLD_SUM_THREADS) void k_fold_sum(const uint8_t* __restrict__ in, uint32_t n, uint8_t* __restrict__ out) {
+    constexpr int XB = RawLayout<Fp>::XYZZ;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[FOLD_SUM_THREADS * XB];
+    const uint32_t t = threadIdx.x, i = blockIdx.x * FOLD_SUM_THREADS + t;
+    Xyzz<Fp> acc = xyzz_inf<Fp>();
+    if (i < n) acc = xyzz_load<Fp>(in + 192 * (size_t)i);
+    xyzz_store_raw(lds + XB * t, acc);
+    __syncthreads();
+    for (uint32_t h = FOLD_SUM_THREADS / 2; h > 0; h >>= 1) {          // the bound is the workgroup's: every lane meets every barrier
+        if (t < h) {
+            const Xyzz<Fp> q = xyzz_load_raw<Fp>(lds + XB * (t + h));
+            xyzz_add(acc, q);
+            xyzz_store_raw(lds + XB * t, acc);
+        }
+        __syncthreads();
+    }
+    if (t == 0) xyzz_store<Fp>(out + 192 * (size_t)blockIdx.x, acc);
+}
+// Workgroup k < n: t[k] += sum over the live items i of rho_i w[i n + k] (mod r); workgroup n: S += sum of the live rho_i (mod r; as an integer the sum
+// stays below 2^152 < r) and *dead += the items that are not live.  w: canonical scalars (a live item's are: the range test ran), t and S canonical too.
+static constexpr uint32_t FOLD_FR_THREADS = 256;
+__global__ __launch_bounds__(FOLD_FR_THREADS) void k_fold_fr(const uint32_t* __restrict__ w, uint32_t n, const uint32_t* __restrict__ rho, const uint8_t* __restrict__ live,
+                                                             uint32_t count, uint32_t* __restrict__ t, uint32_t* __restrict__ S, uint32_t* __restrict__ dead) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[FOLD_FR_THREADS * 8];
+    __shared__ uint32_t ndead;
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (lane == 0) ndead = 0;
+    __syncthreads();
+    Fr acc = fe_zero<FrParams>();
+    uint32_t mine = 0;
+    for (uint32_t i = lane; i < count; i += FOLD_FR_THREADS) {
+        if (!live[i]) { mine++; continue; }
+        const uint4 e = reinterpret_cast<const uint4*>(rho)[i];
+        Fr r = fe_zero<FrParams>();
+        r.v[0] = e.x; r.v[1] = e.y; r.v[2] = e.z; r.v[3] = e.w;
+        if (k < n) r = fe_mul(fe_to_mont(r), fe_load<FrParams>(w + 8 * ((size_t)n * i + k)));          // (rho R) w R^-1 = rho w
+        acc = fe_add(acc, r);
+    }
+    if (k == n && mine) atomicAdd(&ndead, mine);
+    fe_store(lds + 8 * lane, acc);
+    __syncthreads();
+    for (uint32_t h = FOLD_FR_THREADS / 2; h > 0; h >>= 1) {
+        if (lane < h) {
+            acc = fe_add(acc, fe_load<FrParams>(lds + 8 * (lane + h)));
+            fe_store(lds + 8 * lane, acc);
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        uint32_t* dst = k < n ? t + 8 * (size_t)k : S;
+        fe_store(dst, fe_add(acc, fe_load<FrParams>(dst)));
+        if (k == n) *dead += ndead;
+    }
+}
+// The two pairs of the key's side, (-p[0], key2[0]) and (-p[1], key2[1]), for two dense XYZZ points p -> q1 (2 x 96 B), q2 (2 x 192 B), and the offsets
+// of ONE product over the three Miller values that lie together (the running product, then these two).
+__global__ __launch_bounds__(64) void k_fold_key_pairs(const uint8_t* __restrict__ p, const uint8_t* __restrict__ key2, uint8_t* __restrict__ q1, uint8_t* __restrict__ q2,
+                                                       uint32_t* __restrict__ off) {
+    const uint32_t i = threadIdx.x;
+    if (i >= 2) return;
+    aff_store<Fp>(q1 + 96 * i, g1_negated(xyzz_to_aff(xyzz_load<Fp>(p + 192 * i))));
+    copy_point<192>(q2 + 192 * i, key2 + 192 * i);
+    off[i] = 3 * i;
+}
+// *all_ok = 1 iff no item was rejected, `want` was an element of Fp12 and the 576 bytes of both sides agree
+__global__ void k_fold_verdict(const uint8_t* __restrict__ lhs, const uint8_t* __restrict__ rhs, const uint32_t* __restrict__ dead, const uint32_t* __restrict__ bad,
+                               uint8_t* __restrict__ all_ok) {
+    if (threadIdx.x) return;
+    uint32_t diff = *dead | *bad;
+    const uint4 *a = reinterpret_cast<const uint4*>(lhs), *b = reinterpret_cast<const uint4*>(rhs);
+    for (int k = 0; k < 36; k++) diff |= (a[k].x ^ b[k].x) | (a[k].y ^ b[k].y) | (a[k].z ^ b[k].z) | (a[k].w ^ b[k].w);
+    *all_ok = diff ? 0 : 1;
+}
+
 // ================================================================== host side
 struct ResidentVk {
     int protocol = 0;                         // 0 Groth16, 1 Pinocchio
@@ -173,13 +285,31 @@ struct ResidentVk {
     // workspaces for `cap` proofs
     uint32_t cap = 0;
     DevBuf in, b1, b2, a1, a2, verdict, flags, sums, q1, q2, off, miller, gt;
-    uint8_t* host = nullptr;                  // pinned: [proofs | scalars] in, [ok | code] out
+    uint8_t* host = nullptr;                  // pinned: [proofs | scalars | rho] in, [ok | code | all_ok] out
     size_t host_bytes = 0;
+    // the folded verifier (Groth16): workspaces for `fold_cap` proofs, and the state a call carries from slab to slab
+    uint32_t fold_cap = 0;
+    DevBuf fa, fc, fsum, fm, fm2, fold;       // [rho] A dense affine | [rho] C and the running sum, XYZZ | partial sums | Miller values | tree levels | FoldState
     ~ResidentVk() {
         for (ShortBases* b : io) short_bases_free(b);
         if (host) (void)hipHostFree(host);
     }
 };
+// Where the folded call's state lies in ResidentVk::fold (offsets in bytes; everything from F_SUMS on is zeroed when a call begins)
+enum : size_t {
+    F_MILLER = 0,                             // three raw Miller values: the running product, then the two key pairs'
+    F_SUMS = 3 * PAIRING_RAW_BYTES,                            // two XYZZ points in the order of key2 = gm | d: sum t_k ltgm_io_k | sum [rho_i] C_i
+    F_SUM_C = F_SUMS + 192,
+    F_S = F_SUMS + 384,                       // S, 32 B
+    F_OFF = F_S + 32,                         // the offsets of the one product: 0, 3
+    F_DEAD = F_OFF + 8,                       // rejected proofs so far
+    F_BAD = F_DEAD + 4,                       // 1: `want` is no element of Fp12
+    F_ONE = F_BAD + 4,                        // a `live` byte for the one short product (16 B with its padding)
+    F_GT = F_ONE + 16,                        // lhs | rhs, 576 B each
+    F_BYTES = F_GT + 1152,                    // the two sums in the ABI's encoding, 96 B each
+    F_T = F_BYTES + 192,                      // t: n_io x 32 B
+};
+static_assert(F_SUMS % 16 == 0 && F_T % 16 == 0, "the state's points and scalars are read 16 bytes at a time");
 static const VkPlan& plan_of(const ResidentVk& k) { return k.protocol == 0 ? PLAN_GROTH16 : PLAN_PINOCCHIO; }
 
 // a range of its own (handle_table.h); like resident bases, a live verification key pins the device list
@@ -208,7 +338,9 @@ static int vk_reserve(ResidentVk& k, uint32_t c, hipStream_t s) {
     if (c <= k.cap) return ZK_OK;
     HIPCHK(hipStreamSynchronize(s));
     const VkPlan& p = plan_of(k);
-    const size_t n = c, in_bytes = ((size_t)p.stride + 32 * k.n_io) * n, out_bytes = 2 * n;
+    // what the folded call adds (Groth16 keys only; a Pinocchio key's workspaces are what they were): 16 B of rho per proof, all_ok behind the codes
+    const size_t fold = k.protocol == 0 ? 1 : 0;
+    const size_t n = c, in_bytes = ((size_t)p.stride + 32 * k.n_io + 16 * fold) * n, out_bytes = 2 * n + 16 * fold;
     const uint32_t nsum1 = k.protocol == 0 ? 1 : 2, nsum2 = k.protocol == 0 ? 0 : 1;
     k.cap = 0;
     ZKCHK(k.in.alloc(in_bytes));
@@ -217,7 +349,7 @@ static int vk_reserve(ResidentVk& k, uint32_t c, hipStream_t s) {
     ZKCHK(k.a1.alloc(96 * p.n1 * n));
     ZKCHK(k.a2.alloc(192 * p.n2 * n));
     ZKCHK(k.verdict.alloc((p.n1 + p.n2) * n));
-    ZKCHK(k.flags.alloc(4 * n));              // scalar-range byte | live | ok | code
+    ZKCHK(k.flags.alloc(4 * n + 16 * fold));  // scalar-range byte | live | ok | code (| all_ok)
     ZKCHK(k.sums.alloc((192 * nsum1 + 384 * nsum2) * n));
     ZKCHK(k.q1.alloc(96 * p.pairs * n));
     ZKCHK(k.q2.alloc(192 * p.pairs * n));
@@ -232,16 +364,42 @@ static int vk_reserve(ResidentVk& k, uint32_t c, hipStream_t s) {
     return ZK_OK;
 }
 
-// proofs [0, c) of a slab: everything of the file's header, steps 1-7
-static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t c, uint8_t* ok, int32_t* status, hipStream_t s) {
+// The workspaces of the folded call on top of vk_reserve's
+static int vk_reserve_fold(ResidentVk& k, uint32_t c, hipStream_t s) {
+    ZKCHK(vk_reserve(k, c, s));
+    if (!k.fold.p) ZKCHK(k.fold.alloc(F_T + 32 * k.n_io));
+    if (c <= k.fold_cap) return ZK_OK;
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t n = c, nsum = (n + FOLD_SUM_THREADS) / FOLD_SUM_THREADS;          // partial sums of n + 1 points
+    k.fold_cap = 0;
+    ZKCHK(k.fa.alloc(96 * n));
+    ZKCHK(k.fc.alloc(192 * (n + 1)));
+    ZKCHK(k.fsum.alloc(192 * (nsum + (nsum + FOLD_SUM_THREADS - 1) / FOLD_SUM_THREADS)));
+    ZKCHK(k.fm.alloc(pairing_miller_bytes(n + 1)));
+    ZKCHK(k.fm2.alloc(pairing_miller_bytes(pairing_tree_scratch(n + 1))));
+    k.fold_cap = c;
+    return ZK_OK;
+}
+
+// where the front half of a slab leaves its results
+struct SlabFront {
+    size_t pb, sb;                            // bytes of the proofs and of the public inputs in k.in and k.host
+    const uint32_t *d_sc, *d_rho;             // the public inputs and the folded call's rho on the device
+    uint8_t *bad, *live, *d_ok, *code;        // k.flags
+};
+// proofs [0, c) of a slab, steps 1-3 of the file's header: the H2D copy (rho behind the public inputs when the folded call brings one), the decoder,
+// the subgroup and range tests, one code and one live byte per proof
+static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t c, SlabFront& f, hipStream_t s) {
     const VkPlan& p = plan_of(k);
-    const size_t n = c, pb = (size_t)p.stride * n, sb = 32 * k.n_io * n;
+    const size_t n = c, pb = (size_t)p.stride * n, sb = 32 * k.n_io * n, rb = rho ? 16 * n : 0;
     memcpy(k.host, proofs, pb);
     if (sb) memcpy(k.host + pb, io_scalars, sb);
-    HIPCHK(hipMemcpyAsync(k.in.p, k.host, pb + sb, hipMemcpyHostToDevice, s));
-    uint8_t *d_in = k.in.as<uint8_t>(), *bad = k.flags.as<uint8_t>(), *live = bad + n, *d_ok = bad + 2 * n, *code = bad + 3 * n;
+    if (rb) memcpy(k.host + pb + sb, rho, rb);
+    HIPCHK(hipMemcpyAsync(k.in.p, k.host, pb + sb + rb, hipMemcpyHostToDevice, s));
+    uint8_t *d_in = k.in.as<uint8_t>(), *bad = k.flags.as<uint8_t>(), *live = bad + n, *code = bad + 3 * n;
     uint8_t *v1 = k.verdict.as<uint8_t>(), *v2 = v1 + p.n1 * n;
     const uint32_t* d_sc = reinterpret_cast<const uint32_t*>(d_in + pb);
+    f = SlabFront{pb, sb, d_sc, reinterpret_cast<const uint32_t*>(d_in + pb + sb), bad, live, bad + 2 * n, code};
     HIPCHK(hipMemsetAsync(bad, 0, n, s));
     hipLaunchKernelGGL(k_vk_gather, grid_for(n * (6 * p.n1 + 12 * p.n2), 256), dim3(256), 0, s, (const uint8_t*)d_in, c, p, k.b1.as<uint8_t>(), k.b2.as<uint8_t>());
     {
@@ -252,6 +410,18 @@ static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proo
     if (sb) hipLaunchKernelGGL(k_vk_scalar_range, grid_for(k.n_io * n, 256), dim3(256), 0, s, d_sc, k.n_io * n, (uint32_t)k.n_io, bad);
     hipLaunchKernelGGL(k_vk_status, grid_for(n, 256), dim3(256), 0, s, (const uint8_t*)v1, (const uint8_t*)v2, (const uint8_t*)bad, c, p, code, live);
     HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+
+// proofs [0, c) of a slab: everything of the file's header, steps 1-7
+static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t c, uint8_t* ok, int32_t* status, hipStream_t s) {
+    const VkPlan& p = plan_of(k);
+    const size_t n = c;
+    SlabFront f;
+    ZKCHK(vk_slab_front(k, io_scalars, proofs, nullptr, c, f, s));
+    const size_t pb = f.pb, sb = f.sb;
+    const uint32_t* d_sc = f.d_sc;
+    uint8_t *live = f.live, *d_ok = f.d_ok;
     // the sums over the public inputs: dense XYZZ, zero bytes = the identity (n_io = 0)
     uint8_t* sum[3] = {k.sums.as<uint8_t>(), k.sums.as<uint8_t>() + 192 * n, k.sums.as<uint8_t>() + 384 * n};
     const int nsums = k.protocol == 0 ? 1 : 3;
@@ -294,6 +464,106 @@ static int vk_verify(uint64_t handle, int protocol, const uint8_t* io_scalars, c
     for (uint32_t lo = 0; lo < count; lo += VK_SLAB) {
         const uint32_t c = count - lo < VK_SLAB ? count - lo : VK_SLAB;
         ZKCHK(vk_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, c, ok + lo, status ? status + lo : nullptr, s));
+    }
+    return ZK_OK;
+}
+
+// One slab of the folded call: the front half, then the slab's share of both sides folded into the state
+static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t c, bool first, bool last, int32_t* status,
+                        uint8_t* all_ok, hipStream_t s) {
+    const size_t n = c;
+    SlabFront f;
+    ZKCHK(vk_slab_front(k, io_scalars, proofs, rho, c, f, s));
+    uint8_t* st = k.fold.as<uint8_t>();
+    uint32_t* run = reinterpret_cast<uint32_t*>(st + F_MILLER);
+    {
+        ScopedTimer t("verify_fold_scale", s);
+        // a1 = A | C per proof
+        hipLaunchKernelGGL(k_fold_scale, grid_for(2 * n, 64), dim3(64), 0, s, (const uint8_t*)k.a1.as<uint8_t>(), 2u, 0u, 1u, f.d_rho, (const uint8_t*)f.live, c,
+                           k.fa.as<uint8_t>(), k.fc.as<uint8_t>());
+        HIPCHK(hipMemcpyAsync(k.fc.as<uint8_t>() + 192 * n, st + F_SUM_C, 192, hipMemcpyDeviceToDevice, s));          // the running sum rides along
+        const uint8_t* src = k.fc.as<uint8_t>();
+        uint8_t* part[2] = {k.fsum.as<uint8_t>(), k.fsum.as<uint8_t>() + 192 * ((n + FOLD_SUM_THREADS) / FOLD_SUM_THREADS)};
+        int lvl = 0;
+        for (uint32_t m = c + 1;; lvl ^= 1) {
+            const uint32_t blocks = (m + FOLD_SUM_THREADS - 1) / FOLD_SUM_THREADS;
+            uint8_t* dst = blocks == 1 ? st + F_SUM_C : part[lvl];
+            hipLaunchKernelGGL(k_fold_sum, dim3(blocks), dim3(FOLD_SUM_THREADS), 0, s, src, m, dst);
+            if (blocks == 1) break;
+            src = dst;
+            m = blocks;
+        }
+        hipLaunchKernelGGL(k_fold_fr, dim3((unsigned)k.n_io + 1), dim3(FOLD_FR_THREADS), 0, s, f.d_sc, (uint32_t)k.n_io, f.d_rho, (const uint8_t*)f.live, c,
+                           reinterpret_cast<uint32_t*>(st + F_T), reinterpret_cast<uint32_t*>(st + F_S), reinterpret_cast<uint32_t*>(st + F_DEAD));
+        HIPCHK(hipGetLastError());
+    }
+    // the pairs ([rho_i] A_i, B_i).  A rejected proof's A is the identity here (k_fold_scale), and k_miller writes 1 for a pair with an identity on
+    // either side whatever the other holds: its loop has no inversion and no branch on data.  Such a proof's B is what the decoder left -- the identity
+    // for a bad encoding or a point off the curve, else a point of the curve, possibly outside the subgroup -- never bytes that are no point
+    ZKCHK(pairing_miller_device(k.fa.as<uint8_t>(), k.a2.as<uint8_t>(), n, k.fm.as<uint32_t>(), s));
+    if (!first) HIPCHK(hipMemcpyAsync(k.fm.as<uint8_t>() + pairing_miller_bytes(n), run, pairing_miller_bytes(1), hipMemcpyDeviceToDevice, s));
+    ZKCHK(pairing_tree_product_device(k.fm.as<uint32_t>(), c + (first ? 0 : 1), k.fm2.as<uint32_t>(), run, s));
+    size_t out = n;
+    if (last) {
+        // sum_k t_k ltgm_io_k (zero bytes, the identity, when n_io = 0), the key's two pairs, the one final exponentiation, ab^S, the comparison
+        if (k.n_io) ZKCHK(short_bases_run(*k.io[0], reinterpret_cast<const uint32_t*>(st + F_T), st + F_ONE, 1, st + F_SUMS, s));
+        hipLaunchKernelGGL(k_fold_key_pairs, dim3(1), dim3(64), 0, s, (const uint8_t*)(st + F_SUMS), (const uint8_t*)k.key2.as<uint8_t>(), k.q1.as<uint8_t>(),
+                           k.q2.as<uint8_t>(), reinterpret_cast<uint32_t*>(st + F_OFF));
+        HIPCHK(hipGetLastError());
+        ZKCHK(pairing_miller_device(k.q1.as<uint8_t>(), k.q2.as<uint8_t>(), 2, run + pairing_miller_bytes(1) / 4, s));
+        ZKCHK(pairing_final_exp_device(run, reinterpret_cast<const uint32_t*>(st + F_OFF), 1, st + F_GT, s));
+        ZKCHK(pairing_gt_pow_device(k.want.as<uint8_t>(), reinterpret_cast<const uint32_t*>(st + F_S), 160, st + F_GT + 576, reinterpret_cast<uint32_t*>(st + F_BAD), s));
+        hipLaunchKernelGGL(k_fold_verdict, dim3(1), dim3(64), 0, s, (const uint8_t*)(st + F_GT), (const uint8_t*)(st + F_GT + 576), reinterpret_cast<const uint32_t*>(st + F_DEAD),
+                           reinterpret_cast<const uint32_t*>(st + F_BAD), f.code + n);
+        HIPCHK(hipGetLastError());
+        out = n + 1;
+    }
+    uint8_t* h_out = k.host + f.pb + f.sb + 16 * n;
+    HIPCHK(hipMemcpyAsync(h_out, f.code, out, hipMemcpyDeviceToHost, s));          // codes | all_ok
+    HIPCHK(hipStreamSynchronize(s));
+    if (status)
+        for (uint32_t i = 0; i < c; i++) status[i] = verdict_code(h_out[i]);
+    if (last) *all_ok = h_out[n];
+    return ZK_OK;
+}
+
+// zk_groth16_verify_folded and zk_selftest_groth16_fold: `debug` = lhs 576 | rhs 576 | sum_io 96 | sum_c 96, or null
+static int vk_fold(uint64_t handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status, uint8_t* debug) {
+    // what needs no handle comes first: these are refused before the table or the device is looked at
+    if (!all_ok) ZK_FAIL(ZK_ERR_ARG, "verify_folded: null argument");
+    if (count > VK_MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "verify_folded: more than 2^24 proofs in one call");
+    if (count && (!proofs || !rho)) ZK_FAIL(ZK_ERR_ARG, "verify_folded: null argument");
+    for (uint32_t i = 0; i < count; i++) {
+        uint8_t any = 0;
+        for (int b = 0; b < 16; b++) any |= rho[16 * (size_t)i + b];
+        if (!any) ZK_FAIL(ZK_ERR_ARG, "verify_folded: a coefficient rho_i is zero");
+    }
+    ResidentVk* kp;
+    if (handle && !g_vk.find(handle)) ZKCHK(ensure_init());          // without a device no handle exists: say that, not that this one is unknown
+    ZKCHK(vk_lookup(handle, 0, &kp));
+    if (!count) {
+        *all_ok = 1;
+        return ZK_OK;
+    }
+    ResidentVk& k = *kp;
+    if (k.n_io && !io_scalars) ZK_FAIL(ZK_ERR_ARG, "verify_folded: null argument");
+    DeviceScope ds(0);
+    hipStream_t s = ctx().stream;
+    ZKCHK(vk_reserve_fold(k, count < VK_SLAB ? count : VK_SLAB, s));
+    uint8_t* st = k.fold.as<uint8_t>();
+    HIPCHK(hipMemsetAsync(st + F_SUMS, 0, F_T + 32 * k.n_io - F_SUMS, s));
+    HIPCHK(hipMemsetAsync(st + F_ONE, 1, 1, s));
+    uint8_t verdict = 0;
+    for (uint32_t lo = 0; lo < count; lo += VK_SLAB) {
+        const uint32_t c = count - lo < VK_SLAB ? count - lo : VK_SLAB;
+        ZKCHK(vk_fold_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + 384 * (size_t)lo, rho + 16 * (size_t)lo, c, lo == 0, lo + c == count,
+                           status ? status + lo : nullptr, &verdict, s));
+    }
+    *all_ok = verdict;
+    if (debug) {
+        ZKCHK(points_xyzz_to_bytes_dev(CURVE_G1, st + F_SUMS, 2, st + F_BYTES, s));
+        HIPCHK(hipMemcpyAsync(debug, st + F_GT, 1152 + 192, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
     }
     return ZK_OK;
 }
@@ -367,5 +637,20 @@ int zk_groth16_verify_resident(uint64_t handle, const uint8_t* io_scalars, const
 }
 int zk_pinocchio_verify_resident(uint64_t handle, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
     return vk_verify(handle, 1, io_scalars, proofs, count, ok, status);
+}
+int zk_groth16_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status) {
+    return vk_fold(vk_handle, io_scalars, proofs, rho, count, all_ok, status, nullptr);
+}
+int zk_selftest_groth16_fold(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, uint8_t lhs_gt[576],
+                             uint8_t rhs_gt[576], uint8_t sum_c[96], uint8_t sum_io[96], int32_t* status) {
+    if (!count || !lhs_gt || !rhs_gt || !sum_c || !sum_io) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_groth16_fold: null argument or no proofs");
+    uint8_t out[1152 + 192];
+    int all_ok = 0;
+    ZKCHK(vk_fold(vk_handle, io_scalars, proofs, rho, count, &all_ok, status, out));
+    memcpy(lhs_gt, out, 576);
+    memcpy(rhs_gt, out + 576, 576);
+    memcpy(sum_io, out + 1152, 96);
+    memcpy(sum_c, out + 1248, 96);
+    return ZK_OK;
 }
 }

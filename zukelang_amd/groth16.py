@@ -17,6 +17,7 @@ An unsatisfied witness raises AssertionError like `assert (Polynomial.is_zero re
 (csrc/pairing_host.hip), as the reference's does in its external library.
 """
 import ctypes as C
+import secrets
 from dataclasses import dataclass
 
 import numpy as np
@@ -54,6 +55,14 @@ class PKey:
     lag_g2: np.ndarray = None
 
 
+def _draw_rho():
+    """16 bytes from the operating system's generator as a little-endian integer; a zero is drawn again"""
+    r = 0
+    while not r:
+        r = int.from_bytes(secrets.token_bytes(16), "little")
+    return r
+
+
 class ResidentVKey:
     """A verification key decoded and checked ONCE and kept on the device (include/zkmi355x.h, "verification keys resident on the device";
     csrc/verify_resident.hip): what VKey.resident() returns, for Groth16 and Pinocchio alike.  verify_many gives the lists Groth16.verify_many /
@@ -62,13 +71,14 @@ class ResidentVKey:
     def __init__(self, handle, n_io, proof_bytes, proof_len, call):
         self.handle, self.n_io, self._proof_bytes, self._proof_len, self._call = handle, n_io, proof_bytes, proof_len, call
 
-    def verify_many(self, input_outputs, proofs, return_status=False):
+    def _batch(self, what, input_outputs, proofs):
+        """The checks of the object itself, before the library sees anything: (count, public inputs, proofs) as two byte arrays."""
         if not self.handle:
-            raise ValueError("verify_many: the resident key is closed")
+            raise ValueError("%s: the resident key is closed" % what)
         proofs = list(proofs)
         input_outputs = list(input_outputs)
         if len(input_outputs) != len(proofs):
-            raise ValueError("verify_many: need one list of public inputs per proof")
+            raise ValueError("%s: need one list of public inputs per proof" % what)
         ios = []
         for io in input_outputs:
             io = bytes(io if isinstance(io, (bytes, bytearray, np.ndarray)) else fr_bytes(list(io)))
@@ -76,12 +86,45 @@ class ResidentVKey:
                 raise AssertionError("Variable not found")          # var.ml:75-77 / curve.ml:96-100: domains must agree
             ios.append(io)
         count = len(proofs)
-        ok = np.zeros(max(count, 1), dtype=np.uint8)
-        status = np.zeros(max(count, 1), dtype=np.int32)
         io_all = np.frombuffer(b"".join(ios), dtype=np.uint8)
         pr_all = np.frombuffer(b"".join(self._proof_bytes(p) for p in proofs), dtype=np.uint8)
         if len(pr_all) != self._proof_len * count:
-            raise ValueError("verify_many: a proof is not %d bytes" % self._proof_len)
+            raise ValueError("%s: a proof is not %d bytes" % (what, self._proof_len))
+        return count, io_all, pr_all
+
+    def verify_all(self, input_outputs, proofs, rho=None, return_status=False):
+        """Are ALL of these proofs good?  One folded pairing equation for the batch (zk_groth16_verify_folded) instead of one per proof: True, or False
+        when any proof is bad -- verify_many then says which.  rho: one non-zero 128-bit coefficient per proof.  Leave it None: 16 bytes per proof are
+        then drawn from `secrets` here, after the proofs are fixed.  A caller that passes its own takes over the contract of include/zkmi355x.h -- drawn
+        after the proofs are fixed, unpredictable to whoever made them -- without which a bad batch can be made to pass.  Groth16 keys only."""
+        if self._call != "zk_groth16_verify_resident":
+            raise NotImplementedError("verify_all: the folded check exists for Groth16 keys only; this is a Pinocchio key (use verify_many)")
+        count, io_all, pr_all = self._batch("verify_all", input_outputs, proofs)
+        if rho is None:
+            rho = [_draw_rho() for _ in range(count)]
+        rho = [int(r) for r in rho]
+        if len(rho) != count or any(not 0 < r < 1 << 128 for r in rho):
+            raise ValueError("verify_all: need one coefficient 0 < rho < 2^128 per proof")
+        rho_all = np.frombuffer(b"".join(r.to_bytes(16, "little") for r in rho), dtype=np.uint8)
+        all_ok = C.c_int(0)
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        _lib.check(_lib.lib().zk_groth16_verify_folded(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
+                                                       _p(rho_all) if count else None, C.c_uint32(count), C.byref(all_ok),
+                                                       status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return (bool(all_ok.value), [int(x) for x in status[:count]]) if return_status else bool(all_ok.value)
+
+    def verify_many(self, input_outputs, proofs, return_status=False, fold_first=False):
+        """fold_first: ask verify_all first (rho drawn here) and answer all-true when it says so; only a batch that holds a bad proof pays for the
+        per-proof call as well.  Off by default: the call is then exactly the per-proof one."""
+        if fold_first:
+            if self._call != "zk_groth16_verify_resident":
+                raise NotImplementedError("verify_many(fold_first=True): the folded check exists for Groth16 keys only; this is a Pinocchio key")
+            proofs, input_outputs = list(proofs), list(input_outputs)
+            if self.verify_all(input_outputs, proofs):
+                return ([True] * len(proofs), [0] * len(proofs)) if return_status else [True] * len(proofs)
+        count, io_all, pr_all = self._batch("verify_many", input_outputs, proofs)
+        ok = np.zeros(max(count, 1), dtype=np.uint8)
+        status = np.zeros(max(count, 1), dtype=np.int32)
         _lib.check(getattr(_lib.lib(), self._call)(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
                                                    C.c_uint32(count), _p(ok), status.ctypes.data_as(C.POINTER(C.c_int32))))
         res = [bool(x) for x in ok[:count]]
