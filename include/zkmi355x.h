@@ -512,6 +512,24 @@ int zk_selftest_fp12(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8
  * run).  verdict[i] = 0 good (the identity included) | 2 bad encoding | 1 not on the curve | 4 on the curve, outside the subgroup.  A null pointer,
  * n = 0, another group or method -> ZK_ERR_ARG before the device is touched. */
 int zk_selftest_subgroup(int group, int method, const uint8_t* points, size_t n, uint8_t* verdict);
+/* Every form of the device's group law on bare operands (tests/test_gpu_group_law.py), each run by a kernel of the translation unit that builds the
+ * form for production, with that unit's flags.  group 0 = G1, 1 = G2 (on lane pairs).  a[i]: an XYZZ point as four field elements x, y, zz, zzz
+ * (x_affine = x / zz, y_affine = y / zzz, zz^3 = zzz^2; zz = 0 is the identity whatever x and y are), each 48 B big-endian -- in G2 96 B, imaginary
+ * part | real part -- so the caller chooses the representation.  b[i] by form: a second XYZZ point | an affine point x, y (all zeros = the identity,
+ * where the form accepts it) | ignored (may be null) | a canonical scalar of 32 B, little-endian.  out[i]: the result, uncompressed, the identity as
+ * the library encodes it.
+ *   form  0 xyzz_add_impl          b XYZZ      4 xyzz_madd_impl, identity q allowed  b affine     11 xyzz_add_slots   b XYZZ
+ *         1 xyzz_dbl_impl          -           5 xyzz_madd_impl, table entries       b affine     12 xyzz_dbl_slots   -
+ *         2 xyzz_dbl_aff (a has                (never the identity)                               13 jac_dbl          -
+ *           zz = zzz = 1, or is                6 xyzz_mmadd_impl (a has zz = zzz = 1 b affine     14 jac_madd         b affine, never the identity
+ *           the identity)          -             or is the identity)                              15 jac_add          b XYZZ
+ *         3 xyzz_add_raw_mem       b XYZZ      7, 8, 9 = 4, 5, 6 with the field products expanded in place        16 xyzz_mul_scalar_endo  b scalar
+ *                                              10 xyzz_madd_parked (G2 only), table entries       b affine
+ * rep 0: the coordinates enter the form canonical.  rep 1: the kernel first lifts every operand to x + k p, the largest k its type in the form's
+ * production caller admits (csrc/group_selftest.cuh lists them), so that the form's zero tests see multiples of p.
+ * A null pointer, n = 0, an unknown group / form / rep, a coordinate >= p, an identity b where the form excludes it -> ZK_ERR_ARG; a scalar >= r ->
+ * ZK_ERR_SCALAR_RANGE; all before the device is touched. */
+int zk_selftest_group(int group, int form, int rep, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
 /* zk_groth16_verify_folded stopped before the comparison (tests/test_gpu_verify_folded.py): both sides of the folded equation as GT encodings --
  * lhs_gt the final exponentiation of the product of the count + 2 Miller values, rhs_gt = ab^S -- and the two sums that enter the key's pairs,
  * sum_c = sum_i [rho_i] C_i and sum_io = sum_k t_k ltgm_io_k, un-negated, uncompressed (the identity as the library encodes it).  Same arguments and

@@ -19,6 +19,7 @@
 #include "endo_consts.cuh"
 #include "frstage.cuh"
 #include "msm.cuh"
+#include "group_selftest.cuh"
 
 #include <type_traits>
 
@@ -659,6 +660,46 @@ int derive_shifted_bases_g1(const FrStage& f, const uint8_t* d_si, uint8_t* d_ou
     DeriveTables tn;
     ZKCHK(derive_tables_build(tn, f, f.n, s));
     return derive_set<Fp>(tn, d_si, f.n - 1, d_out, s);
+}
+
+// ------------------------------------------------------------------ zk_selftest_group, forms 13-16 (group_selftest.cuh)
+// One lane (G1) or lane pair (G2) per pair of operands.  An XYZZ operand becomes the Jacobian point (X ZZ, Y ZZZ, ZZ), as window_table_affine takes its
+// multiplicand; a Jacobian result leaves through jac_to_xyzz.  The scalar multiplication gets the 16 raw XYZZ points of scratch per multiplication
+// that the butterflies give it.
+template <class T> FF_INLINE Jac<T> st_jac_from_xyzz(const Xyzz<T>& p) { return {T(fe_mul(p.x, p.zz)), T(fe_mul(p.y, p.zzz)), p.zz}; }
+template <class T> FF_INLINE void group_selftest_derive_body(int form, int rep, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n, uint8_t* __restrict__ out,
+                                                             uint8_t* __restrict__ scratch) {
+    constexpr int XB = RawLayout<T>::XYZZ, CB = StGeom<T>::CB;
+    const uint64_t i = st_index<T>();
+    if (i >= n) return;
+    const bool lift = rep != 0;
+    const Xyzz<T> p = st_load_xyzz<T>(a, i, lift);
+    Xyzz<T> r;
+    if (form == GROUP_FORM_MUL) {
+        r = xyzz_mul_scalar_endo(p, reinterpret_cast<const uint32_t*>(b) + 8 * i, scratch + (uint64_t)16 * XB * i);
+    } else {
+        Jac<T> acc = st_jac_from_xyzz(p);
+        if (form == GROUP_FORM_JAC_DBL) acc = jac_dbl(acc);
+        else if (form == GROUP_FORM_JAC_MADD) {
+            const uint8_t* q = b + (uint64_t)2 * CB * i;
+            jac_madd(acc, st_coord<2>((const T*)nullptr, q, lift), st_coord<4>((const T*)nullptr, q + CB, lift));
+        } else {
+            const Jac<T> q = st_jac_from_xyzz(st_load_xyzz<T>(b, i, lift));
+            jac_add(acc, q);
+        }
+        r = jac_to_xyzz(acc);
+    }
+    st_store_xyzz<T>(out, i, r);
+}
+template <class T> __global__ __launch_bounds__(128, (std::is_same<T, Fp>::value ? 2 : ZK_DERIVE_G2_WAVES)) void k_group_selftest_derive(int form, int rep, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n, uint8_t* __restrict__ out, uint8_t* __restrict__ scratch) {
+    group_selftest_derive_body<T>(form, rep, a, b, n, out, scratch);
+}
+int group_selftest_derive(const GroupSelftest& t, hipStream_t s) {
+    if (t.form < GROUP_FORM_JAC_DBL || t.form > GROUP_FORM_MUL) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_group: this unit builds forms 13-16");
+    if (t.curve == CURVE_G1) hipLaunchKernelGGL(k_group_selftest_derive<Fp>, g1d(t.n, 128), dim3(128), 0, s, t.form, t.rep, t.d_a, t.d_b, t.n, t.d_out, t.d_scratch);
+    else hipLaunchKernelGGL(k_group_selftest_derive<Fp2H>, g1d(2 * t.n, 128), dim3(128), 0, s, t.form, t.rep, t.d_a, t.d_b, t.n, t.d_out, t.d_scratch);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
 }
 
 }  // namespace zk

@@ -164,6 +164,43 @@ int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n
 // n ZCash-COMPRESSED points (host, 48 / 96 B) -> uncompressed (host, 96 / 192 B): square roots, curve and subgroup checks on the device (msm_points.hip)
 int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, hipStream_t s);
 int points_selftest_sqrt(int field, const uint8_t* a, uint64_t n, uint8_t* root, uint8_t* is_square, hipStream_t s);          // zk_selftest_sqrt
+// ---- zk_selftest_group: every form of the group law on bare operands, one kernel per translation unit that builds the form (group_selftest.cuh says
+// why and what the buffers hold).  The numbers are the `form` argument of the C-ABI.
+enum GroupForm {
+    GROUP_FORM_ADD = 0,                 // xyzz_add_impl, the second operand in the word form block_tree_sum exchanges             msm_red.hip
+    GROUP_FORM_DBL = 1,                 // xyzz_dbl_impl                                                                            msm_red.hip
+    GROUP_FORM_DBL_AFF = 2,             // xyzz_dbl_aff on (x, y) of a (zz = zzz = 1, or the identity)                              msm_red.hip
+    GROUP_FORM_ADD_RAW_MEM = 3,         // xyzz_add_raw_mem, b written to device memory in the raw layout by a launch of its own    msm_red.hip
+    GROUP_FORM_MADD = 4,                // xyzz_madd_impl<F, true>, products out of line (the raw-point accumulate of both curves)  msm_acc_g2.hip
+    GROUP_FORM_MADD_NOINF = 5,          // xyzz_madd_impl<F, false>, q a table entry: never the identity                            msm_acc_g2.hip
+    GROUP_FORM_MMADD = 6,               // xyzz_mmadd_impl<F, true>: a is affine (zz = zzz = 1) or the identity                     msm_acc_g2.hip
+    GROUP_FORM_MADD_INLINE = 7,         // forms 4-6 with the products expanded in place               G1: msm_acc_g1.hip, G2: msm_acc_g2i.hip
+    GROUP_FORM_MADD_NOINF_INLINE = 8,
+    GROUP_FORM_MMADD_INLINE = 9,
+    GROUP_FORM_MADD_PARKED = 10,        // xyzz_madd_parked with its LDS park buffer: G2 only, q a table entry                      msm_acc_g2i.hip
+    GROUP_FORM_ADD_SLOTS = 11,          // xyzz_add_slots, one point per group of 4 (G1) / 8 (G2) lanes                             msm_tail.hip
+    GROUP_FORM_DBL_SLOTS = 12,          // xyzz_dbl_slots                                                                           msm_tail.hip
+    GROUP_FORM_JAC_DBL = 13,            // jac_dbl on the Jacobian point (X ZZ, Y ZZZ, ZZ)                                          lagrange_derive.hip
+    GROUP_FORM_JAC_MADD = 14,           // jac_madd, q affine and never the identity                                               lagrange_derive.hip
+    GROUP_FORM_JAC_ADD = 15,            // jac_add, both operands converted in the kernel                                          lagrange_derive.hip
+    GROUP_FORM_MUL = 16,                // xyzz_mul_scalar_endo (window_table_affine, GLV / GLS split, signed windows), b a scalar  lagrange_derive.hip
+    GROUP_FORM_COUNT = 17
+};
+// d_a: n XYZZ operands, d_b: n second operands (XYZZ / affine / scalars by form), d_out: n dense XYZZ results; d_scratch: per-form working memory
+// (group_selftest_scratch_bytes).  Enqueue only; the unit refuses (ZK_ERR_ARG) a form it does not build.
+struct GroupSelftest {
+    Curve curve;
+    int form, rep;
+    const uint8_t *d_a, *d_b;
+    uint64_t n;
+    uint8_t *d_out, *d_scratch;
+};
+int group_selftest_acc_g1(const GroupSelftest& t, hipStream_t s);        // msm_acc_g1.hip: forms 7-9 in G1
+int group_selftest_acc_g2(const GroupSelftest& t, hipStream_t s);        // msm_acc_g2.hip: forms 4-6, both curves
+int group_selftest_acc_g2i(const GroupSelftest& t, hipStream_t s);       // msm_acc_g2i.hip: forms 7-10 in G2
+int group_selftest_red(const GroupSelftest& t, hipStream_t s);           // msm_red.hip: forms 0-3
+int group_selftest_tail(const GroupSelftest& t, hipStream_t s);          // msm_tail.hip: forms 11, 12
+int group_selftest_derive(const GroupSelftest& t, hipStream_t s);        // lagrange_derive.hip: forms 13-16
 // out[i] = scalars[i] * G (affine Montgomery on device); scalars canonical on device
 int fixed_base_mul(Curve curve, void* d_affine_out, const void* d_scalars, uint64_t n, hipStream_t s);
 // acc[i] = sum_j parts[j*stride + i] over j < count   (XYZZ, tiny: cross-GPU partial reduction)

@@ -4,6 +4,7 @@
 // 64 KB instruction cache shared by a CU pair.
 #define ZK_FP_INLINE_MUL 1
 #include "msm_acc.cuh"
+#include "group_selftest.cuh"
 
 #include <stdlib.h>
 
@@ -16,6 +17,17 @@ int msm_accumulate_launch_g1(uint64_t nthreads, const void* table, const AccJobs
     if (glds && !mm) hipLaunchKernelGGL((k_msm_accumulate<Fp, false, true, false>), dim3((unsigned)((nthreads + 127) / 128), count), dim3(128), 0, s, (const uint8_t*)table, jobs, nb, chunk);
     else if (glds) hipLaunchKernelGGL((k_msm_accumulate<Fp, false, true>), dim3((unsigned)((nthreads + 127) / 128), count), dim3(128), 0, s, (const uint8_t*)table, jobs, nb, chunk);
     else hipLaunchKernelGGL((k_msm_accumulate<Fp, false, false>), dim3((unsigned)((nthreads + 127) / 128), count), dim3(128), 0, s, (const uint8_t*)table, jobs, nb, chunk);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// zk_selftest_group, forms 7-9 in G1: the three mixed additions as this unit builds them (products and the zero test's slow path expanded in place),
+// one lane per pair of operands.  The equal-x case leaves through xyzz_madd_equal_x, out of line, as in the bucket loop.
+__global__ __launch_bounds__(128) void k_group_selftest_acc_g1(int form, int rep, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n, uint8_t* __restrict__ out) {
+    st_acc_forms<Fp>(form, rep, a, b, n, out);
+}
+int group_selftest_acc_g1(const GroupSelftest& t, hipStream_t s) {
+    if (t.curve != CURVE_G1 || t.form < GROUP_FORM_MADD_INLINE || t.form > GROUP_FORM_MMADD_INLINE) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_group: this unit builds forms 7-9 in G1");
+    hipLaunchKernelGGL(k_group_selftest_acc_g1, grid_for(t.n, 128), dim3(128), 0, s, t.form, t.rep, t.d_a, t.d_b, t.n, t.d_out);
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }

@@ -11,6 +11,7 @@
 #endif
 #include "ec.cuh"
 #include "msm_tail.cuh"
+#include "group_selftest.cuh"
 
 #include <stdlib.h>
 
@@ -220,6 +221,55 @@ int msm_red_digit_sums_launch(const TailJobs& jobs, uint32_t count, uint32_t n2,
     else if (wg == 16) ZK_DS_LAUNCH(16);
     else hipLaunchKernelGGL((k_msm_digit_sums<0, 1>), gd, dim3(DS_THREADS), 0, s, jobs, dp);          // the narrow form (small keys: latency-bound) stays at one wave
 #undef ZK_DS_LAUNCH
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------ zk_selftest_group, forms 0-3 (group_selftest.cuh)
+// One lane (G1) or lane pair (G2) per pair of operands, as the kernels above hold their points.  Form 0 takes the second operand in the word form
+// block_tree_sum exchanges (xyzz_to_words / xyzz_from_words: the limbs as they are, no reduction); form 3 reads it from device memory in the raw layout,
+// where stage 0 -- a launch of its own, as the accumulate kernel is for the fix-up -- wrote it with its lazily reduced limbs.
+static constexpr int ST_RED_THREADS = 128;
+template <class T> FF_INLINE void group_selftest_red_body(int form, int rep, int stage, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n, uint8_t* __restrict__ out,
+                                                          uint8_t* __restrict__ raw) {
+    constexpr int XB = RawLayout<T>::XYZZ;
+    const uint64_t i = st_index<T>();
+    if (i >= n) return;
+    const bool lift = rep != 0;
+    if (stage == 0) {
+        xyzz_store_raw<T>(raw + (uint64_t)XB * i, st_load_xyzz<T>(b, i, lift));
+        return;
+    }
+    Xyzz<T> acc = st_load_xyzz<T>(a, i, lift);
+    if (form == GROUP_FORM_ADD) {
+        uint32_t tmp[LANE_POINT_WORDS];
+        xyzz_to_words(tmp, st_load_xyzz<T>(b, i, lift));
+        Xyzz<T> q;
+        xyzz_from_words(q, tmp);
+        xyzz_add_impl(acc, q);
+    } else if (form == GROUP_FORM_DBL) {
+        acc = xyzz_dbl_impl(acc);
+    } else if (form == GROUP_FORM_DBL_AFF) {
+        Aff<T> p = aff_inf<T>();
+        if (!xyzz_is_inf(acc)) p = {acc.x, acc.y};
+        acc = xyzz_dbl_aff(p);
+    } else {
+        xyzz_add_raw_mem<T>(acc, raw + (uint64_t)XB * i);
+    }
+    st_store_xyzz<T>(out, i, acc);
+}
+__global__ __launch_bounds__(ST_RED_THREADS) void k_group_selftest_red(int g2, int form, int rep, int stage, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n,
+                                                                       uint8_t* __restrict__ out, uint8_t* __restrict__ raw) {
+    if (!g2) group_selftest_red_body<Fp>(form, rep, stage, a, b, n, out, raw);
+    else group_selftest_red_body<Fp2H>(form, rep, stage, a, b, n, out, raw);
+}
+int group_selftest_red(const GroupSelftest& t, hipStream_t s) {
+    if (t.form < GROUP_FORM_ADD || t.form > GROUP_FORM_ADD_RAW_MEM) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_group: this unit builds forms 0-3");
+    const int g2 = t.curve == CURVE_G2 ? 1 : 0;
+    const dim3 grid = grid_for(t.n * (g2 ? 2 : 1), ST_RED_THREADS);
+    if (t.form == GROUP_FORM_ADD_RAW_MEM)
+        hipLaunchKernelGGL(k_group_selftest_red, grid, dim3(ST_RED_THREADS), 0, s, g2, t.form, t.rep, 0, t.d_a, t.d_b, t.n, t.d_out, t.d_scratch);
+    hipLaunchKernelGGL(k_group_selftest_red, grid, dim3(ST_RED_THREADS), 0, s, g2, t.form, t.rep, 1, t.d_a, t.d_b, t.n, t.d_out, t.d_scratch);
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }

@@ -12,6 +12,7 @@
 // through the QAP products): only the association order of the additions differs.
 #include "msm_tail.cuh"
 #include "ec_slots.cuh"
+#include "group_selftest.cuh"
 
 namespace zk {
 
@@ -314,6 +315,39 @@ int msm_tail_weight_slots(const TailJobs& jobs, uint32_t count, uint32_t n2, uin
         ScopedTimer t4("msm_reduce:final", s);
         hipLaunchKernelGGL(k_tail_windows, dim3(1, 1, count), dim3(64), 0, s, jobs, nwin, c, B0 + B1);
     }
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------ zk_selftest_group, forms 11 and 12 (group_selftest.cuh)
+// One point per group of four slots (4 lanes in G1, 8 in G2), whole groups only; consecutive pairs of operands sit in consecutive groups of a wave, so the
+// groups of one wave take different branches of the law when the caller mixes its cases.  Slot s reads coordinate s of a and, as add_from_memory does,
+// coordinates s and s ^ 2 of b.
+template <class T> FF_INLINE void group_selftest_tail_body(int form, int rep, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n, uint8_t* __restrict__ out) {
+    constexpr uint32_t G = SlotGeom<T>::G;
+    constexpr int CB = StGeom<T>::CB;
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    if (i >= n) return;                                     // whole groups: G divides the workgroup
+    const bool lift = rep != 0;
+    const uint32_t sl = slot_id<T>();
+    T own = st_coord<ST_REST>((const T*)nullptr, a + (uint64_t)4 * CB * i + CB * sl, lift);
+    if (form == GROUP_FORM_ADD_SLOTS) {
+        const T qs = st_coord<ST_REST>((const T*)nullptr, b + (uint64_t)4 * CB * i + CB * sl, lift);
+        const T qx = st_coord<ST_REST>((const T*)nullptr, b + (uint64_t)4 * CB * i + CB * (sl ^ 2), lift);
+        xyzz_add_slots(own, qs, qx);
+    } else {
+        own = xyzz_dbl_slots(own);
+    }
+    store_f(out + (uint64_t)4 * CB * i + CB * sl, own);
+}
+__global__ __launch_bounds__(64) void k_group_selftest_tail(int g2, int form, int rep, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n, uint8_t* __restrict__ out) {
+    if (!g2) group_selftest_tail_body<Fp>(form, rep, a, b, n, out);
+    else group_selftest_tail_body<Fp2H>(form, rep, a, b, n, out);
+}
+int group_selftest_tail(const GroupSelftest& t, hipStream_t s) {
+    if (t.form != GROUP_FORM_ADD_SLOTS && t.form != GROUP_FORM_DBL_SLOTS) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_group: this unit builds forms 11 and 12");
+    const int g2 = t.curve == CURVE_G2 ? 1 : 0;
+    hipLaunchKernelGGL(k_group_selftest_tail, grid_for(t.n * (g2 ? 8 : 4), 64), dim3(64), 0, s, g2, t.form, t.rep, t.d_a, t.d_b, t.n, t.d_out);
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
