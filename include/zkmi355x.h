@@ -409,7 +409,7 @@ int zk_groth16_verify(const uint8_t ab[576], const uint8_t* ltgm_io /* n_io * 96
 int zk_pinocchio_verify(const uint8_t* vk_g1, const uint8_t* vk_g2, const uint8_t* io_scalars, size_t n_io,
                         const uint8_t proof[960], int* ok);
 
-/* ---- the same three on the device, many per call (zukelang_amd/csrc/pairing_dev.hip) ---------------------
+/* ---- the same three on the device, many per call (zukelang_amd/csrc/pairing_dev.hip: the products; zukelang_amd/csrc/verify_resident.hip: the verifiers)
  * The calls above cost one host core milliseconds to tens of milliseconds each; a host that checks a stream of proofs hands them over in batches instead.  All three run on
  * the first device of the list, are synchronous, keep nothing after they return, check their arguments before they touch the device and return
  * ZK_ERR_HIP where there is none: the device path has no CPU fallback.  A lone proof is quicker through the host calls (profiles/verify_many.json).
@@ -423,20 +423,29 @@ int zk_pairing_product_many(const uint8_t* g1_points, const uint8_t* g2_points, 
  * point fails the call with that function's code.  A proof's own defects never do: ok[i] = its *ok, status[i] = the code the single-proof call
  * would return for proof i under this key -- ZK_OK; ZK_ERR_ARG / ZK_ERR_NOT_ON_CURVE for the first bad point of the proof in the order A, B, C;
  * ZK_ERR_SCALAR_RANGE for a public input >= r -- and ok[i] = 0 whenever status[i] != 0.  status may be NULL.  count = 0: ZK_OK, nothing touched.
- * A malformed ab compares unequal to every product, as on the host: every ok[i] = 0. */
+ * A malformed ab compares unequal to every product, as on the host: every ok[i] = 0.
+ *   What runs is the pipeline of the resident keys below, on a key that lives for this call: the key's points are decoded and checked, its IO points
+ *   become narrow window tables (one per 8192 points: n_io has no limit), and per slab of proofs one H2D copy (proofs | public inputs), every proof
+ *   point decoded and checked once, the statuses, one short product per proof and table, the three pairs per proof assembled on the device, Miller
+ *   loops, final exponentiations, the comparison with ab, and one D2H copy (ok | status).  The key's points and the first slab's proof points are
+ *   checked side by side, on two streams of the device.  The key is in no handle table and is gone, with its workspaces, when the call returns:
+ *   the call keeps nothing.  The subgroup test of every point is [r] P = O.  Kernel families under
+ *   zk_profile_get: pairing_point_checks, msm_short, pairing_miller, pairing_final_exp. */
 int zk_groth16_verify_many(const uint8_t ab[576], const uint8_t* ltgm_io, size_t n_io, const uint8_t gm[192], const uint8_t d[192],
                            const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 384 */, uint32_t count,
                            uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
 /* Pinocchio Verify.f (pinocchio.ml:254-420) of `count` proofs under one key, vk_g1 / vk_g2 as for zk_pinocchio_verify; ok and status as above, the
- * points of a proof in the order vv, ww, yy, h, vavv, waww, yayy, bvwy. */
+ * points of a proof in the order vv, ww, yy, h, vavv, waww, yayy, bvwy.  The same pipeline on a key that lives for the call: three short products per
+ * proof and table (vv_io, yy_io in G1, ww_io in G2), vio + vv, yio + yy and wio + ww added on the device, thirteen pairs in five products per proof,
+ * each compared with 1.  The same kernel families. */
 int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_io,
                              const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 960 */, uint32_t count,
                              uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
 
 /* ---- verification keys resident on the device (zukelang_amd/csrc/verify_resident.hip) ----------------------
  * A verifier checks a stream of proofs under ONE key (Groth16.verify, groth16.ml:163-173; Verify.f, pinocchio.ml:254-420), and the key's points pass
- * of_bytes_exn once when the key is read (curve.ml:199-212), not once per proof.  The _many calls above decode and check the key in every call; a
- * handle does it once, at upload, and keeps on the device: gm and d (Pinocchio: the nine fixed key points) as decoded points, the IO points as a
+ * of_bytes_exn once when the key is read (curve.ml:199-212), not once per proof.  The _many calls above build the key, and allocate its workspaces,
+ * in every call; a handle does it once, at upload, and keeps on the device: gm and d (Pinocchio: the nine fixed key points) as decoded points, the IO points as a
  * narrow window table for one short product per proof, the 576 bytes of ab as given, and workspaces that grow on demand and are reused.  A verify
  * call then costs one H2D copy (proofs | public inputs), the kernels and one D2H copy (ok | status).
  *   Upload: the key laid out as for zk_groth16_verify / zk_pinocchio_verify.  Every point is checked (encoding: ZK_ERR_ARG; curve and subgroup:

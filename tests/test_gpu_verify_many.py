@@ -1,6 +1,6 @@
-"""zk_groth16_verify_many / zk_pinocchio_verify_many (csrc/pairing_dev.hip) against the single-proof host verifiers: keys and proofs made by the
-ORACLE, good and defective entries in one batch, and for every entry the `ok` and the status code that zk_groth16_verify / zk_pinocchio_verify
-return for it alone.  Then the Python surface on proofs the GPU prover made in the same test."""
+"""zk_groth16_verify_many / zk_pinocchio_verify_many (csrc/verify_resident.hip: a resident key that lives for one call) against the single-proof host
+verifiers: keys and proofs made by the ORACLE, good and defective entries in one batch, and for every entry the `ok` and the status code that
+zk_groth16_verify / zk_pinocchio_verify return for it alone.  Then the Python surface on proofs the GPU prover made in the same test."""
 import ctypes as C
 
 import numpy as np
@@ -140,8 +140,8 @@ def test_groth16_with_no_or_one_public_input(n_io):
 
 
 def test_groth16_with_seventy_four_public_inputs():
-    """A random R1CS whose statement has 74 public values: the sums over the public inputs are longer than the 64 scalars up to which a G2 list
-    takes the resident bases' short path, and there are as many batches of them as proofs."""
+    """A random R1CS whose statement has 74 public values: one short product of 74 scalars per proof over the key's narrow table, a changed scalar in
+    the middle of one and a scalar >= r at the end of another."""
     cs, w = RC.random_r1cs(48, 256, 4)
     assert int((cs.mid == 0).sum()) >= 70
     key, ios, proofs = g16_oracle(cs, [w, w, w], 0x5EED0074)
@@ -152,6 +152,27 @@ def test_groth16_with_seventy_four_public_inputs():
     assert host == [(0, 1), (0, 0), (ZK_ERR_SCALAR_RANGE, 0)]
     rc, ok, st = g16_many(key, io_b, proofs)
     assert rc == 0 and ok == [1, 0, 0] and st == [0, 0, ZK_ERR_SCALAR_RANGE]
+
+
+@pytest.mark.parametrize("n_io", [8192, 8193])
+def test_groth16_with_as_many_public_inputs_as_one_narrow_table_holds_and_one_more(n_io):
+    """The batched call takes any number of public inputs; a resident key refuses more than 8192 (tests/test_verify_resident_surface.py).  Built like
+    the test above: ltgm_io[k] = [t] G1 below index 8192 and [t2] G1 from there on, w_k = k + 1, ab = e(G1, G2)^(a b - g sum_k w_k t_k - c dd): a sum
+    that reads a wrong point or a wrong scalar is another sum.  ONE host call per size: the host's sum over 8193 points takes seconds."""
+    a, b, c, dd, t, t2, g = 11, 13, 17, 19, 23, 37, 29
+    g1 = lambda k: P.g1_to_bytes(P.pt_mul(P.G1, k % R))
+    g2 = lambda k: P.g2_to_bytes(P.pt_mul(P.G2, k % R))
+    w = [k + 1 for k in range(n_io)]
+    dot = sum(wk * (t if k < 8192 else t2) for k, wk in enumerate(w))
+    ab = host_pairing(g1(a * b - g * dot - c * dd), g2(1))
+    key = (ab, g1(t) * min(n_io, 8192) + g1(t2) * (n_io - min(n_io, 8192)), g2(g), g2(dd))
+    io = frs(w)
+    good = g1(a) + g2(b) + g1(c)
+    proofs = [good, g1(2 * a) + g2(b * pow(2, -1, R)) + g1(c), g1(a) + g2(b) + g1(c + 1), good]
+    ios = [io, io, io, io[:-32] + R.to_bytes(32, "little")]
+    assert g16_host(key, ios[0], proofs[0]) == (0, 1)
+    rc, ok, st = g16_many(key, ios, proofs)
+    assert rc == 0 and ok == [1, 1, 0, 0] and st == [0, 0, 0, ZK_ERR_SCALAR_RANGE]
 
 
 # ------------------------------------------------------------------------------------------------------------------ Pinocchio
@@ -243,6 +264,23 @@ def test_pinocchio_bad_key_fails_the_call_with_the_hosts_code(pinocchio_batch):
         assert want in (ZK_ERR_ARG, ZK_ERR_NOT_ON_CURVE)
         assert pin_many(k1, k2, ios, proofs)[0] == want
     assert pin_host(bad_vv, bad_ww, ios[0], proofs[0])[0] == (ZK_ERR_ARG if n_io > 1 else ZK_ERR_NOT_ON_CURVE)
+
+
+@pytest.mark.parametrize("n_io", [2, 8193])
+def test_pinocchio_hand_built_with_two_and_with_8193_public_inputs(n_io):
+    """tests/pinocchio_handbuilt.py: the sums over the public inputs in G1 AND in G2 over more points than one narrow table holds.  At two public inputs
+    the host verifier is asked as well (tests/test_pairing_host.py holds the construction to it without a GPU); at 8193 the expected verdicts are the
+    construction's: a host call would take three sums over 8193 points."""
+    import pinocchio_handbuilt as H
+    vk1, vk2 = H.key(n_io)
+    w = H.public_inputs(n_io)
+    good = H.proof(n_io)
+    ios = [frs(w), frs(w[:-1] + [w[-1] + 1]), frs(w)]
+    proofs = [good, good, H.ww_off_the_curve(good)]
+    if n_io == 2:
+        assert [pin_host(vk1, vk2, i, p) for i, p in zip(ios, proofs)] == [(0, 1), (0, 0), (ZK_ERR_NOT_ON_CURVE, 0)]
+    rc, ok, st = pin_many(vk1, vk2, ios, proofs)
+    assert rc == 0 and ok == [1, 0, 0] and st == [0, 0, ZK_ERR_NOT_ON_CURVE]
 
 
 # ------------------------------------------------------------------------------------------------------------------ through the Python surface

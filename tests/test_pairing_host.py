@@ -148,3 +148,22 @@ def test_pinocchio_verify_accepts_the_oracle_proof_and_rejects_changes():
     assert not verify(bytes(bad), io)
     bad_io = list(io); bad_io[0] = (bad_io[0] + 1) % P.R
     assert not verify(proof, bad_io)
+
+
+def test_pinocchio_verify_accepts_the_hand_built_key_and_proof():
+    """tests/pinocchio_handbuilt.py at two public inputs: the construction the GPU tests run at 8193, where no host call is made."""
+    import pinocchio_handbuilt as H
+    vk1, vk2 = H.key(2)
+    io = H.public_inputs(2)
+
+    def verify(pr, io_vals):
+        ok = C.c_int(-1)
+        rc = _lib.lib().zk_pinocchio_verify(vk1, vk2, frs(io_vals), C.c_size_t(2), pr, C.byref(ok))
+        return rc, ok.value
+
+    assert verify(H.proof(2), io) == (0, 1)
+    assert O.pinocchio_verify(vk1, vk2, io, H.proof(2))                # the oracle agrees
+    assert verify(H.proof(2), [io[0], io[1] + 1]) == (0, 0)
+    assert verify(H.proof(2), [io[1], io[0]]) == (0, 0)                # the two IO points of every list differ: the inputs swapped are another sum
+    assert verify(H.proof(2, [5, 9]), [5, 9]) == (0, 1)
+    assert verify(H.ww_off_the_curve(H.proof(2)), io)[0] == -2         # ZK_ERR_NOT_ON_CURVE

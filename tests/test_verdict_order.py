@@ -1,5 +1,5 @@
-"""csrc/verdict_order.h on the CPU: the order in which the verifiers meet the points of a proof and of a key, written once for the host loops of
-zk_*_verify_many, the kernel k_vk_status of the resident keys and both upload functions.
+"""csrc/verdict_order.h on the CPU: the order in which the verifiers meet the points of a proof and of a key, written once for the kernel
+k_vk_status and the two key builders of csrc/verify_resident.hip, which the resident keys' uploads and the zk_*_verify_many calls share.
 
 tests/host/verdict_order_main.cpp includes only that header; it is built here as a stand-alone program with g++ under AddressSanitizer + UBSan and run
 (nothing is loaded into Python).  Against lists written out in the program it checks each plan's order (Groth16: A B C; Pinocchio: vv ww yy h vavv waww

@@ -151,16 +151,15 @@ int pairing_final_exp_device(const uint32_t* d_miller, const uint32_t* d_off, ui
 uint64_t pairing_tree_scratch(uint64_t n);
 int pairing_tree_product_device(uint32_t* d_a, uint32_t n, uint32_t* d_b, uint32_t* d_out, hipStream_t s);
 int pairing_gt_pow_device(const uint8_t* d_base, const uint32_t* d_exp, uint32_t bits, uint8_t* d_out, uint32_t* d_bad, hipStream_t s);
-// the short products of msm_resident.hip over a narrow table of n <= SHORT_BASES_MAX subgroup points: product i = sum_k scalars[i n + k] P_k as dense XYZZ,
-// the identity where d_live[i] == 0 (those scalars are not read).  The scalars must be canonical: the caller has checked them.  Enqueues only.
+// the short products of msm_resident.hip over a narrow table of n <= SHORT_BASES_MAX subgroup points: product i = sum_k scalars[i stride + first + k] P_k as
+// dense XYZZ (stride = n, first = 0: one table over a whole list; a longer list is cut into tables over consecutive points, each with its first index), the
+// identity where d_live[i] == 0 (those scalars are not read).  The scalars must be canonical: the caller has checked them.  Enqueues only.
 struct ShortBases;
 static constexpr uint64_t SHORT_BASES_MAX = 8192;
 int short_bases_create(ShortBases** out, Curve curve, const void* d_affine, uint64_t n, hipStream_t s);
 void short_bases_free(ShortBases* b);
-int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_live, uint32_t count, uint8_t* d_out_xyzz, hipStream_t s);
+int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_live, uint32_t count, uint64_t stride, uint64_t first, uint8_t* d_out_xyzz, hipStream_t s);
 int points_selftest_subgroup(Curve curve, SubgroupTest test, const uint8_t* points, uint64_t n, uint8_t* verdict, hipStream_t s);          // zk_selftest_subgroup
-// out[i] = a[i] + b[i] over encoded, already checked points (host bytes in, host bytes out)
-int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, hipStream_t s);
 // n ZCash-COMPRESSED points (host, 48 / 96 B) -> uncompressed (host, 96 / 192 B): square roots, curve and subgroup checks on the device (msm_points.hip)
 int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, hipStream_t s);
 int points_selftest_sqrt(int field, const uint8_t* a, uint64_t n, uint8_t* root, uint8_t* is_square, hipStream_t s);          // zk_selftest_sqrt

@@ -380,18 +380,6 @@ template <class F, SubgroupTest T> __global__ __launch_bounds__(128) void k_subg
     if (!in_subgroup<T>(p)) verdict[i] = 4;
 }
 
-// out[i] = a[i] + b[i] on dense affine points, every case of the group law (an identity operand, P + P, P + (-P)): the verifier's vio + vv and the like
-// (pinocchio.ml:418-420), G.add of curve.ml:159-191
-template <class F> __global__ __launch_bounds__(64) void k_aff_add(uint8_t* __restrict__ out, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    constexpr int B = FieldOps<F>::WORDS * 8;
-    Xyzz<F> acc = xyzz_from_aff(aff_load<F>(a + B * i));
-    const Aff<F> q = aff_load<F>(b + B * i);
-    xyzz_madd(acc, q);
-    aff_store<F>(out + B * i, xyzz_to_aff(acc));
-}
-
 // ------------------------------------------------------------------ base tables: table[j*n + i] = 2^(c*j) * P_i, j < nw
 // `dense` holds the n base points in the dense affine format (what the key arrived as); the table takes them -- and with nw > 1 their
 // multiples by 2^(c j) -- in the 128-byte record layout of ec.cuh (TableLayout).
@@ -581,26 +569,6 @@ int points_selftest_subgroup(Curve curve, SubgroupTest test, const uint8_t* poin
     HIPCHK(hipMemcpyAsync(raw.p, points, ab * n, hipMemcpyHostToDevice, s));
     ZKCHK(points_decode_verdicts(curve, aff.p, raw.p, n, dv.as<uint8_t>(), test, s));
     HIPCHK(hipMemcpyAsync(verdict, dv.p, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return ZK_OK;
-}
-// n sums a[i] + b[i] of encoded points (host bytes, both lists already checked) -> n encoded points (host)
-int points_add_pairs(Curve curve, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, hipStream_t s) {
-    if (!n) return ZK_OK;
-    const size_t ab = aff_bytes(curve);
-    DevBuf raw, da, db, dv;
-    ZKCHK(raw.alloc(2 * ab * n));
-    ZKCHK(da.alloc(2 * ab * n));
-    ZKCHK(db.alloc(ab * n));
-    ZKCHK(dv.alloc(2 * n));
-    HIPCHK(hipMemcpyAsync(raw.p, a, ab * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(raw.as<uint8_t>() + ab * n, b, ab * n, hipMemcpyHostToDevice, s));
-    ZKCHK(points_decode_verdicts(curve, da.p, raw.p, 2 * n, dv.as<uint8_t>(), SUBGROUP_NONE, s));
-    const uint8_t* sum_a = da.as<uint8_t>();
-    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_aff_add<FIELD_OF(f)>, grid_for(n, 64), dim3(64), 0, s, db.as<uint8_t>(), sum_a, sum_a + ab * n, n); });
-    HIPCHK(hipGetLastError());
-    ZKCHK(points_affine_to_bytes(curve, raw.p, db.p, n, s));
-    HIPCHK(hipMemcpyAsync(out, raw.p, ab * n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return ZK_OK;
 }

@@ -382,11 +382,11 @@ struct ShortBases {
     uint32_t cap_jobs = 0;
 };
 static constexpr uint32_t SHORT_BASES_CHUNK = 4096;          // products per launch (blockIdx.y): 16 / 32 MiB of bucket partials
-// job i of a launch: the scalars [i n, (i + 1) n) of the launch's block, none when live[i] == 0 (the product is then the identity, its scalars unread)
-__global__ void k_short_jobs(ResidentJob* jobs, const uint8_t* __restrict__ live, uint32_t count, uint32_t n) {
+// job i of a launch: the n scalars from i stride + first of the launch's block, none when live[i] == 0 (the product is then the identity, its scalars unread)
+__global__ void k_short_jobs(ResidentJob* jobs, const uint8_t* __restrict__ live, uint32_t count, uint32_t n, uint32_t stride, uint32_t first) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    jobs[i] = ResidentJob{i * n, live[i] ? n : 0u, 0u, 0u};
+    jobs[i] = ResidentJob{i * stride + first, live[i] ? n : 0u, 0u, 0u};
 }
 int short_bases_create(ShortBases** out, Curve curve, const void* d_affine, uint64_t n, hipStream_t s) {
     if (n == 0 || n > SHORT_BASES_MAX) ZK_FAIL(ZK_ERR_ARG, "short bases: 1 .. 2^13 points");
@@ -401,8 +401,11 @@ int short_bases_create(ShortBases** out, Curve curve, const void* d_affine, uint
     return ZK_OK;
 }
 void short_bases_free(ShortBases* b) { delete b; }
-int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_live, uint32_t count, uint8_t* d_out_xyzz, hipStream_t s) {
-    const uint32_t want = count < SHORT_BASES_CHUNK ? count : SHORT_BASES_CHUNK;
+int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_live, uint32_t count, uint64_t stride, uint64_t first, uint8_t* d_out_xyzz, hipStream_t s) {
+    // ResidentJob::sc_off has 32 bits: a launch's last job begins below per * stride
+    if (first + b.n > stride || stride > UINT32_MAX) ZK_FAIL(ZK_ERR_ARG, "short bases: the products' scalars lie outside a stride of 32 bits");
+    const uint32_t fit = (uint32_t)(UINT32_MAX / stride), per = fit < SHORT_BASES_CHUNK ? fit : SHORT_BASES_CHUNK;
+    const uint32_t want = count < per ? count : per;
     if (want > b.cap_jobs) {
         HIPCHK(hipStreamSynchronize(s));          // the buffers about to go may still be read
         ZKCHK(b.jobs.alloc(sizeof(ResidentJob) * (size_t)want));
@@ -411,11 +414,11 @@ int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_l
     }
     const size_t xb = xyzz_bytes(b.curve);
     ScopedTimer t("msm_short", s);
-    for (uint32_t k = 0; k < count; k += SHORT_BASES_CHUNK) {
-        const uint32_t cnt = count - k < SHORT_BASES_CHUNK ? count - k : SHORT_BASES_CHUNK;
-        hipLaunchKernelGGL(k_short_jobs, grid_for(cnt, 256), dim3(256), 0, s, b.jobs.as<ResidentJob>(), d_live + k, cnt, (uint32_t)b.n);
+    for (uint32_t k = 0; k < count; k += per) {
+        const uint32_t cnt = count - k < per ? count - k : per;
+        hipLaunchKernelGGL(k_short_jobs, grid_for(cnt, 256), dim3(256), 0, s, b.jobs.as<ResidentJob>(), d_live + k, cnt, (uint32_t)b.n, (uint32_t)stride, (uint32_t)first);
         const dim3 grid(SHORT_BUCKETS, cnt);
-        const uint32_t* sc = d_scalars + 8 * b.n * (uint64_t)k;
+        const uint32_t* sc = d_scalars + 8 * stride * k;
         if (b.curve == CURVE_G1)
             hipLaunchKernelGGL(k_msm_short<Fp>, grid, dim3(SHORT_THREADS), 0, s, (const uint8_t*)b.small.table.as<uint8_t>(), b.da, b.jobs.as<ResidentJob>(), sc,
                                b.partial.as<uint8_t>(), d_out_xyzz + xb * k, b.flag.as<int>());

@@ -1,11 +1,10 @@
-// Pairings in batches on the device (scope row f1; include/zkmi355x.h: zk_pairing_product_many, zk_groth16_verify_many, zk_pinocchio_verify_many):
-// many products of pairings -- many proofs' verifications -- per call.  The single-proof verifiers stay on the host (pairing_host.hip, which this
-// file does not touch: the host-only sanitizer library is built from it alone); a stream of proofs is checked here.  Same definitions, same bytes:
-// Pairing.pairing of curve.mli:46-54, Groth16.verify of groth16.ml:163-173, Verify.f of pinocchio.ml:254-420.
+// Pairings in batches on the device (scope row f1): many products of pairings per call.  This file holds the pairing kernels, the pairing_*_device entries
+// that enqueue them on device buffers, zk_pairing_product_many (include/zkmi355x.h) and zk_selftest_fp12 -- and no verifier: the batched and the resident
+// verifiers are one pipeline in verify_resident.hip, which calls the entries below.  The single-proof verifiers stay on the host (pairing_host.hip, which
+// this file does not touch: the host-only sanitizer library is built from it alone).  Same definition, same bytes: Pairing.pairing of curve.mli:46-54.
 //
-//   bytes -> affine + one verdict per point    k_bytes_to_affine_verdict, k_subgroup_verdict by [r] P = O (msm_points.hip: one lane per point); which
-//                                               bad point decides a proof's or the call's status: verdict_order.h
-//   sums over the public inputs                 the resident short products of msm_resident.hip: the key's points uploaded once per call, one product per proof
+//   bytes -> affine + one verdict per point    (zk_pairing_product_many) k_bytes_to_affine_verdict, k_subgroup_verdict by [r] P = O (msm_points.hip: one lane
+//                                               per point); the first bad point in the host's decoding order fails the call
 //   Miller loops                                k_miller: one group of 8 lanes per PAIR (pairing_tower.cuh), inversion-free, 63 steps
 //   products + final exponentiations            k_final_exp: one group per PRODUCT multiplies its pairs' Miller values and raises to (p^12 - 1) / r
 //   one long product (the folded verifier)      k_gt_tree_mul: one group per RUN of GT_TREE_RUN raw Miller values, level after level until one is left;
@@ -16,10 +15,8 @@
 #include "pairing_tower.cuh"
 
 #include "msm.cuh"
-#include "pairing_consts.h"
 #include "verdict_order.h"
 
-#include <string.h>
 #include <vector>
 
 namespace zk {
@@ -137,8 +134,6 @@ __global__ __launch_bounds__(64) void k_selftest_fp12(int op, const uint8_t* __r
 }
 
 // ================================================================== host side
-static constexpr uint32_t MAX_PROOFS = 1u << 24;          // 13 pairs each stay inside the 31-bit pair index
-
 // The two pairing kernels on buffers that are ALREADY on the device: npairs checked dense affine pairs (d_g1: 96 B each, d_g2: 192 B), product q = the
 // pairs [d_off[q], d_off[q + 1]) -> count GT encodings in d_gt (576 B each).  d_miller: F12_RAW_WORDS words per pair.  Enqueues, does not wait.
 size_t pairing_miller_bytes(uint64_t npairs) { return (size_t)F12_RAW_WORDS * 4 * npairs; }
@@ -185,125 +180,13 @@ int pairing_gt_pow_device(const uint8_t* d_base, const uint32_t* d_exp, uint32_t
     return ZK_OK;
 }
 
-// count products over npairs = sum lens pairs (host bytes) -> count GT encodings.  test: every point's subgroup membership too (SUBGROUP_NONE: encoding
-// and curve only, the caller has checked them).  v1 / v2: the verdicts, one per pair and side; a rejected point counts as the identity.
-static int run_products(const uint8_t* g1, const uint8_t* g2, uint64_t npairs, const uint64_t* lens, uint32_t count, SubgroupTest test, std::vector<uint8_t>& v1,
-                        std::vector<uint8_t>& v2, uint8_t* gt_out, hipStream_t s) {
-    v1.assign(npairs, 0);
-    v2.assign(npairs, 0);
-    if (npairs >= ((uint64_t)1 << 31)) ZK_FAIL(ZK_ERR_ARG, "pairing products: too many pairs for one call");
-    std::vector<uint32_t> off(count + 1);
-    uint64_t run = 0;
-    for (uint32_t k = 0; k < count; k++) { off[k] = (uint32_t)run; run += lens[k]; }
-    off[count] = (uint32_t)run;
-    DevBuf b1, b2, a1, a2, dv, dm, doff, dgt;
-    ZKCHK(b1.alloc(96 * npairs));
-    ZKCHK(b2.alloc(192 * npairs));
-    ZKCHK(a1.alloc(96 * npairs));
-    ZKCHK(a2.alloc(192 * npairs));
-    ZKCHK(dv.alloc(2 * npairs));
-    ZKCHK(dm.alloc((size_t)F12_RAW_WORDS * 4 * npairs));
-    ZKCHK(doff.alloc(4 * (size_t)(count + 1)));
-    ZKCHK(dgt.alloc(576 * (size_t)count));
-    HIPCHK(hipMemcpyAsync(doff.p, off.data(), 4 * (size_t)(count + 1), hipMemcpyHostToDevice, s));
-    if (npairs) {
-        HIPCHK(hipMemcpyAsync(b1.p, g1, 96 * npairs, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(b2.p, g2, 192 * npairs, hipMemcpyHostToDevice, s));
-        {
-            ScopedTimer t("pairing_point_checks", s);
-            ZKCHK(points_decode_verdicts(CURVE_G2, a2.p, b2.p, npairs, dv.as<uint8_t>() + npairs, test, s));
-            ZKCHK(points_decode_verdicts(CURVE_G1, a1.p, b1.p, npairs, dv.as<uint8_t>(), test, s));
-        }
-        HIPCHK(hipMemcpyAsync(v1.data(), dv.p, npairs, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(v2.data(), dv.as<uint8_t>() + npairs, npairs, hipMemcpyDeviceToHost, s));
-    }
-    ZKCHK(pairing_products_device(a1.as<uint8_t>(), a2.as<uint8_t>(), npairs, doff.as<uint32_t>(), count, dm.as<uint32_t>(), dgt.as<uint8_t>(), s));
-    HIPCHK(hipMemcpyAsync(gt_out, dgt.p, 576 * (size_t)count, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return ZK_OK;
-}
-
-// ---- byte-level point helpers of the verifiers (the encodings are canonical: they passed the checks or came from the device's encoder)
-static void be48_p(uint8_t out[48]) {
-    for (int i = 0; i < 6; i++)
-        for (int k = 0; k < 8; k++) out[8 * (5 - i) + k] = (uint8_t)(HP_P[i] >> (8 * (7 - k)));
-}
-// -P of a G1 encoding: y -> p - y (the identity, and y = 0, stay)
-static void g1_neg_bytes(uint8_t out[96], const uint8_t in[96]) {
-    memcpy(out, in, 96);
-    if (in[0] & 0x40) return;
-    uint8_t any = 0;
-    for (int i = 48; i < 96; i++) any |= in[i];
-    if (!any) return;
-    uint8_t p[48];
-    be48_p(p);
-    int borrow = 0;
-    for (int i = 47; i >= 0; i--) {
-        const int d = (int)p[i] - (int)in[48 + i] - borrow;
-        out[48 + i] = (uint8_t)(d & 0xff);
-        borrow = d < 0 ? 1 : 0;
-    }
-}
-static void g1_identity(uint8_t out[96]) { memset(out, 0, 96); out[0] = 0x40; }
-static void g2_identity(uint8_t out[192]) { memset(out, 0, 192); out[0] = 0x40; }
-static bool fr_canonical(const uint8_t* b) {          // 32-byte little-endian < r
-    for (int i = 3; i >= 0; i--) {
-        uint64_t w = 0;
-        for (int k = 7; k >= 0; k--) w = (w << 8) | b[8 * i + k];
-        if (w < HP_R[i]) return true;
-        if (w > HP_R[i]) return false;
-    }
-    return false;
-}
-// out[i] = sum_k scalars[i][k] * points[k] for count scalar vectors of n over ONE point list (G.dot, curve.ml:91-103): the list goes up once as
-// resident bases, one product per proof.  live[i] = 0: vector i is not multiplied (its proof is already rejected; it may hold scalars >= r).
-static int dot_many(int group, const uint8_t* points, size_t n, const uint8_t* scalars, uint32_t count, const std::vector<uint8_t>& live, uint8_t* out) {
-    const size_t ab = group ? 192 : 96;
-    if (!n) {
-        for (uint32_t i = 0; i < count; i++) { memset(out + ab * i, 0, ab); out[ab * i] = 0x40; }
-        return ZK_OK;
-    }
-    std::vector<uint8_t> sc(scalars, scalars + 32 * n * (size_t)count);
-    for (uint32_t i = 0; i < count; i++)
-        if (!live[i]) memset(sc.data() + 32 * n * i, 0, 32 * n);
-    const std::vector<uint64_t> lens(count, n);
-    uint64_t h = 0;
-    ZKCHK(zk_bases_upload(group, points, n, &h));
-    const int rc = zk_msm_resident_many(h, sc.data(), lens.data(), count, out);
-    (void)zk_bases_free(h);
-    return rc;
-}
-// The front half of both verifiers.  Every point of the call through the decoder and [r] P = O, once: the proofs' points laid out per proof as the plan
-// says (G1 point q of proof i at n1 i + q: the layout of k_vk_gather), the key's k1 / k2 points behind them.  A defect of the key is the call's; else
-// st[i] = proof i's status (its first bad point in the host's order, then its public inputs: verdict_order.h), live[i] = its pairings are still to be taken.
-static int check_call(const VkPlan& p, const uint8_t* proofs, uint32_t count, const uint8_t* key1, size_t k1, const uint8_t* key2, size_t k2,
-                      KeyDefect (*key_defect)(const uint8_t*, const uint8_t*, size_t), size_t n_io, const uint8_t* io_scalars, std::vector<int32_t>& st,
-                      std::vector<uint8_t>& live, hipStream_t s) {
-    const size_t c = count;
-    std::vector<uint8_t> p1(96 * (p.n1 * c + k1)), p2(192 * (p.n2 * c + k2)), v1, v2, bad(c, 0);
-    for (size_t i = 0; i < c; i++) {
-        for (uint32_t q = 0; q < p.n1; q++) memcpy(&p1[96 * (p.n1 * i + q)], proofs + p.stride * i + p.off1[q], 96);
-        for (uint32_t q = 0; q < p.n2; q++) memcpy(&p2[192 * (p.n2 * i + q)], proofs + p.stride * i + p.off2[q], 192);
-        for (size_t k = 0; k < n_io && !bad[i]; k++) bad[i] = !fr_canonical(io_scalars + 32 * (n_io * i + k));
-    }
-    if (k1) memcpy(&p1[96 * p.n1 * c], key1, 96 * k1);
-    memcpy(&p2[192 * p.n2 * c], key2, 192 * k2);
-    DevBuf a1, a2;          // the decoded points are not kept: the pairs go up as bytes again
-    ZKCHK(points_decode_two_lists(p1.data(), p.n1 * c + k1, p2.data(), p.n2 * c + k2, "pairing_point_checks", SUBGROUP_ORDER, a1, a2, v1, v2, s));
-    const KeyDefect kd = key_defect(v1.data() + p.n1 * c, v2.data() + p.n2 * c, n_io);
-    if (kd.verdict) ZK_FAIL(verdict_code(kd.verdict), kd.what);
-    for (uint32_t i = 0; i < count; i++) {
-        st[i] = verdict_code(proof_code(p, v1.data(), v2.data(), bad.data(), i));
-        live[i] = st[i] == ZK_OK;
-    }
-    return ZK_OK;
-}
-
 }  // namespace zk
 
 using namespace zk;
 extern "C" {
 
+// count products over npairs = sum lens pairs (host bytes) -> count GT encodings (Pairing.pairing, curve.mli:46-54): every point decoded and held to the
+// curve and the subgroup once, then the two kernels; a rejected point counts as the identity and fails the call
 int zk_pairing_product_many(const uint8_t* g1_points, const uint8_t* g2_points, const uint64_t* lens, uint32_t count, uint8_t* gt_out) {
     if (!count) return ZK_OK;
     if (!lens || !gt_out) ZK_FAIL(ZK_ERR_ARG, "zk_pairing_product_many: null argument");
@@ -312,130 +195,25 @@ int zk_pairing_product_many(const uint8_t* g1_points, const uint8_t* g2_points, 
     if (npairs && (!g1_points || !g2_points)) ZK_FAIL(ZK_ERR_ARG, "zk_pairing_product_many: null argument");
     ZKCHK(ensure_init());
     DeviceScope ds(0);
+    hipStream_t s = ctx().stream;
+    if (npairs >= ((uint64_t)1 << 31)) ZK_FAIL(ZK_ERR_ARG, "pairing products: too many pairs for one call");
+    std::vector<uint32_t> off(count + 1);
+    uint64_t run = 0;
+    for (uint32_t k = 0; k < count; k++) { off[k] = (uint32_t)run; run += lens[k]; }
+    off[count] = (uint32_t)run;
+    DevBuf a1, a2, dm, doff, dgt;
     std::vector<uint8_t> v1, v2;
-    ZKCHK(run_products(g1_points, g2_points, npairs, lens, count, SUBGROUP_ORDER, v1, v2, gt_out, ctx().stream));
+    ZKCHK(points_decode_two_lists(g1_points, npairs, g2_points, npairs, "pairing_point_checks", SUBGROUP_ORDER, a1, a2, v1, v2, s));
+    ZKCHK(dm.alloc(pairing_miller_bytes(npairs)));
+    ZKCHK(doff.alloc(4 * (size_t)(count + 1)));
+    ZKCHK(dgt.alloc(576 * (size_t)count));
+    HIPCHK(hipMemcpyAsync(doff.p, off.data(), 4 * (size_t)(count + 1), hipMemcpyHostToDevice, s));
+    ZKCHK(pairing_products_device(a1.as<uint8_t>(), a2.as<uint8_t>(), npairs, doff.as<uint32_t>(), count, dm.as<uint32_t>(), dgt.as<uint8_t>(), s));
+    HIPCHK(hipMemcpyAsync(gt_out, dgt.p, 576 * (size_t)count, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     for (uint64_t i = 0; i < npairs; i++) {          // the host's decoding order: G1 of pair i, then G2 of pair i
         if (v1[i]) ZK_FAIL(verdict_code(v1[i]), "zk_pairing_product_many: bad G1 point (encoding, curve or subgroup)");
         if (v2[i]) ZK_FAIL(verdict_code(v2[i]), "zk_pairing_product_many: bad G2 point (encoding, curve or subgroup)");
-    }
-    return ZK_OK;
-}
-
-// groth16.ml:163-173:  e(A, B) = ab * e(sum_k w_k ltgm_io_k, gm) * e(C, d), as zk_groth16_verify decides it: e(A, B) e(-acc, gm) e(-C, d) == ab on bytes
-int zk_groth16_verify_many(const uint8_t ab[576], const uint8_t* ltgm_io, size_t n_io, const uint8_t gm[192], const uint8_t d[192], const uint8_t* io_scalars,
-                           const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
-    if (!ab || !gm || !d || (n_io && !ltgm_io)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: null argument");
-    if (!count) return ZK_OK;
-    if (!proofs || !ok || (n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: null argument");
-    if (count > MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: more than 2^24 proofs in one call");
-    ZKCHK(ensure_init());
-    DeviceScope ds(0);
-    hipStream_t s = ctx().stream;
-    uint8_t key2[384];
-    memcpy(key2, gm, 192);
-    memcpy(key2 + 192, d, 192);
-    std::vector<int32_t> st(count);
-    std::vector<uint8_t> live(count), v1, v2;
-    ZKCHK(check_call(PLAN_GROTH16, proofs, count, ltgm_io, n_io, key2, 2, groth16_key_defect, n_io, io_scalars, st, live, s));
-    std::vector<uint8_t> acc(96 * (size_t)count);
-    ZKCHK(dot_many(0, ltgm_io, n_io, io_scalars, count, live, acc.data()));
-    std::vector<uint8_t> q1(96 * 3 * (size_t)count), q2(192 * 3 * (size_t)count), gt(576 * (size_t)count);
-    for (uint32_t i = 0; i < count; i++) {
-        uint8_t* a = &q1[96 * 3 * (size_t)i];
-        uint8_t* b = &q2[192 * 3 * (size_t)i];
-        if (!live[i]) {          // three pairs that contribute 1
-            for (int k = 0; k < 3; k++) { g1_identity(a + 96 * k); g2_identity(b + 192 * k); }
-            continue;
-        }
-        memcpy(a, proofs + 384 * (size_t)i, 96);
-        g1_neg_bytes(a + 96, &acc[96 * (size_t)i]);
-        g1_neg_bytes(a + 192, proofs + 384 * (size_t)i + 288);
-        memcpy(b, proofs + 384 * (size_t)i + 96, 192);
-        memcpy(b + 192, gm, 192);
-        memcpy(b + 384, d, 192);
-    }
-    const std::vector<uint64_t> lens(count, 3);
-    ZKCHK(run_products(q1.data(), q2.data(), 3 * (uint64_t)count, lens.data(), count, SUBGROUP_NONE, v1, v2, gt.data(), s));
-    for (uint32_t i = 0; i < count; i++) {
-        ok[i] = live[i] && memcmp(&gt[576 * (size_t)i], ab, 576) == 0 ? 1 : 0;
-        if (status) status[i] = st[i];
-    }
-    return ZK_OK;
-}
-
-// Verify.f, pinocchio.ml:254-420, as zk_pinocchio_verify decides it: five products of pairings, each equal to 1.
-//   vk_g1 = one | aw | bgm | vv_io[n_io] | yy_io[n_io]      vk_g2 = one2 | av | ay | gm2 | bgm2 | yt | ww_io[n_io]
-//   proof = vv | ww (G2) | yy | h | vavv | waww (G2) | yayy | bvwy
-int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_io, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok,
-                             int32_t* status) {
-    if (!vk_g1 || !vk_g2) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: null argument");
-    if (!count) return ZK_OK;
-    if (!proofs || !ok || (n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: null argument");
-    if (count > MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: more than 2^24 proofs in one call");
-    ZKCHK(ensure_init());
-    DeviceScope ds(0);
-    hipStream_t s = ctx().stream;
-    const size_t c = count;
-    std::vector<int32_t> st(count);
-    std::vector<uint8_t> live(count), v1, v2;
-    ZKCHK(check_call(PLAN_PINOCCHIO, proofs, count, vk_g1, 3 + 2 * n_io, vk_g2, 6 + n_io, pinocchio_key_defect, n_io, io_scalars, st, live, s));
-    // vio, yio, wio (G.dot over the public inputs), then vio + vv, yio + yy, wio + ww
-    std::vector<uint8_t> vio(96 * c), yio(96 * c), wio(192 * c), pv(96 * c), py(96 * c), pw(192 * c);
-    ZKCHK(dot_many(0, vk_g1 + 96 * 3, n_io, io_scalars, count, live, vio.data()));
-    ZKCHK(dot_many(0, vk_g1 + 96 * (3 + n_io), n_io, io_scalars, count, live, yio.data()));
-    ZKCHK(dot_many(1, vk_g2 + 192 * 6, n_io, io_scalars, count, live, wio.data()));
-    for (size_t i = 0; i < c; i++) {
-        if (live[i]) {
-            memcpy(&pv[96 * i], proofs + 960 * i, 96);
-            memcpy(&py[96 * i], proofs + 960 * i + 288, 96);
-            memcpy(&pw[192 * i], proofs + 960 * i + 96, 192);
-        } else {
-            g1_identity(&pv[96 * i]);
-            g1_identity(&py[96 * i]);
-            g2_identity(&pw[192 * i]);
-        }
-    }
-    std::vector<uint8_t> vsum(96 * c), ysum(96 * c), wsum(192 * c);
-    ZKCHK(points_add_pairs(CURVE_G1, vio.data(), pv.data(), c, vsum.data(), s));
-    ZKCHK(points_add_pairs(CURVE_G1, yio.data(), py.data(), c, ysum.data(), s));
-    ZKCHK(points_add_pairs(CURVE_G2, wio.data(), pw.data(), c, wsum.data(), s));
-    // the five equations, 13 pairs per proof
-    const uint8_t *one = vk_g1, *aw = vk_g1 + 96, *bgm = vk_g1 + 192;
-    const uint8_t *one2 = vk_g2, *av = vk_g2 + 192, *ay = vk_g2 + 384, *gm2 = vk_g2 + 576, *bgm2 = vk_g2 + 768, *yt = vk_g2 + 960;
-    std::vector<uint8_t> q1(96 * 13 * c), q2(192 * 13 * c), gt(576 * 5 * c);
-    std::vector<uint64_t> lens(5 * c);
-    for (size_t i = 0; i < c; i++) {
-        uint8_t* a = &q1[96 * 13 * i];
-        uint8_t* b = &q2[192 * 13 * i];
-        static const uint64_t L[5] = {2, 2, 2, 4, 3};
-        for (int q = 0; q < 5; q++) lens[5 * i + q] = L[q];
-        if (!live[i]) {
-            for (int k = 0; k < 13; k++) { g1_identity(a + 96 * k); g2_identity(b + 192 * k); }
-            continue;
-        }
-        const uint8_t* pr = proofs + 960 * i;
-        const uint8_t *vv = pr, *ww = pr + 96, *yy = pr + 288, *h = pr + 384, *vavv = pr + 480, *waww = pr + 576, *yayy = pr + 768, *bvwy = pr + 864;
-        int k = 0;
-        auto pair = [&](const uint8_t* g1p, bool neg, const uint8_t* g2p) {
-            if (neg) g1_neg_bytes(a + 96 * k, g1p);
-            else memcpy(a + 96 * k, g1p, 96);
-            memcpy(b + 192 * k, g2p, 192);
-            k++;
-        };
-        pair(vv, false, av); pair(vavv, true, one2);                                                         // :285
-        pair(aw, false, ww); pair(one, true, waww);                                                          // :298
-        pair(yy, false, ay); pair(yayy, true, one2);                                                         // :311
-        pair(bvwy, false, gm2); pair(vv, true, bgm2); pair(bgm, true, ww); pair(yy, true, bgm2);             // :361-366
-        pair(&vsum[96 * i], false, &wsum[192 * i]); pair(&ysum[96 * i], true, one2); pair(h, true, yt);      // :418-420
-    }
-    ZKCHK(run_products(q1.data(), q2.data(), 13 * (uint64_t)c, lens.data(), 5 * count, SUBGROUP_NONE, v1, v2, gt.data(), s));
-    uint8_t gt_one[576];
-    gt_one_bytes(gt_one);
-    for (size_t i = 0; i < c; i++) {
-        bool good = live[i] != 0;
-        for (int q = 0; q < 5; q++) good = good && memcmp(&gt[576 * (5 * i + q)], gt_one, 576) == 0;
-        ok[i] = good ? 1 : 0;
-        if (status) status[i] = st[i];
     }
     return ZK_OK;
 }

@@ -1,23 +1,27 @@
-// Verification keys resident on the device (include/zkmi355x.h: zk_groth16_vk_upload, zk_pinocchio_vk_upload, zk_vk_info, zk_vk_free,
-// zk_groth16_verify_resident, zk_pinocchio_verify_resident): the verification-side twin of the resident MSM bases.  A verifier checks a stream of proofs
-// under ONE key (Groth16.verify of groth16.ml:163-173, Verify.f of pinocchio.ml:254-420, the points through of_bytes_exn, curve.ml:199-212), and the
-// batched verifiers of pairing_dev.hip pay for the key again in every call: its points are decoded and subgroup-checked, its IO points go through the
-// public zk_bases_upload (a second decode and check, window tables, a pinned arena), and a dozen buffers are allocated and freed.  Here the key is
-// decoded and checked ONCE, and a call moves only what belongs to its proofs:
+// Verification of many proofs under one key, on the device (include/zkmi355x.h: zk_groth16_vk_upload, zk_pinocchio_vk_upload, zk_vk_info, zk_vk_free,
+// zk_groth16_verify_resident, zk_pinocchio_verify_resident, zk_groth16_verify_folded, and zk_groth16_verify_many, zk_pinocchio_verify_many): the
+// verification-side twin of the resident MSM bases.  A verifier checks a stream of proofs under ONE key (Groth16.verify of groth16.ml:163-173, Verify.f of
+// pinocchio.ml:254-420, the points through of_bytes_exn, curve.ml:199-212).  The key is decoded and checked ONCE, and a call moves only what belongs to
+// its proofs.  ONE pipeline serves both kinds of call: a *_verify_many call builds the same key with the same code, keeps it out of the handle table,
+// runs the same slabs and drops it when it returns -- a resident key that lives for one call.  Two fields of the key (VkChecks) tell the two apart and
+// nothing else does: the subgroup test of every point (an uploaded key SUBGROUP_ENDO, a one-call key SUBGROUP_ORDER) and the timer family of the point
+// checks (verify_point_checks / pairing_point_checks).
 //
-//   upload   key bytes -> dense affine points on the device, every one checked (encoding, curve, subgroup by endomorphism: SUBGROUP_ENDO of
-//            msm_points.hip); the IO points also as a narrow table for the short products of msm_resident.hip; `ab` kept as its 576 bytes.
-//   verify   per slab of up to VK_SLAB proofs, on workspaces the handle keeps and grows on demand:
+//   build    key bytes -> dense affine points on the device, every one checked (encoding, curve, subgroup: msm_points.hip); the IO points also as
+//            narrow tables for the short products of msm_resident.hip, one per SHORT_BASES_MAX consecutive points of a list (an uploaded key holds at
+//            most that many public inputs: one table per list; a one-call key has no such limit); `ab` kept as its 576 bytes.
+//   verify   per slab of up to VK_SLAB proofs, on workspaces the key keeps and grows on demand:
 //              1 one H2D copy: proofs | public inputs
 //              2 k_vk_gather + k_bytes_to_affine_verdict + k_subgroup_verdict: every proof point decoded once, one verdict byte each
 //              3 k_vk_scalar_range, k_vk_status: a public input >= r, then the proof's first failure in the host's order (verdict_order.h) -> one code byte per proof
-//              4 one short product per IO sum and proof (k_msm_short; a rejected proof's product has no scalars), results stay on the device
+//              4 one short product per IO sum, table and proof (k_msm_short; a rejected proof's product has no scalars), results stay on the device;
+//                where a list has several tables, one xyzz_sum_columns launch adds their sums
 //              5 k_vk_pairs_*: the pair lists assembled on the device -- G1 points negated as points (y -> p - y), Pinocchio's vio + vv, yio + yy,
 //                wio + ww added here; a rejected proof gets identity pairs
 //              6 k_miller, k_final_exp (pairing_dev.hip, unchanged), k_vk_compare against the 576 bytes of `ab` / of 1
 //              7 one D2H copy: ok | code
-// The verdicts are those of zk_*_verify_many byte for byte: the same decoder, the same order of checks, the same pairs into the same two kernels, and
-// a subgroup verdict that is the same predicate (tests/test_subgroup_criterion.py, tests/test_gpu_subgroup_endo.py).  Nothing here reads an option.
+// The verdicts are those of the host verifiers (pairing_host.hip), and the same under both subgroup tests: one predicate
+// (tests/test_subgroup_criterion.py, tests/test_gpu_subgroup_endo.py).  Nothing here reads an option.
 //
 // zk_groth16_verify_folded answers ONE question about a batch -- are all of these proofs good? -- with one pairing equation instead of one per proof:
 // with a secret random rho_i per proof,
@@ -42,6 +46,9 @@ namespace zk {
 
 static constexpr uint32_t VK_MAX_PROOFS = 1u << 24;
 static constexpr uint32_t VK_SLAB = 8192;          // proofs per pass: bounds the workspaces (Pinocchio: 20 KiB per proof) whatever the call's count
+// ... and whatever the key's n_io: a slab's input buffer, stride + 32 n_io bytes per proof on the device and as many in its pinned twin, stays under this
+// budget.  A slab holds VK_SLAB proofs whenever that fits (keys of up to some 2000 public inputs), and at least one.
+static constexpr uint64_t VK_SLAB_BYTES = (uint64_t)1 << 30;
 
 // 16-byte units of every proof's points -> the dense lists the decoder reads: G1 point q of proof i at g1[(n1 i + q) 96], G2 at g2[(n2 i + q) 192]
 __global__ void k_vk_gather(const uint8_t* __restrict__ proofs, uint32_t count, VkPlan p, uint8_t* __restrict__ g1, uint8_t* __restrict__ g2) {
@@ -276,12 +283,22 @@ __global__ void k_fold_verdict(const uint8_t* __restrict__ lhs, const uint8_t* _
 }
 
 // ================================================================== host side
+// what an uploaded key and the key of one *_verify_many call differ in
+struct VkChecks {
+    SubgroupTest test;                        // of every point of the key and of its proofs
+    const char* family;                       // the timer family of those checks
+};
+static constexpr VkChecks CHECKS_UPLOADED = {SUBGROUP_ENDO, "verify_point_checks"}, CHECKS_ONE_CALL = {SUBGROUP_ORDER, "pairing_point_checks"};
+
 struct ResidentVk {
     int protocol = 0;                         // 0 Groth16, 1 Pinocchio
     uint64_t n_io = 0;
+    VkChecks checks = CHECKS_UPLOADED;
+    uint32_t slab = VK_SLAB;                  // proofs per pass (VK_SLAB_BYTES)
     DevBuf key1, key2;                        // the key's points, dense affine.  Groth16: ltgm_io[n_io] / gm | d.  Pinocchio: the layouts of zk_pinocchio_verify
     DevBuf want;                              // 576 B: ab (Groth16) / the encoding of 1 (Pinocchio)
-    ShortBases* io[3] = {nullptr, nullptr, nullptr};          // Groth16: ltgm_io.  Pinocchio: vv_io, yy_io, ww_io.  null when n_io = 0
+    std::vector<ShortBases*> io[3];           // Groth16: ltgm_io.  Pinocchio: vv_io, yy_io, ww_io.  One table per SHORT_BASES_MAX points of the list; none when n_io = 0
+    DevBuf parts;                             // the tables' sums of one list for `cap` proofs, before they are added (lists of several tables only)
     // workspaces for `cap` proofs
     uint32_t cap = 0;
     DevBuf in, b1, b2, a1, a2, verdict, flags, sums, q1, q2, off, miller, gt;
@@ -291,7 +308,8 @@ struct ResidentVk {
     uint32_t fold_cap = 0;
     DevBuf fa, fc, fsum, fm, fm2, fold;       // [rho] A dense affine | [rho] C and the running sum, XYZZ | partial sums | Miller values | tree levels | FoldState
     ~ResidentVk() {
-        for (ShortBases* b : io) short_bases_free(b);
+        for (const std::vector<ShortBases*>& list : io)
+            for (ShortBases* b : list) short_bases_free(b);
         if (host) (void)hipHostFree(host);
     }
 };
@@ -326,12 +344,56 @@ static int vk_lookup(uint64_t handle, int protocol, ResidentVk** out) {
     if (protocol >= 0 && (*out)->protocol != protocol) ZK_FAIL(ZK_ERR_HANDLE, "the verification key handle belongs to the other protocol");
     return ZK_OK;
 }
-static int vk_install(std::unique_ptr<ResidentVk>& k, const uint8_t want[576], hipStream_t s, uint64_t* handle) {
-    ZKCHK(k->want.alloc(576));
-    HIPCHK(hipMemcpyAsync(k->want.p, want, 576, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));          // the tables are built, the caller's bytes are read
-    *handle = g_vk.add(std::move(k));
+// ---- the builders: a key of either kind, not yet in the table.  vk_new touches no device; *_vk_fill decodes, checks and tabulates the key's points on
+// stream s and waits for it.  A defect of the key is the caller's error, in the host verifier's order (verdict_order.h)
+static std::unique_ptr<ResidentVk> vk_new(int protocol, uint64_t n_io, VkChecks checks) {
+    auto k = std::make_unique<ResidentVk>();
+    k->protocol = protocol;
+    k->n_io = n_io;
+    k->checks = checks;
+    const uint64_t fit = VK_SLAB_BYTES / (2 * (plan_of(*k).stride + 32 * n_io));
+    k->slab = fit >= VK_SLAB ? VK_SLAB : fit ? (uint32_t)fit : 1;
+    return k;
+}
+// IO list q = the n_io dense affine points at d_affine (checked, in the subgroup) as narrow tables
+static int vk_io_tables(ResidentVk& k, int q, Curve curve, const uint8_t* d_affine, hipStream_t s) {
+    for (uint64_t lo = 0; lo < k.n_io; lo += SHORT_BASES_MAX) {
+        ShortBases* b = nullptr;
+        ZKCHK(short_bases_create(&b, curve, d_affine + aff_bytes(curve) * lo, k.n_io - lo < SHORT_BASES_MAX ? k.n_io - lo : SHORT_BASES_MAX, s));
+        k.io[q].push_back(b);
+    }
     return ZK_OK;
+}
+static int vk_finish(ResidentVk& k, const uint8_t want[576], hipStream_t s) {
+    ZKCHK(k.want.alloc(576));
+    HIPCHK(hipMemcpyAsync(k.want.p, want, 576, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));          // the tables are built, the caller's bytes are read
+    return ZK_OK;
+}
+static int groth16_vk_fill(ResidentVk& k, const uint8_t ab[576], const uint8_t* ltgm_io, const uint8_t gm[192], const uint8_t d[192], hipStream_t s) {
+    const size_t n_io = k.n_io;
+    uint8_t g2[384];
+    memcpy(g2, gm, 192);
+    memcpy(g2 + 192, d, 192);
+    std::vector<uint8_t> v1, v2;
+    ZKCHK(points_decode_two_lists(ltgm_io, n_io, g2, 2, k.checks.family, k.checks.test, k.key1, k.key2, v1, v2, s));
+    const KeyDefect bad = groth16_key_defect(v1.data(), v2.data(), n_io);
+    if (bad.verdict) ZK_FAIL(verdict_code(bad.verdict), bad.what);
+    ZKCHK(vk_io_tables(k, 0, CURVE_G1, k.key1.as<uint8_t>(), s));
+    return vk_finish(k, ab, s);
+}
+static int pinocchio_vk_fill(ResidentVk& k, const uint8_t* vk_g1, const uint8_t* vk_g2, hipStream_t s) {
+    const size_t n_io = k.n_io;
+    std::vector<uint8_t> v1, v2;
+    ZKCHK(points_decode_two_lists(vk_g1, 3 + 2 * n_io, vk_g2, 6 + n_io, k.checks.family, k.checks.test, k.key1, k.key2, v1, v2, s));
+    const KeyDefect bad = pinocchio_key_defect(v1.data(), v2.data(), n_io);
+    if (bad.verdict) ZK_FAIL(verdict_code(bad.verdict), bad.what);
+    ZKCHK(vk_io_tables(k, 0, CURVE_G1, k.key1.as<uint8_t>() + 96 * 3, s));
+    ZKCHK(vk_io_tables(k, 1, CURVE_G1, k.key1.as<uint8_t>() + 96 * (3 + n_io), s));
+    ZKCHK(vk_io_tables(k, 2, CURVE_G2, k.key2.as<uint8_t>() + 192 * 6, s));
+    uint8_t gt_one[576];
+    gt_one_bytes(gt_one);
+    return vk_finish(k, gt_one, s);
 }
 
 static int vk_reserve(ResidentVk& k, uint32_t c, hipStream_t s) {
@@ -351,6 +413,8 @@ static int vk_reserve(ResidentVk& k, uint32_t c, hipStream_t s) {
     ZKCHK(k.verdict.alloc((p.n1 + p.n2) * n));
     ZKCHK(k.flags.alloc(4 * n + 16 * fold));  // scalar-range byte | live | ok | code (| all_ok)
     ZKCHK(k.sums.alloc((192 * nsum1 + 384 * nsum2) * n));
+    const uint64_t tables = (k.n_io + SHORT_BASES_MAX - 1) / SHORT_BASES_MAX;          // per IO list
+    if (tables > 1) ZKCHK(k.parts.alloc(xyzz_bytes(k.protocol == 0 ? CURVE_G1 : CURVE_G2) * tables * n));
     ZKCHK(k.q1.alloc(96 * p.pairs * n));
     ZKCHK(k.q2.alloc(192 * p.pairs * n));
     ZKCHK(k.off.alloc(4 * (p.products * n + 1)));
@@ -403,9 +467,9 @@ static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t
     HIPCHK(hipMemsetAsync(bad, 0, n, s));
     hipLaunchKernelGGL(k_vk_gather, grid_for(n * (6 * p.n1 + 12 * p.n2), 256), dim3(256), 0, s, (const uint8_t*)d_in, c, p, k.b1.as<uint8_t>(), k.b2.as<uint8_t>());
     {
-        ScopedTimer t("verify_point_checks", s);
-        ZKCHK(points_decode_verdicts(CURVE_G2, k.a2.p, k.b2.p, p.n2 * n, v2, SUBGROUP_ENDO, s));
-        ZKCHK(points_decode_verdicts(CURVE_G1, k.a1.p, k.b1.p, p.n1 * n, v1, SUBGROUP_ENDO, s));
+        ScopedTimer t(k.checks.family, s);
+        ZKCHK(points_decode_verdicts(CURVE_G2, k.a2.p, k.b2.p, p.n2 * n, v2, k.checks.test, s));
+        ZKCHK(points_decode_verdicts(CURVE_G1, k.a1.p, k.b1.p, p.n1 * n, v1, k.checks.test, s));
     }
     if (sb) hipLaunchKernelGGL(k_vk_scalar_range, grid_for(k.n_io * n, 256), dim3(256), 0, s, d_sc, k.n_io * n, (uint32_t)k.n_io, bad);
     hipLaunchKernelGGL(k_vk_status, grid_for(n, 256), dim3(256), 0, s, (const uint8_t*)v1, (const uint8_t*)v2, (const uint8_t*)bad, c, p, code, live);
@@ -413,12 +477,25 @@ static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t
     return ZK_OK;
 }
 
-// proofs [0, c) of a slab: everything of the file's header, steps 1-7
-static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t c, uint8_t* ok, int32_t* status, hipStream_t s) {
+// out[i] = sum_k scalars[i n_io + k] P_k over IO list q (2: the list in G2) for c proofs, dense XYZZ, the identity where live[i] == 0: one short product per
+// table of the list, and where it has several, their sums added by the complete addition of xyzz_sum_columns
+static int vk_io_sum(ResidentVk& k, int q, const uint32_t* d_sc, const uint8_t* live, uint32_t c, uint8_t* out, hipStream_t s) {
+    const std::vector<ShortBases*>& tables = k.io[q];
+    if (tables.size() == 1) return short_bases_run(*tables[0], d_sc, live, c, k.n_io, 0, out, s);
+    const Curve curve = q == 2 ? CURVE_G2 : CURVE_G1;
+    for (size_t j = 0; j < tables.size(); j++)
+        ZKCHK(short_bases_run(*tables[j], d_sc, live, c, k.n_io, SHORT_BASES_MAX * j, k.parts.as<uint8_t>() + xyzz_bytes(curve) * c * j, s));
+    ScopedTimer t("msm_short", s);
+    return xyzz_sum_columns(curve, out, k.parts.p, (uint32_t)tables.size(), c, s);
+}
+
+// proofs [0, c) of a slab: everything of the file's header, steps 1-7 (front: steps 1-3 are already enqueued and left this)
+static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t c, const SlabFront* front, uint8_t* ok, int32_t* status, hipStream_t s) {
     const VkPlan& p = plan_of(k);
     const size_t n = c;
     SlabFront f;
-    ZKCHK(vk_slab_front(k, io_scalars, proofs, nullptr, c, f, s));
+    if (front) f = *front;
+    else ZKCHK(vk_slab_front(k, io_scalars, proofs, nullptr, c, f, s));
     const size_t pb = f.pb, sb = f.sb;
     const uint32_t* d_sc = f.d_sc;
     uint8_t *live = f.live, *d_ok = f.d_ok;
@@ -427,7 +504,7 @@ static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proo
     const int nsums = k.protocol == 0 ? 1 : 3;
     if (!k.n_io) HIPCHK(hipMemsetAsync(k.sums.p, 0, k.protocol == 0 ? 192 * n : 768 * n, s));
     else
-        for (int q = 0; q < nsums; q++) ZKCHK(short_bases_run(*k.io[q], d_sc, live, c, sum[q], s));
+        for (int q = 0; q < nsums; q++) ZKCHK(vk_io_sum(k, q, d_sc, live, c, sum[q], s));
     if (k.protocol == 0)
         hipLaunchKernelGGL(k_vk_pairs_groth16, grid_for(n, 64), dim3(64), 0, s, (const uint8_t*)k.a1.as<uint8_t>(), (const uint8_t*)k.a2.as<uint8_t>(),
                            (const uint8_t*)k.key2.as<uint8_t>(), (const uint8_t*)sum[0], (const uint8_t*)live, c, k.q1.as<uint8_t>(), k.q2.as<uint8_t>(), k.off.as<uint32_t>());
@@ -450,6 +527,16 @@ static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proo
     return ZK_OK;
 }
 
+// count >= 1 proofs under key k, slab after slab (the arguments are checked).  first: the front half of the first slab, where it is already enqueued
+static int vk_run(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, const SlabFront* first, uint8_t* ok, int32_t* status, hipStream_t s) {
+    ZKCHK(vk_reserve(k, count < k.slab ? count : k.slab, s));
+    const size_t stride = plan_of(k).stride;
+    for (uint32_t lo = 0; lo < count; lo += k.slab) {
+        const uint32_t c = count - lo < k.slab ? count - lo : k.slab;
+        ZKCHK(vk_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, c, lo ? nullptr : first, ok + lo, status ? status + lo : nullptr, s));
+    }
+    return ZK_OK;
+}
 static int vk_verify(uint64_t handle, int protocol, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
     ResidentVk* kp;
     ZKCHK(vk_lookup(handle, protocol, &kp));
@@ -458,14 +545,25 @@ static int vk_verify(uint64_t handle, int protocol, const uint8_t* io_scalars, c
     if (!proofs || !ok || (k.n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "verify_resident: null argument");
     if (count > VK_MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "verify_resident: more than 2^24 proofs in one call");
     DeviceScope ds(0);
-    hipStream_t s = ctx().stream;
-    ZKCHK(vk_reserve(k, count < VK_SLAB ? count : VK_SLAB, s));
-    const size_t stride = plan_of(k).stride;
-    for (uint32_t lo = 0; lo < count; lo += VK_SLAB) {
-        const uint32_t c = count - lo < VK_SLAB ? count - lo : VK_SLAB;
-        ZKCHK(vk_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, c, ok + lo, status ? status + lo : nullptr, s));
-    }
-    return ZK_OK;
+    return vk_run(k, io_scalars, proofs, count, nullptr, ok, status, ctx().stream);
+}
+// A *_verify_many call (the arguments are checked, the device is current): the key of vk_new lives for this call and is in no table -- it draws no handle
+// number, does not count among the live handles and does not pin the device list.  `fill` is its protocol's *_vk_fill.  The first slab's proof points are
+// checked WHILE the key's are, on the context's two streams: neither needs the other, and [r] P = O is a chain of 254 doublings on one lane per point --
+// some 20 ms for two G2 points as for thousands -- so one after the other they would cost a call twice that.  A defective key still fails the call before
+// anything is written.  Nothing of the call is in flight when the key goes (as in zk_vk_free), whatever the call returns.
+template <class Fill>
+static int vk_verify_once(std::unique_ptr<ResidentVk> k, Fill fill, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
+    hipStream_t s = ctx().stream, s_key = ctx().stream2;
+    const uint32_t c = count < k->slab ? count : k->slab;
+    SlabFront f;
+    int rc = vk_reserve(*k, c, s);
+    if (!rc) rc = vk_slab_front(*k, io_scalars, proofs, nullptr, c, f, s);
+    if (!rc) rc = fill(*k, s_key);
+    if (!rc) rc = vk_run(*k, io_scalars, proofs, count, &f, ok, status, s);
+    (void)hipStreamSynchronize(s_key);
+    (void)hipStreamSynchronize(s);
+    return rc;
 }
 
 // One slab of the folded call: the front half, then the slab's share of both sides folded into the state
@@ -506,7 +604,7 @@ static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t*
     size_t out = n;
     if (last) {
         // sum_k t_k ltgm_io_k (zero bytes, the identity, when n_io = 0), the key's two pairs, the one final exponentiation, ab^S, the comparison
-        if (k.n_io) ZKCHK(short_bases_run(*k.io[0], reinterpret_cast<const uint32_t*>(st + F_T), st + F_ONE, 1, st + F_SUMS, s));
+        if (k.n_io) ZKCHK(vk_io_sum(k, 0, reinterpret_cast<const uint32_t*>(st + F_T), st + F_ONE, 1, st + F_SUMS, s));
         hipLaunchKernelGGL(k_fold_key_pairs, dim3(1), dim3(64), 0, s, (const uint8_t*)(st + F_SUMS), (const uint8_t*)k.key2.as<uint8_t>(), k.q1.as<uint8_t>(),
                            k.q2.as<uint8_t>(), reinterpret_cast<uint32_t*>(st + F_OFF));
         HIPCHK(hipGetLastError());
@@ -549,13 +647,13 @@ static int vk_fold(uint64_t handle, const uint8_t* io_scalars, const uint8_t* pr
     if (k.n_io && !io_scalars) ZK_FAIL(ZK_ERR_ARG, "verify_folded: null argument");
     DeviceScope ds(0);
     hipStream_t s = ctx().stream;
-    ZKCHK(vk_reserve_fold(k, count < VK_SLAB ? count : VK_SLAB, s));
+    ZKCHK(vk_reserve_fold(k, count < k.slab ? count : k.slab, s));
     uint8_t* st = k.fold.as<uint8_t>();
     HIPCHK(hipMemsetAsync(st + F_SUMS, 0, F_T + 32 * k.n_io - F_SUMS, s));
     HIPCHK(hipMemsetAsync(st + F_ONE, 1, 1, s));
     uint8_t verdict = 0;
-    for (uint32_t lo = 0; lo < count; lo += VK_SLAB) {
-        const uint32_t c = count - lo < VK_SLAB ? count - lo : VK_SLAB;
+    for (uint32_t lo = 0; lo < count; lo += k.slab) {
+        const uint32_t c = count - lo < k.slab ? count - lo : k.slab;
         ZKCHK(vk_fold_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + 384 * (size_t)lo, rho + 16 * (size_t)lo, c, lo == 0, lo + c == count,
                            status ? status + lo : nullptr, &verdict, s));
     }
@@ -578,19 +676,10 @@ int zk_groth16_vk_upload(const uint8_t ab[576], const uint8_t* ltgm_io, size_t n
     if (n_io > SHORT_BASES_MAX) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_vk_upload: a resident key holds at most 2^13 public inputs (zk_groth16_verify_many has no such limit)");
     ZKCHK(ensure_init());
     DeviceScope ds(0);
-    hipStream_t s = ctx().stream;
-    auto k = std::make_unique<ResidentVk>();
-    k->protocol = 0;
-    k->n_io = n_io;
-    uint8_t g2[384];
-    memcpy(g2, gm, 192);
-    memcpy(g2 + 192, d, 192);
-    std::vector<uint8_t> v1, v2;
-    ZKCHK(points_decode_two_lists(ltgm_io, n_io, g2, 2, "verify_point_checks", SUBGROUP_ENDO, k->key1, k->key2, v1, v2, s));
-    const KeyDefect bad = groth16_key_defect(v1.data(), v2.data(), n_io);
-    if (bad.verdict) ZK_FAIL(verdict_code(bad.verdict), bad.what);
-    if (n_io) ZKCHK(short_bases_create(&k->io[0], CURVE_G1, k->key1.p, n_io, s));
-    return vk_install(k, ab, s, handle);
+    auto k = vk_new(0, n_io, CHECKS_UPLOADED);
+    ZKCHK(groth16_vk_fill(*k, ab, ltgm_io, gm, d, ctx().stream));
+    *handle = g_vk.add(std::move(k));
+    return ZK_OK;
 }
 
 int zk_pinocchio_vk_upload(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_io, uint64_t* handle) {
@@ -598,22 +687,36 @@ int zk_pinocchio_vk_upload(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_
     if (n_io > SHORT_BASES_MAX) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_vk_upload: a resident key holds at most 2^13 public inputs (zk_pinocchio_verify_many has no such limit)");
     ZKCHK(ensure_init());
     DeviceScope ds(0);
-    hipStream_t s = ctx().stream;
-    auto k = std::make_unique<ResidentVk>();
-    k->protocol = 1;
-    k->n_io = n_io;
-    std::vector<uint8_t> v1, v2;
-    ZKCHK(points_decode_two_lists(vk_g1, 3 + 2 * n_io, vk_g2, 6 + n_io, "verify_point_checks", SUBGROUP_ENDO, k->key1, k->key2, v1, v2, s));
-    const KeyDefect bad = pinocchio_key_defect(v1.data(), v2.data(), n_io);
-    if (bad.verdict) ZK_FAIL(verdict_code(bad.verdict), bad.what);
-    if (n_io) {
-        ZKCHK(short_bases_create(&k->io[0], CURVE_G1, k->key1.as<uint8_t>() + 96 * 3, n_io, s));
-        ZKCHK(short_bases_create(&k->io[1], CURVE_G1, k->key1.as<uint8_t>() + 96 * (3 + n_io), n_io, s));
-        ZKCHK(short_bases_create(&k->io[2], CURVE_G2, k->key2.as<uint8_t>() + 192 * 6, n_io, s));
-    }
-    uint8_t gt_one[576];
-    gt_one_bytes(gt_one);
-    return vk_install(k, gt_one, s, handle);
+    auto k = vk_new(1, n_io, CHECKS_UPLOADED);
+    ZKCHK(pinocchio_vk_fill(*k, vk_g1, vk_g2, ctx().stream));
+    *handle = g_vk.add(std::move(k));
+    return ZK_OK;
+}
+
+// groth16.ml:163-173:  e(A, B) = ab * e(sum_k w_k ltgm_io_k, gm) * e(C, d), as zk_groth16_verify decides it: e(A, B) e(-acc, gm) e(-C, d) == ab on bytes
+int zk_groth16_verify_many(const uint8_t ab[576], const uint8_t* ltgm_io, size_t n_io, const uint8_t gm[192], const uint8_t d[192], const uint8_t* io_scalars,
+                           const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
+    if (!ab || !gm || !d || (n_io && !ltgm_io)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: null argument");
+    if (!count) return ZK_OK;
+    if (!proofs || !ok || (n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: null argument");
+    if (count > VK_MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_verify_many: more than 2^24 proofs in one call");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    return vk_verify_once(vk_new(0, n_io, CHECKS_ONE_CALL), [&](ResidentVk& k, hipStream_t s) { return groth16_vk_fill(k, ab, ltgm_io, gm, d, s); }, io_scalars, proofs, count,
+                          ok, status);
+}
+
+// Verify.f, pinocchio.ml:254-420, as zk_pinocchio_verify decides it: five products of pairings, each equal to 1 (k_vk_pairs_pinocchio)
+int zk_pinocchio_verify_many(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t n_io, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok,
+                             int32_t* status) {
+    if (!vk_g1 || !vk_g2) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: null argument");
+    if (!count) return ZK_OK;
+    if (!proofs || !ok || (n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: null argument");
+    if (count > VK_MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_verify_many: more than 2^24 proofs in one call");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    return vk_verify_once(vk_new(1, n_io, CHECKS_ONE_CALL), [&](ResidentVk& k, hipStream_t s) { return pinocchio_vk_fill(k, vk_g1, vk_g2, s); }, io_scalars, proofs, count, ok,
+                          status);
 }
 
 int zk_vk_info(uint64_t handle, int* protocol, uint64_t* n_io) {
