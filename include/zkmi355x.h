@@ -506,6 +506,14 @@ int zk_bench_field_mul(int kind, uint32_t iters, double* gmul_per_s);
  * integers) the device evaluates 23 base-field expressions through the lazy-reduction code paths of the group law and
  * returns them fully reduced (23 x 48 B per pair, little-endian); pairs (2k, 2k+1) also act as one Fp2 operand pair. */
 int zk_selftest_fp(const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
+/* The paired field products (tests/test_gpu_fp_paired.py): two or three independent products of the group law run side by side where the products are
+ * expanded in place.  operands: n x 4 values a, b, c, d as their 14 limbs of 29 bits in a 16-word slot each (64 words per lane), weakly normalised --
+ * every limb at most 2^29 + 7, top limb at most 64 * 13 (every value below the at-rest bound 64 p qualifies) -- so the caller chooses the representation.
+ * out: 13 x 48 B per lane, little-endian, fully reduced, each the Montgomery product x y / 2^406 mod p:
+ *   0, 1  a b | c d      2, 3  a^2 | c^2      4, 5  a b | a b      6, 7  a b | c a      8, 9  a b | c d with each output written over an input
+ *   10, 11, 12  a b - c d | a d | c b (the fused double product with its lazily negated factor beside two plain products).
+ * A null pointer, n = 0, a limb or a top limb out of range -> ZK_ERR_ARG before the device is touched. */
+int zk_selftest_fp_paired(const uint32_t* operands, size_t n, uint8_t* out);
 /* Square roots as the decompression kernels take them (tests/test_gpu_field.py): n elements of Fp (field 0: 48 B big-endian each) or Fp2 (field 1:
  * 96 B each, imaginary part | real part, the order of a G2 coordinate on the wire), one lane per element.  is_square[i] = 1 / 0; root[i] = of the two
  * roots the one the ZCash sign rule calls the larger (Fp2: by the imaginary part, by the real part when that is zero) -- decided by the same device

@@ -8,9 +8,21 @@ Every column of partial products is ONE asm statement (<= 30 operands) made of
     v_addc_co_u32 acc2, vcc, 0, acc2, vcc          ; carry into the third word
 so the compiler's per-statement hazard padding (one s_nop) is paid ~4 times per column instead of
 once per product, and no zero-extension moves exist at all.  Modulus limbs travel in SGPRs.
-Run: python scripts/gen_mont_mul.py
+
+It also generates zukelang_amd/csrc/fp_pair_gen.cuh: PAIRED Montgomery products of the base field Fp (14 limbs of
+29 bits, R = 2^406, carry-free 64-bit columns; ff.cuh).  Two (at the end of an addition, three) independent products of
+a group addition run side by side: every column of each product is ONE chain of v_mad_u64_u32 seeded with the shifted
+carry of the column before, and the multiply-adds of the products alternate inside each asm statement, so a dependent
+multiply-add is always two or more instructions away from its producer and no 64-bit add ever joins two partial chains
+of one column.  The forms are
+described by one list of steps (schedule()) that both the emitter and the integer model (model_*) consume: the model
+replays the schedule on Python integers, checks the result, and checks that no accumulator reaches 2^64 at the worst
+limb values each form admits.
+Run: python scripts/gen_mont_mul.py            (writes both headers)
+     python scripts/gen_mont_mul.py --check    (runs the integer model only)
 """
 import os
+import sys
 
 FR = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 FP = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
@@ -73,14 +85,273 @@ def gen(name, N, mod, inv):
     return "\n".join(out)
 
 
+# ====================================================================== Fp: paired products, radix 2^29
+W29, L29 = 29, 14
+M29 = (1 << W29) - 1
+FP29_MOD = [(FP >> (W29 * i)) & M29 for i in range(L29 - 1)] + [FP >> (W29 * (L29 - 1))]
+FP29_NINV = (-pow(FP, -1, 1 << W29)) % (1 << W29)
+WEAK = (1 << 29) + 7          # a weakly normalised limb (ff.cuh: one carry pass over limbs < 2^32)
+LAZY = 1 << 30                # a limb of K p - a without a carry pass (fe_neg_lazy)
+MAX_OPERANDS = 30             # per asm statement, accumulators included
+
+
+def terms_mul(x, y):
+    """Partial products of column k of x * y, as (left, right) operand names."""
+    def col(k):
+        return [("%s[%d]" % (x, i), "%s[%d]" % (y, k - i)) for i in range(max(0, k - L29 + 1), min(k, L29 - 1) + 1)]
+    return col
+
+
+def terms_sqr(x, d):
+    """Column k of x^2: the off-diagonal products once, against the doubled operand d."""
+    def col(k):
+        t = [("%s[%d]" % (x, i), "%s[%d]" % (d, k - i)) for i in range(max(0, k - L29 + 1), L29) if 2 * i < k]
+        if k % 2 == 0:
+            t.append(("%s[%d]" % (x, k // 2), "%s[%d]" % (x, k // 2)))
+        return t
+    return col
+
+
+# A form = the chains that run side by side.  A chain is (output, [products]): the Montgomery reduction of the SUM of its products (one for a
+# product or a square, two for the fused double product); a product is ("mul", x, y) or ("sqr", x) over operand names.
+FORMS = {
+    "fp_mul_pair_limbs": dict(
+        args="uint32_t* r0, const uint32_t* a0, const uint32_t* b0, uint32_t* r1, const uint32_t* a1, const uint32_t* b1",
+        chains=[("r0", [("mul", "a0", "b0")]), ("r1", [("mul", "a1", "b1")])],
+        limb_max={"a0": WEAK, "b0": WEAK, "a1": WEAK, "b1": WEAK}),
+    "fp_sqr_pair_limbs": dict(
+        args="uint32_t* r0, const uint32_t* a0, uint32_t* r1, const uint32_t* a1",
+        chains=[("r0", [("sqr", "a0")]), ("r1", [("sqr", "a1")])],
+        limb_max={"a0": WEAK, "a1": WEAK}),
+    # (x1 y1 + x2 y2) / R beside two plain products: the end of a mixed addition (Y3 | ZZ PP | ZZZ PPP).  x2 may be a lazy negation (fe_neg_lazy).
+    "fp_mul2_mul_pair_limbs": dict(
+        args="uint32_t* r0, const uint32_t* x1, const uint32_t* y1, const uint32_t* x2, const uint32_t* y2, "
+             "uint32_t* r1, const uint32_t* a1, const uint32_t* b1, uint32_t* r2, const uint32_t* a2, const uint32_t* b2",
+        chains=[("r0", [("mul", "x1", "y1"), ("mul", "x2", "y2")]), ("r1", [("mul", "a1", "b1")]), ("r2", [("mul", "a2", "b2")])],
+        limb_max={"x1": WEAK, "y1": WEAK, "x2": LAZY, "y2": WEAK, "a1": WEAK, "b1": WEAK, "a2": WEAK, "b2": WEAK}),
+}
+
+
+def chain_operands(chain):
+    return [n for pr in chain[1] for n in pr[1:]]
+
+
+def column_terms(pr, k):
+    return terms_mul(pr[1], pr[2])(k) if pr[0] == "mul" else terms_sqr(pr[1], "d_" + pr[1])(k)
+
+
+def schedule(form):
+    """The straight-line program of a form: ('mads', [(chain, left, right), ...]) with the chains alternating,
+    ('digit', chain, k) (quotient digit of column k, its product with p[0], the shift) and ('out', chain, k)."""
+    chains = FORMS[form]["chains"]
+    prog = []
+    for k in range(2 * L29 - 1):
+        per = []
+        for c, (_, prods) in enumerate(chains):
+            t = [x for pr in prods for x in column_terms(pr, k)]
+            t += [("m%d[%d]" % (c, i), "P%d" % (k - i)) for i in range(max(0, k - L29 + 1), min(k, L29))]
+            per.append([(c, l, r) for l, r in t])
+        inter = []
+        for j in range(max(len(x) for x in per)):
+            for x in per:
+                if j < len(x):
+                    inter.append(x[j])
+        prog.append(("mads", inter))
+        for c in range(len(chains)):
+            prog.append(("digit", c, k) if k < L29 else ("out", c, k - L29))
+    return prog
+
+
+def squared_operands(form):
+    return [pr[1] for ch in FORMS[form]["chains"] for pr in ch[1] if pr[0] == "sqr"]
+
+
+def statements(mads, nch):
+    """Cut one column's multiply-adds into asm statements of at most MAX_OPERANDS distinct operands."""
+    out, cur, ops = [], [], []
+    for c, l, r in mads:
+        need = [x for x in (l, r) if x not in ops]
+        if nch + len(ops) + len(set(need)) > MAX_OPERANDS:
+            out.append((cur, ops))
+            cur, ops = [], []
+            need = [l, r]
+        for x in need:
+            if x not in ops:
+                ops.append(x)
+        cur.append((c, l, r))
+    if cur:
+        out.append((cur, ops))
+    return out
+
+
+def emit_form(form):
+    f = FORMS[form]
+    nch = len(f["chains"])
+    o = ["FF_INLINE void %s(%s) {" % (form, f["args"])]
+    o.append("    uint64_t " + ", ".join("c%d" % c for c in range(nch)) + ";")
+    o.append("    uint32_t " + ", ".join("m%d[%d], t%d[%d]" % (c, L29, c, L29) for c in range(nch)) + ";")
+    for a in squared_operands(form):
+        o.append("    uint32_t d_%s[%d];" % (a, L29))
+        o.append("    _Pragma(\"unroll\") for (int i = 0; i < %d; i++) d_%s[i] = %s[i] << 1;" % (L29, a, a))
+    fresh = [True] * nch
+    for step in schedule(form):
+        if step[0] == "mads":
+            for cur, ops in statements(step[1], nch):
+                used = sorted(set(c for c, _, _ in cur))          # the accumulators are operands 0 .. len(used) - 1
+                first = fresh[used[0]]
+                assert all(fresh[c] == first for c in used)
+                lines = []
+                for c, l, r in cur:
+                    li, ri = len(used) + ops.index(l), len(used) + ops.index(r)
+                    lines.append("v_mad_u64_u32 %%%d, vcc, %%%d, %%%d, %s" % (used.index(c), li, ri, "0" if fresh[c] else "%%%d" % used.index(c)))
+                    fresh[c] = False
+                outs = ", ".join(('"=&v"(c%d)' if first else '"+v"(c%d)') % c for c in used)
+                ins = ", ".join('"s"(0x%08xu)' % FP29_MOD[int(x[1:])] if x[0] == "P" else '"v"(%s)' % x for x in ops)
+                o.append('    asm("%s" : %s : %s : "vcc");' % ("\\n\\t".join(lines), outs, ins))
+        elif step[0] == "digit":
+            _, c, k = step
+            o.append("    m%d[%d] = ((uint32_t)c%d * 0x%08xu) & 0x%08xu; c%d += (uint64_t)m%d[%d] * 0x%08xu; c%d >>= %d;"
+                     % (c, k, c, FP29_NINV, M29, c, c, k, FP29_MOD[0], c, W29))
+        else:
+            _, c, j = step
+            if j < L29 - 2:
+                o.append("    t%d[%d] = (uint32_t)c%d & 0x%08xu; c%d >>= %d;" % (c, j, c, M29, c, W29))
+            else:
+                o.append("    t%d[%d] = (uint32_t)c%d & 0x%08xu; t%d[%d] = (uint32_t)(c%d >> %d);" % (c, j, c, M29, c, j + 1, c, W29))
+    for c, (r, _) in enumerate(f["chains"]):
+        o.append("    _Pragma(\"unroll\") for (int i = 0; i < %d; i++) %s[i] = t%d[i];" % (L29, r, c))
+    o.append("}")
+    return "\n".join(o)
+
+
+# ---------------------------------------------------------------------- integer model of the schedules
+def model_run(form, vals):
+    """Replays schedule(form) on Python integers.  vals: operand name -> 14 limbs.  Returns the output limbs per chain
+    and the largest value any accumulator held; asserts the 64-bit and 32-bit ranges on the way."""
+    f = FORMS[form]
+    nch = len(f["chains"])
+    env = dict(vals)
+    for a in squared_operands(form):
+        env["d_" + a] = [x << 1 for x in env[a]]
+        assert all(x < 1 << 32 for x in env["d_" + a])
+    for c in range(nch):
+        env["m%d" % c] = [None] * L29
+    acc, peak, out = [0] * nch, 0, [[0] * L29 for _ in range(nch)]
+
+    def get(name):
+        if name[0] == "P":
+            return FP29_MOD[int(name[1:])]
+        arr, i = name[:-1].split("[")
+        return env[arr][int(i)]
+    for step in schedule(form):
+        if step[0] == "mads":
+            for c, l, r in step[1]:
+                x, y = get(l), get(r)
+                assert x < 1 << 32 and y < 1 << 32
+                acc[c] += x * y
+                peak = max(peak, acc[c])
+        elif step[0] == "digit":
+            _, c, k = step
+            m = ((acc[c] & 0xFFFFFFFF) * FP29_NINV) & M29
+            env["m%d" % c][k] = m
+            acc[c] += m * FP29_MOD[0]
+            peak = max(peak, acc[c])
+            assert acc[c] & M29 == 0
+            acc[c] >>= W29
+        else:
+            _, c, j = step
+            out[c][j] = acc[c] & M29
+            if j == L29 - 2:
+                out[c][j + 1] = acc[c] >> W29
+                assert out[c][j + 1] < 1 << 32
+            acc[c] >>= W29
+        assert peak < 1 << 64, (form, step[:1], "a column accumulator reaches 2^64")
+    return out, peak
+
+
+def limbs_value(l):
+    return sum(x << (W29 * i) for i, x in enumerate(l))
+
+
+def model_expected(form, vals):
+    """The value each chain must return: the sum of its products / 2^406 mod p (as a residue)."""
+    rinv = pow(1 << (W29 * L29), -1, FP)
+    v = {k: limbs_value(x) for k, x in vals.items()}
+    return [sum(v[pr[1]] * v[pr[-1]] for pr in ch[1]) * rinv % FP for ch in FORMS[form]["chains"]]
+
+
+def model_cases(form, samples=0, seed=0x29):
+    """The operand sets a form is checked on: every operand at its admitted maximum; all zero; for each chain, that chain all-maximum beside the
+    others all-zero and the reverse (nothing may leak between chains); then `samples` sets of random limbs.  The first case is the all-maximum one."""
+    import random
+    rnd = random.Random(seed)
+    f = FORMS[form]
+    names = list(f["limb_max"])
+    top = {n: [f["limb_max"][n]] * L29 for n in names}
+    zero = {n: [0] * L29 for n in names}
+    cases = [top, zero]
+    if len(f["chains"]) > 1:
+        for ch in f["chains"]:
+            mine = chain_operands(ch)
+            cases.append({n: (top if n in mine else zero)[n] for n in names})
+            cases.append({n: (zero if n in mine else top)[n] for n in names})
+    for _ in range(samples):
+        cases.append({n: [rnd.randrange(f["limb_max"][n] + 1) for _ in range(L29)] for n in names})
+    return cases
+
+
+def model_check(samples=64, seed=0x29):
+    """Every form on model_cases: the residues are right, the output limbs exact, no accumulator reaches 2^64 (model_run asserts it step by step).
+    Returns {form: log2 of the largest accumulator seen}."""
+    import math
+    report = {}
+    for form in FORMS:
+        cases = model_cases(form, samples, seed)
+        peak = 0
+        for vals in cases:
+            out, pk = model_run(form, vals)
+            peak = max(peak, pk)
+            for o, e in zip(out, model_expected(form, vals)):
+                assert limbs_value(o) % FP == e, (form, "wrong residue")
+                assert all(x <= M29 for x in o[:-1]), (form, "output limb not exact")
+        # the admitted maximum is the worst case of every accumulator (all terms are products of non-negative limbs):
+        assert peak == model_run(form, cases[0])[1]
+        report[form] = math.log2(peak)
+    return report
+
+
+def gen_fp_pair():
+    o = ["// GENERATED by scripts/gen_mont_mul.py -- do not edit.",
+         "// Paired Montgomery products of Fp (14 x 29-bit limbs, R = 2^406): two or three independent products side by side, every column of each",
+         "// ONE v_mad_u64_u32 chain seeded with the shifted carry, the products' multiply-adds alternating.  Results are those of fp_mul_limbs /",
+         "// fp_sqr_limbs / fp_mul2_limbs (ff.cuh) bit for bit; outputs may alias inputs.  Column bounds: the generator's integer model.",
+         "#pragma once", "#include <stdint.h>", "", "namespace zk {", ""]
+    for form in FORMS:
+        o.append(emit_form(form))
+        o.append("")
+    o.append("}  // namespace zk")
+    return "\n".join(o) + "\n"
+
+
+def gen_fr_header():
+    # the base field Fp no longer uses this scheme: radix 2^29, carry-free columns (ff.cuh, gen_fp29_consts.py)
+    return ("// GENERATED by scripts/gen_mont_mul.py -- do not edit.\n#pragma once\n#include <stdint.h>\n\nnamespace zk {\n\n"
+            + gen("fr", 8, FR, (-pow(FR, -1, 1 << 32)) % (1 << 32)) + "\n\n}  // namespace zk\n")
+
+
 def main():
+    for form, bits in model_check().items():
+        print("model: %s holds, largest column accumulator 2^%.3f" % (form, bits))
+    if "--check" in sys.argv[1:]:
+        return
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = os.path.join(root, "zukelang_amd", "csrc", "ff_mul_gen.cuh")
     with open(path, "w") as f:
-        f.write("// GENERATED by scripts/gen_mont_mul.py -- do not edit.\n#pragma once\n#include <stdint.h>\n\nnamespace zk {\n\n")
-        f.write(gen("fr", 8, FR, (-pow(FR, -1, 1 << 32)) % (1 << 32)))
-        # the base field Fp no longer uses this scheme: radix 2^29, carry-free columns (ff.cuh, gen_fp29_consts.py)
-        f.write("\n\n}  // namespace zk\n")
+        f.write(gen_fr_header())
+    print("wrote", path)
+    path = os.path.join(root, "zukelang_amd", "csrc", "fp_pair_gen.cuh")
+    with open(path, "w") as f:
+        f.write(gen_fp_pair())
     print("wrote", path)
 
 

@@ -29,7 +29,7 @@ EXPORTS = [
     "zk_groth16_vk_upload", "zk_pinocchio_vk_upload", "zk_vk_info", "zk_vk_free", "zk_groth16_verify_resident", "zk_pinocchio_verify_resident",
     "zk_groth16_verify_folded",
     "zk_profile_enable", "zk_profile_reset", "zk_profile_get", "zk_profile_names", "zk_profile_counter", "zk_sync",
-    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_group",
+    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_group",
 ]
 
 
@@ -82,6 +82,10 @@ FOLD_PROTOTYPES = {
 GROUP_PROTOTYPES = {
     "zk_selftest_group": [C.c_int, C.c_int, C.c_int, _P8, _P8, C.c_size_t, _P8],
 }
+# the paired field products' hook (tests/test_gpu_fp_paired.py)
+FP_PAIR_PROTOTYPES = {
+    "zk_selftest_fp_paired": [C.POINTER(C.c_uint32), C.c_size_t, _P8],
+}
 KEY_FORMS = {"tau_powers": 0, "lagrange": 1}          # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
 
 _lib = None
@@ -97,7 +101,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

@@ -110,6 +110,14 @@ template <class F> FF_INLINE void xyzz_madd_equal_x(Xyzz<F>& acc, bool same_y) {
     xyzz_madd_equal_x_fn<F>(&t, same_y ? 1 : 0);
     acc = t;
 }
+// PAIRED PRODUCTS.  The G1 bucket accumulation (msm_acc_g1.hip: ZK_FP_INLINE_MUL, the base-field products expanded in place) runs the independent
+// products of its mixed addition side by side (ff.cuh: fe_mul2, fe_sqr2, fe_mul_sub_mul2): U2 | S2, PP | R^2, PPP | Q, Y3 | ZZ PP | ZZZ PPP.  The same
+// operations on the same values, so the same limbs come out.  Units whose products are calls, and the extension fields, keep the sequence of single products.
+#ifdef ZK_FP_INLINE_MUL
+template <class F> static constexpr bool PAIRED_PRODUCTS = std::is_same<F, Fp>::value;
+#else
+template <class F> static constexpr bool PAIRED_PRODUCTS = false;
+#endif
 // madd-2008-s: acc += q (q affine).  Q_MAY_BE_INF = false: the caller knows q is a genuine point (entries of the resident base tables: the
 // counting sort never files an identity base into a bucket), so the identity test -- 28 limbs OR-ed, a zero test of the lazily reduced y with
 // its out-of-line slow path, and the registers that path pins -- stays out of the bucket loop
@@ -119,6 +127,27 @@ template <class F, bool Q_MAY_BE_INF = true> FF_INLINE void xyzz_madd_impl(Xyzz<
     }
     if (xyzz_is_inf(acc)) {
         acc = {q.x, q.y, FieldOps<F>::one(), FieldOps<F>::one()};
+        return;
+    }
+    if constexpr (PAIRED_PRODUCTS<F>) {
+        const auto us = fe_mul2(q.x, acc.zz, q.y, acc.zzz);     // U2 | S2
+        const auto P = fe_sub(us.first, acc.x);
+        const auto R = fe_sub(us.second, acc.y);
+        if (fe_is_zero(P)) {
+            xyzz_madd_equal_x(acc, fe_is_zero(R));
+            return;
+        }
+        const auto sq = fe_sqr2(P, R);                           // PP | R^2
+        const auto& PP = sq.first;
+        const auto pq = fe_mul2(P, PP, acc.x, PP);               // PPP | Q
+        const auto& PPP = pq.first;
+        const auto& Q = pq.second;
+        const auto X3 = fe_sub_sub_dbl(sq.second, PPP, Q);      // R^2 - PPP - 2 Q, one carry pass
+        const auto yz = fe_mul_sub_mul2(R, fe_sub(Q, X3), acc.y, PPP, acc.zz, PP, acc.zzz, PPP);          // Y3 | ZZ PP | ZZZ PPP
+        acc.x = X3;
+        acc.y = yz.first;
+        acc.zz = yz.second;
+        acc.zzz = yz.third;
         return;
     }
     const auto U2 = fe_mul(q.x, acc.zz);

@@ -29,6 +29,7 @@
 
 #include "ff_mul_gen.cuh"
 #include "fp29_consts.cuh"
+#include "fp_pair_gen.cuh"
 
 namespace zk {
 
@@ -530,6 +531,25 @@ template <int A, int B> FF_INLINE FpB<2> fe_mul_inline(const FpB<A>& a, const Fp
     fp_mul_limbs(r.v, a.v, b.v);
     return r;
 }
+// Two INDEPENDENT products side by side, expanded in place (fp_pair_gen.cuh): the multiply-adds of the two alternate, every column of each is ONE
+// accumulator chain seeded with the shifted carry, and no 64-bit add joins partial chains -- a lone product gets its instruction-level parallelism
+// from two chains per column and pays 26 joins.  The values are those of two fe_mul / fe_sqr, bit for bit.  For the units that expand their products
+// in place (ec.cuh: PAIRED_PRODUCTS).  An out-of-line pair -- 56 operand registers in, 28 out, part of them through scratch -- was neither built nor measured.
+struct FpPair {
+    FpB<2> first, second;
+};
+template <int A, int B, int C, int D> FF_INLINE FpPair fe_mul2(const FpB<A>& a, const FpB<B>& b, const FpB<C>& c, const FpB<D>& d) {
+    static_assert((long long)A * B <= FP_MUL_BUDGET && (long long)C * D <= FP_MUL_BUDGET, "operand bounds exceed the Montgomery headroom");
+    FpPair r;
+    fp_mul_pair_limbs(r.first.v, a.v, b.v, r.second.v, c.v, d.v);
+    return r;
+}
+template <int A, int C> FF_INLINE FpPair fe_sqr2(const FpB<A>& a, const FpB<C>& c) {
+    static_assert((long long)A * A <= FP_MUL_BUDGET && (long long)C * C <= FP_MUL_BUDGET, "operand bound exceeds the Montgomery headroom");
+    FpPair r;
+    fp_sqr_pair_limbs(r.first.v, a.v, r.second.v, c.v);
+    return r;
+}
 
 // ---- full reduction: any value < 8192 p -> the unique representative < p with exact 29-bit limbs
 __device__ __noinline__ static FpRaw fp_canon_call(FP_ARGS(a)) {
@@ -870,6 +890,20 @@ template <int A, int B, int C, int D> FF_INLINE FpB<2> fe_mul_sub(const FpB<A>& 
 #endif
 }
 template <class X, class Y, class Z, class W> FF_INLINE auto fe_mul_sub(const X& a, const Y& b, const Z& c, const W& d) { return fe_sub(fe_mul(a, b), fe_mul(c, d)); }
+// a b - c d | e f | g h side by side, expanded in place: the end of a group addition (Y3 | ZZ PP | ZZZ PPP), three chains per column.  The lazily negated
+// factor (limbs up to 2^30, no carry pass) enters the FUSED chain only, whose column bound the generator's integer model holds below 2^64.
+struct FpTriple {
+    FpB<2> first, second, third;
+};
+template <int A, int B, int C, int D, int E, int F, int G, int H>
+FF_INLINE FpTriple fe_mul_sub_mul2(const FpB<A>& a, const FpB<B>& b, const FpB<C>& c, const FpB<D>& d, const FpB<E>& e, const FpB<F>& f, const FpB<G>& g, const FpB<H>& h) {
+    static_assert((long long)A * B + (long long)fp_ks(C) * D <= FP_MUL_BUDGET && (long long)E * F <= FP_MUL_BUDGET && (long long)G * H <= FP_MUL_BUDGET,
+                  "operand bounds exceed the Montgomery headroom");
+    const auto nc = fe_neg_lazy(c);
+    FpTriple r;
+    fp_mul2_mul_pair_limbs(r.first.v, a.v, b.v, nc.v, d.v, r.second.v, e.v, f.v, r.third.v, g.v, h.v);
+    return r;
+}
 
 }  // namespace zk
 
