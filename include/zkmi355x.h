@@ -514,6 +514,12 @@ int zk_selftest_fp(const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
  *   10, 11, 12  a b - c d | a d | c b (the fused double product with its lazily negated factor beside two plain products).
  * A null pointer, n = 0, a limb or a top limb out of range -> ZK_ERR_ARG before the device is touched. */
 int zk_selftest_fp_paired(const uint32_t* operands, size_t n, uint8_t* out);
+/* Two Fp2 products on a lane pair, one whole lazy-Karatsuba product per lane (tests/test_gpu_fp2_lanewise.py): what the G2 bucket accumulation issues.
+ * operands: n x 4 values a, b, c, d of Fp2, each as c0 | c1, each component as its 14 limbs of 29 bits in a 16-word slot (128 words per quadruple),
+ * weakly normalised as for zk_selftest_fp_paired.  out: 3 x 96 B per quadruple (c0 | c1, 48 B each, little-endian, fully reduced), each a Montgomery
+ * product x y / 2^406 in Fp2:   0  a b      1  c d      2  a b - c d (the fused end of a mixed addition).
+ * A null pointer, n = 0, a limb or a top limb out of range -> ZK_ERR_ARG before the device is touched. */
+int zk_selftest_fp2_lanewise(const uint32_t* operands, size_t n, uint8_t* out);
 /* Square roots as the decompression kernels take them (tests/test_gpu_field.py): n elements of Fp (field 0: 48 B big-endian each) or Fp2 (field 1:
  * 96 B each, imaginary part | real part, the order of a G2 coordinate on the wire), one lane per element.  is_square[i] = 1 / 0; root[i] = of the two
  * roots the one the ZCash sign rule calls the larger (Fp2: by the imaginary part, by the real part when that is zero) -- decided by the same device

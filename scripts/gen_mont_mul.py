@@ -18,7 +18,9 @@ of one column.  The forms are
 described by one list of steps (schedule()) that both the emitter and the integer model (model_*) consume: the model
 replays the schedule on Python integers, checks the result, and checks that no accumulator reaches 2^64 at the worst
 limb values each form admits.
-Run: python scripts/gen_mont_mul.py            (writes both headers)
+It also generates zukelang_amd/csrc/fp2_lane_gen.cuh: the Montgomery product of Fp2 on ONE lane (lazy Karatsuba, three base
+multiplications feeding two running reductions; see "Fp2 on ONE lane" below), with a schedule and an integer model of its own.
+Run: python scripts/gen_mont_mul.py            (writes the three headers)
      python scripts/gen_mont_mul.py --check    (runs the integer model only)
 """
 import os
@@ -333,6 +335,211 @@ def gen_fp_pair():
     return "\n".join(o) + "\n"
 
 
+# ====================================================================== Fp2 on ONE lane: lazy Karatsuba, column-interleaved
+# (a0 + a1 u)(b0 + b1 u), u^2 = -1, as three base multiplications feeding TWO running Montgomery reductions.  Column k forms
+#     T0 = sum a0_i b0_j        T1 = sum a1_i b1_j        t2 = sum (a0 + a1)_i (b0 + b1)_j          (i + j = k)
+# T0 and T1 each in an accumulator of their own starting at zero, t2 on top of the c1 chain's shifted carry; then
+#     c0 += T0 - T1             c1 -= T0 + T1
+# BEFORE the quotient digits' m p terms go on top (t2 alone is 14 * 2^60: with the m p terms it would pass 2^64), and the two chains reduce like two
+# plain products.  No unreduced double-width product is kept.
+#   * The sums a0 + a1, b0 + b1 are taken limb by limb WITHOUT a carry pass (limbs <= 2^30 + 14), so t2 - T0 - T1 is the exact column of
+#     a0 b1 + a1 b0 and the c1 chain never goes negative.
+#   * The c0 chain can: its accumulator is SIGNED (two's complement; v_mad_u64_u32 adds modulo 2^64, the shift is arithmetic).  The high columns
+#     add the limbs of p, that is p R to the product, so the value leaves as c0 + p, non-negative with exact limbs: c0 + p < 3p, c1 < 2p for operand
+#     bounds 2 A B <= 2^25 (ff.cuh: fe_mul2_lanewise).
+# The schedule (fp2_schedule) is one list of steps that the emitter and the integer model both consume, as for the paired forms above.
+FP2_FORM = "fp2_mul_lane_limbs"
+FP2_OPERANDS = ("a0", "a1", "b0", "b1")
+FP2_SUM = 2 * WEAK            # a limb of a0 + a1 (no carry pass)
+
+
+def fp2_schedule():
+    """('mads', [(acc, left, right), ...]): T0, T1 (fresh every column) and C1 (seeded with its carry) alternating, then after ('comb',) the m p terms
+    of C0 and C1 alternating; ('digit', chain, k) / ('out', chain, j) as in schedule(); ('addp', j): the c0 chain takes limb j of p; ('addtop',): its top limb."""
+    prog = []
+    for k in range(2 * L29 - 1):
+        idx = range(max(0, k - L29 + 1), min(k, L29 - 1) + 1)
+        inter = []
+        for i in idx:
+            inter += [("T0", "a0[%d]" % i, "b0[%d]" % (k - i)), ("T1", "a1[%d]" % i, "b1[%d]" % (k - i)), ("C1", "sa[%d]" % i, "sb[%d]" % (k - i))]
+        prog.append(("mads", inter))
+        prog.append(("comb",))
+        inter = []
+        for i in range(max(0, k - L29 + 1), min(k, L29)):
+            inter += [("C0", "m0[%d]" % i, "P%d" % (k - i)), ("C1", "m1[%d]" % i, "P%d" % (k - i))]
+        if inter:
+            prog.append(("mads", inter))
+        if k >= L29:
+            prog.append(("addp", k - L29))
+        for c in range(2):
+            prog.append(("digit", c, k) if k < L29 else ("out", c, k - L29))
+    prog.append(("addtop",))          # the top limb of p goes straight onto the top limb of c0: there is no column 27
+    return prog
+
+
+def emit_fp2():
+    accs = ("C0", "C1", "T0", "T1")
+    o = ["FF_INLINE void %s(uint32_t* r0, uint32_t* r1, const uint32_t* a0, const uint32_t* a1, const uint32_t* b0, const uint32_t* b1) {" % FP2_FORM]
+    o.append("    int64_t C0 = 0;")
+    o.append("    uint64_t C1 = 0, T0, T1;")
+    o.append("    uint32_t sa[%d], sb[%d], m0[%d], m1[%d], t0[%d], t1[%d];" % ((L29,) * 6))
+    o.append("    _Pragma(\"unroll\") for (int i = 0; i < %d; i++) { sa[i] = a0[i] + a1[i]; sb[i] = b0[i] + b1[i]; }" % L29)
+    for step in fp2_schedule():
+        if step[0] == "mads":
+            fresh = {"T0": True, "T1": True, "C0": False, "C1": False}
+            for cur, ops in statements(step[1], 3):
+                used = [a for a in accs if any(c == a for c, _, _ in cur)]
+                cons = ", ".join(('"=&v"(%s)' if fresh[a] else '"+v"(%s)') % a for a in used)
+                lines = []
+                for c, l, r in cur:
+                    li, ri = len(used) + ops.index(l), len(used) + ops.index(r)
+                    lines.append("v_mad_u64_u32 %%%d, vcc, %%%d, %%%d, %s" % (used.index(c), li, ri, "0" if fresh[c] else "%%%d" % used.index(c)))
+                    fresh[c] = False
+                ins = ", ".join('"s"(0x%08xu)' % FP29_MOD[int(x[1:])] if x[0] == "P" else '"v"(%s)' % x for x in ops)
+                o.append('    asm("%s" : %s : %s : "vcc");' % ("\\n\\t".join(lines), cons, ins))
+        elif step[0] == "comb":
+            o.append("    C0 += (int64_t)(T0 - T1); C1 -= T0 + T1;")
+        elif step[0] == "addp":
+            o.append("    C0 += 0x%08x;" % FP29_MOD[step[1]])
+        elif step[0] == "addtop":
+            o.append("    t0[%d] += 0x%08xu;" % (L29 - 1, FP29_MOD[L29 - 1]))
+        elif step[0] == "digit":
+            _, c, k = step
+            o.append("    m%d[%d] = ((uint32_t)C%d * 0x%08xu) & 0x%08xu; C%d += (uint64_t)m%d[%d] * 0x%08xu; C%d >>= %d;"
+                     % (c, k, c, FP29_NINV, M29, c, c, k, FP29_MOD[0], c, W29))
+        else:
+            _, c, j = step
+            if j < L29 - 2:
+                o.append("    t%d[%d] = (uint32_t)C%d & 0x%08xu; C%d >>= %d;" % (c, j, c, M29, c, W29))
+            else:
+                o.append("    t%d[%d] = (uint32_t)C%d & 0x%08xu; t%d[%d] = (uint32_t)(C%d >> %d);" % (c, j, c, M29, c, j + 1, c, W29))
+    o.append("    _Pragma(\"unroll\") for (int i = 0; i < %d; i++) { r0[i] = t0[i]; r1[i] = t1[i]; }" % L29)
+    o.append("}")
+    return "\n".join(o)
+
+
+def fp2_model_run(vals):
+    """Replays fp2_schedule() on Python integers.  vals: a0, a1, b0, b1 -> 14 limbs.  Returns (c0 limbs, c1 limbs) and the ranges seen:
+    the largest unsigned accumulator (T0, T1, C1) and the smallest / largest value of the signed one (C0).  Asserts the 64-bit ranges at every step."""
+    env = dict(vals)
+    env["sa"] = [x + y for x, y in zip(vals["a0"], vals["a1"])]
+    env["sb"] = [x + y for x, y in zip(vals["b0"], vals["b1"])]
+    assert all(x < 1 << 32 for x in env["sa"] + env["sb"])
+    env["m0"], env["m1"] = [None] * L29, [None] * L29
+    acc = {"C0": 0, "C1": 0, "T0": 0, "T1": 0}
+    out = [[0] * L29, [0] * L29]
+    upeak, slo, shi = 0, 0, 0
+
+    def get(name):
+        if name[0] == "P":
+            return FP29_MOD[int(name[1:])]
+        arr, i = name[:-1].split("[")
+        return env[arr][int(i)]
+    for step in fp2_schedule():
+        if step[0] == "mads":
+            fresh = {"T0": True, "T1": True}
+            for c, l, r in step[1]:
+                x, y = get(l), get(r)
+                assert x < 1 << 32 and y < 1 << 32
+                if fresh.get(c):
+                    acc[c], fresh[c] = 0, False
+                acc[c] += x * y
+        elif step[0] == "comb":
+            acc["C0"] += acc["T0"] - acc["T1"]
+            acc["C1"] -= acc["T0"] + acc["T1"]
+        elif step[0] == "addp":
+            acc["C0"] += FP29_MOD[step[1]]
+        elif step[0] == "addtop":
+            out[0][L29 - 1] += FP29_MOD[L29 - 1]
+        elif step[0] == "digit":
+            _, c, k = step
+            a = "C%d" % c
+            m = (((acc[a] & 0xFFFFFFFF) * FP29_NINV) & 0xFFFFFFFF) & M29
+            env["m%d" % c][k] = m
+            acc[a] += m * FP29_MOD[0]
+            assert acc[a] & M29 == 0
+            acc[a] >>= W29          # Python's shift of a negative integer is arithmetic
+        else:
+            _, c, j = step
+            a = "C%d" % c
+            out[c][j] = acc[a] & M29
+            acc[a] >>= W29
+            if j == L29 - 2:
+                assert -(1 << 31) <= acc[a] < 1 << 31          # the top limb; negative only where c0 + p is (operand bounds beyond the contract)
+                out[c][j + 1] = acc[a]
+        upeak = max(upeak, acc["C1"], acc["T0"], acc["T1"])
+        slo, shi = min(slo, acc["C0"]), max(shi, acc["C0"])
+        assert acc["C1"] >= 0 and upeak < 1 << 64, "an unsigned accumulator leaves [0, 2^64)"
+        assert -(1 << 63) <= slo and shi < 1 << 63, "the signed accumulator leaves [-2^63, 2^63)"
+    return out, (upeak, slo, shi)
+
+
+def fp2_model_expected(vals):
+    """(c0 + p, c1) of the Montgomery product, as integers: exact values, not residues (the reductions are deterministic)."""
+    rinv = pow(1 << (W29 * L29), -1, FP)
+    a0, a1, b0, b1 = (limbs_value(vals[n]) for n in FP2_OPERANDS)
+    return [(a0 * b0 - a1 * b1) * rinv % FP, (a0 * b1 + a1 * b0) * rinv % FP]
+
+
+def fp2_extreme(bound):
+    """The largest weakly normalised operand below bound * p: limbs 0..12 at 2^29 + 7, the top limb as large as the bound lets it be."""
+    low = sum(WEAK << (W29 * i) for i in range(L29 - 1))
+    return [WEAK] * (L29 - 1) + [(bound * FP - 1 - low) >> (W29 * (L29 - 1))]
+
+
+def fp2_model_cases(bound, samples=0, seed=0x2F2):
+    """The sixteen corner patterns of {extreme, zero} per operand, all-extreme first (a1 b1 extreme beside a0 b0 = 0 is the most negative c0 chain, the
+    reverse the most positive); then `samples` sets of random weakly normalised limbs below bound * p."""
+    import random
+    rnd = random.Random(seed)
+    top, zero = fp2_extreme(bound), [0] * L29
+    cases = [dict(zip(FP2_OPERANDS, (top if (bits >> i) & 1 else zero for i in range(4)))) for bits in (15,) + tuple(range(15))]
+    for _ in range(samples):
+        cases.append({n: [rnd.randrange(WEAK + 1) for _ in range(L29 - 1)] + [rnd.randrange(top[-1] + 1)] for n in FP2_OPERANDS})
+    return cases
+
+
+FP2_REST = 64                 # ff.cuh: FP_REST, the bound of values at rest
+FP2_TYPE_MAX = 8192           # ff.cuh: FP_MAX_BOUND, the largest bound a register value's type can state
+
+
+def fp2_model_check(samples=64, seed=0x2F2):
+    """The one-lane Fp2 product: (1) at the largest limbs ANY typed operand can have (bound 8192 p, beyond the product's contract) every accumulator stays
+    inside its 64-bit range and the residues are right; (2) at the at-rest bound 64 p, and at 4096 p x 4096 p = the contract's limit 2 A B <= 2^25,
+    the outputs are moreover non-negative with exact limbs, c0 + p < 3p and c1 < 2p.
+    Returns (log2 of the largest unsigned accumulator, log2 of the largest magnitude of the signed one)."""
+    import math
+    upeak, smag = 0, 0
+    for bound, contract in ((FP2_TYPE_MAX, False), (FP2_REST, True), (4096, True)):
+        for vals in fp2_model_cases(bound, samples, seed):
+            out, (u, lo, hi) = fp2_model_run(vals)
+            upeak, smag = max(upeak, u), max(smag, -lo, hi)
+            for o, e in zip(out, fp2_model_expected(vals)):
+                assert limbs_value(o) % FP == e, (FP2_FORM, "wrong residue")
+                assert all(0 <= x <= M29 for x in o[:-1]), (FP2_FORM, "output limb not exact")
+            if contract:
+                assert 0 <= limbs_value(out[0]) < 3 * FP and 0 <= limbs_value(out[1]) < 2 * FP and out[0][-1] >= 0 and out[1][-1] >= 0
+    return math.log2(upeak), math.log2(smag)
+
+
+def fp2_output_bounds(A, B):
+    """Operand values below A p and B p: (c0 + p, c1) lie below these multiples of p.  c0 = (a0 b0 - a1 b1 + m p) / R with m < R, so
+    -A B p^2 / R < c0 < A B p^2 / R + p; c1 = (a0 b1 + a1 b0 + m p) / R < 2 A B p^2 / R + p."""
+    from fractions import Fraction
+    x = Fraction(A * B * FP, 1 << (W29 * L29))
+    assert x < 1, "c0 + p could be negative"
+    return 2 + x, 1 + 2 * x
+
+
+def gen_fp2_lane():
+    o = ["// GENERATED by scripts/gen_mont_mul.py -- do not edit.",
+         "// Montgomery product of Fp2 = Fp[u] / (u^2 + 1) on ONE lane (Fp: 14 x 29-bit limbs, R = 2^406): lazy Karatsuba, three base multiplications",
+         "// (a0 b0, a1 b1, (a0 + a1)(b0 + b1)) feeding two running reductions column by column, 5 x 196 multiply-adds.  r0 = c0 + p < 3p, r1 = c1 < 2p,",
+         "// exact limbs; the c0 accumulator is signed.  Outputs may alias inputs.  Ranges: the generator's integer model (fp2_model_check).",
+         "#pragma once", "#include <stdint.h>", "", "namespace zk {", "", emit_fp2(), "", "}  // namespace zk"]
+    return "\n".join(o) + "\n"
+
+
 def gen_fr_header():
     # the base field Fp no longer uses this scheme: radix 2^29, carry-free columns (ff.cuh, gen_fp29_consts.py)
     return ("// GENERATED by scripts/gen_mont_mul.py -- do not edit.\n#pragma once\n#include <stdint.h>\n\nnamespace zk {\n\n"
@@ -342,6 +549,7 @@ def gen_fr_header():
 def main():
     for form, bits in model_check().items():
         print("model: %s holds, largest column accumulator 2^%.3f" % (form, bits))
+    print("model: %s holds, largest unsigned accumulator 2^%.3f, signed accumulator within +-2^%.3f" % ((FP2_FORM,) + fp2_model_check()))
     if "--check" in sys.argv[1:]:
         return
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -352,6 +560,10 @@ def main():
     path = os.path.join(root, "zukelang_amd", "csrc", "fp_pair_gen.cuh")
     with open(path, "w") as f:
         f.write(gen_fp_pair())
+    print("wrote", path)
+    path = os.path.join(root, "zukelang_amd", "csrc", "fp2_lane_gen.cuh")
+    with open(path, "w") as f:
+        f.write(gen_fp2_lane())
     print("wrote", path)
 
 

@@ -29,7 +29,7 @@ EXPORTS = [
     "zk_groth16_vk_upload", "zk_pinocchio_vk_upload", "zk_vk_info", "zk_vk_free", "zk_groth16_verify_resident", "zk_pinocchio_verify_resident",
     "zk_groth16_verify_folded",
     "zk_profile_enable", "zk_profile_reset", "zk_profile_get", "zk_profile_names", "zk_profile_counter", "zk_sync",
-    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_group",
+    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_fp2_lanewise", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_group",
 ]
 
 
@@ -85,6 +85,7 @@ GROUP_PROTOTYPES = {
 # the paired field products' hook (tests/test_gpu_fp_paired.py)
 FP_PAIR_PROTOTYPES = {
     "zk_selftest_fp_paired": [C.POINTER(C.c_uint32), C.c_size_t, _P8],
+    "zk_selftest_fp2_lanewise": [C.POINTER(C.c_uint32), C.c_size_t, _P8],
 }
 KEY_FORMS = {"tau_powers": 0, "lagrange": 1}          # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
 

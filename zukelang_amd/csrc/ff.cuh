@@ -30,6 +30,7 @@
 #include "ff_mul_gen.cuh"
 #include "fp29_consts.cuh"
 #include "fp_pair_gen.cuh"
+#include "fp2_lane_gen.cuh"
 
 namespace zk {
 
@@ -864,6 +865,44 @@ template <int A> FF_INLINE Fp2HB<4> fe_sqr(const Fp2HB<A>& a) {
     for (int i = 0; i < FPL; i++) r.v[i] = c1 ? m.v[i] << 1 : m.v[i];
     fp_carry(r.v);
     return {r};
+}
+
+// TWO independent Fp2 products on a lane pair, one WHOLE product per lane: the even lane runs a b, the odd lane c d, both through the same instruction
+// stream -- the one-lane lazy-Karatsuba product of fp2_lane_gen.cuh, three base multiplications and two reductions, 5 x 196 multiply-adds per lane
+// and pair of products where two fe_mul above pay 2 x 588.  Operands and results stay in the component layout (lane 2k: c0, lane 2k+1: c1): only for
+// the duration of the product does a lane hold the four halves of ITS product, gathered with one select per limb whose partner-side source is the
+// DPP quad_perm(1,0,3,2) view of the register (a DPP row or bank mask cannot tell the two lanes of a pair apart: banks are four lanes wide).
+// Results: c0 + p < 3p, c1 < 2p (the generator's fp2_output_bounds), exact limbs.
+struct Fp2HPair {
+    Fp2HB<3> first, second;
+};
+FF_INLINE uint32_t pair_partner(uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true); }
+template <int A, int B, int C, int D> FF_INLINE Fp2HPair fe_mul2_lanewise(const Fp2HB<A>& a, const Fp2HB<B>& b, const Fp2HB<C>& c, const Fp2HB<D>& d) {
+    static_assert(2ll * A * B <= FP_MUL_BUDGET && 2ll * C * D <= FP_MUL_BUDGET, "operand bounds exceed the Montgomery headroom of the one-lane Fp2 product");
+    const bool odd = pair_comp() != 0;
+    uint32_t x0[FPL], x1[FPL], y0[FPL], y1[FPL], r0[FPL], r1[FPL];
+#pragma unroll
+    for (int i = 0; i < FPL; i++) {          // even lane: (a.c0, a.c1, b.c0, b.c1)   odd lane: (c.c0, c.c1, d.c0, d.c1)
+        const uint32_t pa = pair_partner(a.v.v[i]), pb = pair_partner(b.v.v[i]), pc = pair_partner(c.v.v[i]), pd = pair_partner(d.v.v[i]);          // both lanes execute every move
+        x0[i] = odd ? pc : a.v.v[i];
+        x1[i] = odd ? c.v.v[i] : pa;
+        y0[i] = odd ? pd : b.v.v[i];
+        y1[i] = odd ? d.v.v[i] : pb;
+    }
+    fp2_mul_lane_limbs(r0, r1, x0, x1, y0, y1);
+    Fp2HPair r;
+#pragma unroll
+    for (int i = 0; i < FPL; i++) {          // back to the component layout: (a b).c1 comes from the even lane, (c d).c0 from the odd one
+        const uint32_t p0 = pair_partner(r0[i]), p1 = pair_partner(r1[i]);
+        r.first.v.v[i] = odd ? p1 : r0[i];
+        r.second.v.v[i] = odd ? r1[i] : p0;
+    }
+    return r;
+}
+// a b - c d on the same pair of products: Y3 = R (Q - X3) - Y1 PPP, the end of a mixed addition
+template <int A, int B, int C, int D> FF_INLINE Fp2HB<3 + fp_ks(3)> fe_mul2_sub_lanewise(const Fp2HB<A>& a, const Fp2HB<B>& b, const Fp2HB<C>& c, const Fp2HB<D>& d) {
+    const Fp2HPair m = fe_mul2_lanewise(a, b, c, d);
+    return fe_sub(m.first, m.second);
 }
 
 // a b - c d.  For Fp as ONE fused double product a b + (K p - c) d (one Montgomery reduction instead of

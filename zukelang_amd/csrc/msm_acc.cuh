@@ -60,8 +60,10 @@ template <class F> struct ZPark {
         asm volatile("" ::: "memory");
     }
 };
-// xyzz_madd_impl<F, false> (ec.cuh) with acc = (ax, ay, park[0], park[1]): the same operations in the same order on the same values
+// xyzz_madd_impl<F, false> (ec.cuh) with acc = (ax, ay, park[0], park[1]): the same values, with the eight Fp2 products taken as four independent
+// pairs (U2 | S2, PPP | Q, R (Q - X3) | Y1 PPP, ZZ PP | ZZZ PPP), each pair as one whole lazy-Karatsuba product per lane (ff.cuh: fe_mul2_lanewise)
 template <class F> FF_INLINE void xyzz_madd_parked(F& ax, F& ay, ZPark<F>& pk, const Aff<F>& q) {
+    static_assert(std::is_same<F, Fp2H>::value, "the parked accumulator serves G2 on lane pairs");
     {
         const F zz = pk.get(0);
         if (fe_is_zero(zz)) {                            // the accumulator is the identity
@@ -72,10 +74,9 @@ template <class F> FF_INLINE void xyzz_madd_parked(F& ax, F& ay, ZPark<F>& pk, c
             return;
         }
     }
-    const auto U2 = fe_mul(q.x, pk.get(0));
-    const auto S2 = fe_mul(q.y, pk.get(1));
-    const auto P = fe_sub(U2, ax);
-    const auto R = fe_sub(S2, ay);
+    const auto US = fe_mul2_lanewise(q.x, pk.get(0), q.y, pk.get(1));          // U2 | S2
+    const auto P = fe_sub(US.first, ax);
+    const auto R = fe_sub(US.second, ay);
     if (fe_is_zero(P)) {
         Xyzz<F> t{ax, ay, pk.get(0), pk.get(1)};
         xyzz_madd_equal_x(t, fe_is_zero(R));
@@ -86,14 +87,14 @@ template <class F> FF_INLINE void xyzz_madd_parked(F& ax, F& ay, ZPark<F>& pk, c
         return;
     }
     const auto PP = fe_sqr(P);
-    const auto PPP = fe_mul(P, PP);
-    const auto Q = fe_mul(ax, PP);
-    const auto X3 = fe_sub_sub_dbl(fe_sqr(R), PPP, Q);
-    const auto Y3 = fe_mul_sub(R, fe_sub(Q, X3), ay, PPP);
+    const auto PQ = fe_mul2_lanewise(P, PP, ax, PP);                            // PPP | Q
+    const auto X3 = fe_sub_sub_dbl(fe_sqr(R), PQ.first, PQ.second);
+    const auto Y3 = fe_mul2_sub_lanewise(R, fe_sub(PQ.second, X3), ay, PQ.first);
     ax = X3;
     ay = Y3;
-    pk.put(0, F(fe_mul(pk.get(0), PP)));
-    pk.put(1, F(fe_mul(pk.get(1), PPP)));
+    const auto ZZ = fe_mul2_lanewise(pk.get(0), PP, pk.get(1), PQ.first);      // ZZ PP | ZZZ PPP
+    pk.put(0, F(ZZ.first));
+    pk.put(1, F(ZZ.second));
 }
 
 // RAW = false: the sorted entries are table references (index | sign).  RAW = true (the finisher of the batch-affine rounds,
