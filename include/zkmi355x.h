@@ -486,6 +486,34 @@ int zk_pinocchio_verify_resident(uint64_t handle, const uint8_t* io_scalars /* c
  *   pairing_miller, verify_fold_tree, msm_short, pairing_final_exp, verify_fold_pow. */
 int zk_groth16_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 384 */,
                              const uint8_t* rho /* count * 16 */, uint32_t count, int* all_ok, int32_t* status /* count, may be NULL */);
+/* The same one answer under a resident Pinocchio key.  Verify.f (pinocchio.ml:254-420) decides five equations per proof -- the vv check (285), the ww
+ * check (298), the yy check (311), the bvwy check (361-366) and divisibility (418-420).  Equation e of proof i is raised to a coefficient rho_ie, all
+ * of them are multiplied, and the pairs are collected by their fixed key point:
+ *     prod_i e([rho_i4](vio_i + vv_i), wio_i + ww_i)
+ *       . e(S_av, av) e(-(S_one2 + S_yio), one2) e(S_ay, ay) e(S_gm2, gm2) e(-S_bgm2, bgm2) e(-S_yt, yt) . e(aw, T_aw) e(-one, T_one) e(-bgm, T_bgm) = 1
+ *     S_av = sum_i [rho_i0] vv_i     S_one2 = sum_i ([rho_i0] vavv_i + [rho_i2] yayy_i + [rho_i4] yy_i)     S_ay = sum_i [rho_i2] yy_i
+ *     S_gm2 = sum_i [rho_i3] bvwy_i  S_bgm2 = sum_i [rho_i3](vv_i + yy_i)   S_yt = sum_i [rho_i4] h_i    S_yio = sum_k t_k yy_io_k, t_k = sum_i rho_i4 w_ik
+ *     T_aw = sum_i [rho_i1] ww_i     T_one = sum_i [rho_i1] waww_i          T_bgm = sum_i [rho_i3] ww_i   (G2)
+ * with vio_i, wio_i the sums over the public inputs as the per-proof call forms them.  Per proof one Miller loop and two short products instead of
+ * thirteen Miller loops, five final exponentiations and three short products; per batch nine Miller loops and one final exponentiation, and no power
+ * in GT: the right-hand side is 1.  status[i] is byte for byte what zk_pinocchio_verify_resident reports for proof i; a proof with a non-zero status
+ * enters nothing (no pair, no summand, no share of t).  *all_ok = 1 if and only if every status is 0 and the folded equation holds.
+ *   THE CONTRACT FOR rho.  FIVE coefficients per proof, rho_i0 .. rho_i4, one per equation in the order above, 16 bytes each, little-endian, every
+ *   one non-zero.  The caller draws all of them from a cryptographic generator AFTER the proofs are fixed, and keeps them unpredictable to whoever
+ *   made the proofs.  A batch that holds a bad proof then passes with probability at most 2^-128.  With coefficients known or chosen in advance a bad
+ *   batch CAN pass, in two ways (tests/test_gpu_pinocchio_verify_folded.py shows both): ACROSS proofs -- vavv of two proofs moved by +D and -D cancels
+ *   when rho_00 = rho_10 -- and INSIDE one proof -- vavv moved by +D and yayy by -D both meet one2 and cancel when rho_i0 = rho_i2.  The second way is
+ *   why a proof has five independent coefficients and not one: with one, a single proof could trade an error of one equation against another's.
+ *   vk_handle: from zk_pinocchio_vk_upload.  Refused before the device is touched, with ZK_ERR_ARG: all_ok, proofs or rho null (count > 0), a zero
+ *   among the 5 count coefficients, count > 2^24.  Then a Groth16, freed or unknown handle -> ZK_ERR_HANDLE (a non-zero handle without a usable GPU:
+ *   ZK_ERR_HIP); count = 0 -> ZK_OK, *all_ok = 1, nothing else touched; io_scalars null with n_io > 0 -> ZK_ERR_ARG.  More than 8192 proofs are
+ *   folded slab by slab into state kept on the device; the equation is decided once.  Kernel families: verify_point_checks, msm_short,
+ *   verify_fold_scale (the G1 multiples, every sum, the scalars), verify_fold_scale_g2 (the G2 multiples), pairing_miller, verify_fold_tree,
+ *   pairing_final_exp.  Measured on an MI355X against zk_pinocchio_verify_resident: faster at 4096 and 16384 proofs, slower at 256 and
+ *   below. */
+int zk_pinocchio_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 960 */,
+                               const uint8_t* rho /* count * 80: rho_i0 .. rho_i4, 16 B little-endian each */, uint32_t count,
+                               int* all_ok, int32_t* status /* count, may be NULL */);
 
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------
  * With profiling on, kernel families are bracketed by HIP events on the stream they run on;
@@ -559,6 +587,12 @@ int zk_selftest_group(int group, int form, int rep, const uint8_t* a, const uint
  * refusals as the call itself; count = 0 or a null output -> ZK_ERR_ARG. */
 int zk_selftest_groth16_fold(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count,
                              uint8_t lhs_gt[576], uint8_t rhs_gt[576], uint8_t sum_c[96], uint8_t sum_io[96], int32_t* status);
+/* zk_pinocchio_verify_folded stopped before the comparison (tests/test_gpu_pinocchio_verify_folded.py): lhs_gt = the final exponentiation of the
+ * product of all count + 9 Miller values, and the ten sums that enter the key's pairs, un-negated, uncompressed (the identity as the library encodes
+ * it): sums_g1 = S_av | S_one2 (the proofs' part only, without S_yio) | S_ay | S_gm2 | S_bgm2 | S_yt | S_yio, sums_g2 = T_aw | T_one | T_bgm.  Same
+ * arguments and refusals as the call itself; count = 0 or a null output -> ZK_ERR_ARG. */
+int zk_selftest_pinocchio_fold(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count,
+                               uint8_t lhs_gt[576], uint8_t sums_g1[7 * 96], uint8_t sums_g2[3 * 192], int32_t* status);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

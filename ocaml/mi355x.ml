@@ -313,6 +313,18 @@ let zk_selftest_groth16_fold =
     (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes
    @-> ptr int32_t @-> returning int)
 
+(* The same question under a resident Pinocchio key (zk_pinocchio_verify_folded): rho holds FIVE coefficients per proof, one per equation of Verify.f,
+   16 bytes each, every one non-zero, drawn AFTER the proofs are fixed and unpredictable to whoever made them. *)
+let zk_pinocchio_verify_folded =
+  fn "zk_pinocchio_verify_folded"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ptr int @-> ptr int32_t @-> returning int)
+
+(* the same stopped before the comparison: the left-hand side as GT bytes, the seven G1 sums and the three G2 sums as points (the test suite's hook) *)
+let zk_selftest_pinocchio_fold =
+  fn "zk_selftest_pinocchio_fold"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> ptr int32_t
+   @-> returning int)
+
 let vk_free (h : Unsigned.UInt64.t) = ignore (zk_vk_free h)
 
 let groth16_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =

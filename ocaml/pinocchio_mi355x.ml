@@ -341,6 +341,32 @@ module Make (C : Curve.S) = struct
       Mi355x.(check (zk_pinocchio_verify_resident t.handle (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
       List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
 
+    (* Are ALL of these proofs good?  One folded pairing equation for the list (zk_pinocchio_verify_folded) instead of five per proof.  FIVE
+       coefficients per proof, one per equation of Verify.f, are drawn HERE, from `rng`, after the proofs are in hand: 16 bytes each, the low half of
+       an Fr.gen (uniform up to 2^-127), a zero drawn again.  `rng` must be unpredictable to whoever made the proofs -- a seeded test generator is
+       not; with known coefficients a bad list, or one bad proof, can be made to pass.  false: some proof is bad, and verify_many says which. *)
+    let verify_all rng (t : t) (jobs : (Fr.t Var.Map.t * proof) list) : bool =
+      List.iter (fun (ios, _) -> assert (Var.Set.equal (Var.Map.domain ios) t.domain)) jobs;
+      let count = List.length jobs in
+      let rec draw () =
+        let b = Bytes.sub (Fr.to_bytes (Fr.gen rng)) 0 16 in
+        if Bytes.equal b (Bytes.make 16 (Char.chr 0)) then draw () else b
+      in
+      let rho = Mi355x.cat (List.init (5 * count) (fun _ -> draw ())) in
+      let io_all = fr_bytes (List.concat_map (fun (ios, _) -> values ios) jobs) in
+      let proofs =
+        Mi355x.cat
+          (List.concat_map
+             (fun (_, (p : proof)) ->
+               [ G1.to_bytes p.vv; G2.to_bytes p.ww; G1.to_bytes p.yy; G1.to_bytes p.h; G1.to_bytes p.vavv; G2.to_bytes p.waww;
+                 G1.to_bytes p.yayy; G1.to_bytes p.bvwy ])
+             jobs)
+      in
+      let all_ok = Ctypes.allocate Ctypes.int 0 in
+      Mi355x.(
+        check (zk_pinocchio_verify_folded t.handle (bytes_start io_all) (bytes_start proofs) (bytes_start rho) (u32 count) all_ok no_status));
+      Ctypes.( !@ ) all_ok <> 0
+
     let free (t : t) = Mi355x.vk_free t.handle
   end
 

@@ -183,54 +183,97 @@ __global__ void k_vk_compare(const uint8_t* __restrict__ gt, const uint8_t* __re
 }
 
 // ------------------------------------------------------------------ the folded verifier's kernels
-// Lane j < count: point `pa` of item j -> [rho_j] P as dense affine in out_aff[j]; lane count + j: point `px` of item j -> [rho_j] P as dense XYZZ in
-// out_xyzz[j].  pts: per_item dense affine points per item; rho: four little-endian words per item.  Items that are not live give the identity (zero
-// bytes) and their points are not read.  xyzz_dbl / xyzz_madd are the complete ones: P may be the identity, and nothing is assumed of rho.
-__global__ __launch_bounds__(64) void k_fold_scale(const uint8_t* __restrict__ pts, uint32_t per_item, uint32_t pa, uint32_t px, const uint32_t* __restrict__ rho,
-                                                   const uint8_t* __restrict__ live, uint32_t count, uint8_t* __restrict__ out_aff, uint8_t* __restrict__ out_xyzz) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= 2 * count) return;
-    const bool second = j >= count;
-    const uint32_t i = second ? j - count : j;
-    Xyzz<Fp> acc = xyzz_inf<Fp>();
+// The scaling stage of both folds, one lane per (item, job).  A job takes a base point of item i -- point `pt` of its per_item dense affine points,
+// plus point `add` of the same item (FOLD_ADD_IO: plus io[i], a sum over the public inputs as dense XYZZ; FOLD_NONE: nothing) -- multiplies it by
+// coefficient `rho` of the item's rho_per_item (16 B little-endian each; FOLD_NONE: by 1) and writes the result to out_aff[i] as dense affine (dst
+// FOLD_NONE) or to segment dst of out_xyzz as dense XYZZ.  Segment d holds count + 1 points: the items' and, behind them, the running sum carry[d] of
+// the earlier slabs, which the lanes past the jobs copy there, so that one tree of k_fold_sum adds everything.  Lanes are job-major: the lanes of a
+// wave share their job.  Items that are not live give the identity (zero bytes) and their points are not read.  xyzz_dbl / xyzz_madd are the complete
+// ones: a base may be the identity (vio + vv = O, vv + yy = O), and nothing is assumed of rho.
+enum : uint8_t { FOLD_NONE = 0xff, FOLD_ADD_IO = 0xfe };
+struct FoldJob { uint8_t pt, add, rho, dst; };
+struct FoldPlan {
+    uint32_t njobs, per_item, rho_per_item, nseg;
+    FoldJob job[9];
+};
+// Groth16 (a1 = A | C): [rho] A -> affine, [rho] C -> segment 0
+static const FoldPlan FOLD_GROTH16 = {2, 2, 1, 1, {{0, FOLD_NONE, 0, FOLD_NONE}, {1, FOLD_NONE, 0, 0}}};
+// Pinocchio, G1 (a1 = vv yy h vavv yayy bvwy): the eight segments are S_av | S_one2 in its three parts | S_ay | S_gm2 | S_bgm2 | S_yt, then the Miller
+// loop's [rho_4](vio + vv)
+static const FoldPlan FOLD_PINOCCHIO_G1 = {9, 6, 5, 8, {{0, FOLD_NONE, 0, 0}, {3, FOLD_NONE, 0, 1}, {4, FOLD_NONE, 2, 2}, {1, FOLD_NONE, 4, 3}, {1, FOLD_NONE, 2, 4},
+                                                        {5, FOLD_NONE, 3, 5}, {0, 1, 3, 6}, {2, FOLD_NONE, 4, 7}, {0, FOLD_ADD_IO, 4, FOLD_NONE}}};
+// Pinocchio, G2 (a2 = ww waww): T_aw | T_one | T_bgm, then the Miller loop's wio + ww
+static const FoldPlan FOLD_PINOCCHIO_G2 = {4, 2, 5, 3, {{0, FOLD_NONE, 1, 0}, {1, FOLD_NONE, 1, 1}, {0, FOLD_NONE, 3, 2}, {0, FOLD_ADD_IO, FOLD_NONE, FOLD_NONE}}};
+template <class F>
+__global__ __launch_bounds__(64) void k_fold_scale(const uint8_t* __restrict__ pts, FoldPlan p, const uint8_t* __restrict__ io, const uint32_t* __restrict__ rho,
+                                                   const uint8_t* __restrict__ live, uint32_t count, const uint8_t* __restrict__ carry, uint8_t* __restrict__ out_aff,
+                                                   uint8_t* __restrict__ out_xyzz) {
+    constexpr size_t AB = FieldOps<F>::WORDS * 8, XB = FieldOps<F>::WORDS * 16;          // a dense affine point, a dense XYZZ point
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, jobs = (uint64_t)p.njobs * count;
+    if (j >= jobs + p.nseg) return;
+    if (j >= jobs) {
+        const uint32_t d = (uint32_t)(j - jobs);
+        xyzz_store<F>(out_xyzz + XB * ((size_t)(count + 1) * d + count), xyzz_load<F>(carry + XB * d));
+        return;
+    }
+    const FoldJob job = p.job[j / count];
+    const uint32_t i = (uint32_t)(j % count);
+    Xyzz<F> acc = xyzz_inf<F>();
     if (live[i]) {
-        const Aff<Fp> P = aff_load<Fp>(pts + 96 * ((size_t)per_item * i + (second ? px : pa)));
-        const uint4 e = reinterpret_cast<const uint4*>(rho)[i];
-        const uint32_t w[4] = {e.x, e.y, e.z, e.w};
-        for (int b = 127; b >= 0; b--) {
-            acc = xyzz_dbl(acc);
-            if ((w[b >> 5] >> (b & 31)) & 1) xyzz_madd(acc, P);
+        Aff<F> P = aff_load<F>(pts + AB * ((size_t)p.per_item * i + job.pt));
+        if (job.add != FOLD_NONE) {
+            acc = job.add == FOLD_ADD_IO ? xyzz_load<F>(io + XB * (size_t)i) : xyzz_from_aff(aff_load<F>(pts + AB * ((size_t)p.per_item * i + job.add)));
+            xyzz_madd(acc, P);
+            if (job.rho != FOLD_NONE) {
+                P = xyzz_to_aff(acc);
+                acc = xyzz_inf<F>();
+            }
+        } else if (job.rho == FOLD_NONE) acc = xyzz_from_aff(P);
+        if (job.rho != FOLD_NONE) {
+            const uint4 e = reinterpret_cast<const uint4*>(rho)[(size_t)p.rho_per_item * i + job.rho];
+            const uint32_t w[4] = {e.x, e.y, e.z, e.w};
+            for (int b = 127; b >= 0; b--) {
+                acc = xyzz_dbl(acc);
+                if ((w[b >> 5] >> (b & 31)) & 1) xyzz_madd(acc, P);
+            }
         }
     }
-    if (second) xyzz_store<Fp>(out_xyzz + 192 * (size_t)i, acc);
-    else aff_store<Fp>(out_aff + 96 * (size_t)i, xyzz_to_aff(acc));
+    if (job.dst == FOLD_NONE) aff_store<F>(out_aff + AB * (size_t)i, xyzz_to_aff(acc));
+    else xyzz_store<F>(out_xyzz + XB * ((size_t)(count + 1) * job.dst + i), acc);
 }
-// out[blockIdx.x] = the sum of in[64 blockIdx.x ...] (dense XYZZ, at most 64 of the n): every lane takes one point (the identity past the end), then
-// the wave halves them in LDS.  The additions are the complete xyzz_add: equal summands (a proof repeated with the same rho) and opposite ones occur.
+// Segment blockIdx.y: out[out_stride y + blockIdx.x] = the sum of in[in_stride y + 64 blockIdx.x ...] (dense XYZZ, at most 64 of the segment's n; the
+// strides count points): every lane takes one point (the identity past the end), then the wave halves them in LDS -- 16 KiB of raw points in G1,
+// 32 KiB in G2, both under the 64 KiB a kernel may declare.  The additions are the complete xyzz_add: equal summands (a proof repeated with the same
+// rho) and opposite ones occur.
 static constexpr uint32_t FOLD_SUM_THREADS = 64;
-__global__ __launch_bounds__(FOLD_SUM_THREADS) void k_fold_sum(const uint8_t* __restrict__ in, uint32_t n, uint8_t* __restrict__ out) {
-    constexpr int XB = RawLayout<Fp>::XYZZ;
-    __shared__ __attribute__((aligned(16))) uint8_t lds[FOLD_SUM_THREADS * XB];
+template <class F>
+__global__ __launch_bounds__(FOLD_SUM_THREADS) void k_fold_sum(const uint8_t* __restrict__ in, uint32_t n, uint32_t in_stride, uint8_t* __restrict__ out, uint32_t out_stride) {
+    constexpr int RB = RawLayout<F>::XYZZ;
+    constexpr size_t XB = FieldOps<F>::WORDS * 16;
+    static_assert(FOLD_SUM_THREADS * RB <= 65536, "k_fold_sum: the raw points of one workgroup must fit the static LDS limit");
+    __shared__ __attribute__((aligned(16))) uint8_t lds[FOLD_SUM_THREADS * RB];
     const uint32_t t = threadIdx.x, i = blockIdx.x * FOLD_SUM_THREADS + t;
-    Xyzz<Fp> acc = xyzz_inf<Fp>();
-    if (i < n) acc = xyzz_load<Fp>(in + 192 * (size_t)i);
-    xyzz_store_raw(lds + XB * t, acc);
+    Xyzz<F> acc = xyzz_inf<F>();
+    if (i < n) acc = xyzz_load<F>(in + XB * ((size_t)in_stride * blockIdx.y + i));
+    xyzz_store_raw(lds + RB * t, acc);
     __syncthreads();
     for (uint32_t h = FOLD_SUM_THREADS / 2; h > 0; h >>= 1) {          // the bound is the workgroup's: every lane meets every barrier
         if (t < h) {
-            const Xyzz<Fp> q = xyzz_load_raw<Fp>(lds + XB * (t + h));
+            const Xyzz<F> q = xyzz_load_raw<F>(lds + RB * (t + h));
             xyzz_add(acc, q);
-            xyzz_store_raw(lds + XB * t, acc);
+            xyzz_store_raw(lds + RB * t, acc);
         }
         __syncthreads();
     }
-    if (t == 0) xyzz_store<Fp>(out + 192 * (size_t)blockIdx.x, acc);
+    if (t == 0) xyzz_store<F>(out + XB * ((size_t)out_stride * blockIdx.y + blockIdx.x), acc);
 }
 // Workgroup k < n: t[k] += sum over the live items i of rho_i w[i n + k] (mod r); workgroup n: S += sum of the live rho_i (mod r; as an integer the sum
-// stays below 2^152 < r) and *dead += the items that are not live.  w: canonical scalars (a live item's are: the range test ran), t and S canonical too.
+// stays below 2^152 < r; skipped when S is null) and *dead += the items that are not live.  rho_i = coefficient rho_at of the item's rho_per_item.
+// w: canonical scalars (a live item's are: the range test ran), t and S canonical too.
 static constexpr uint32_t FOLD_FR_THREADS = 256;
-__global__ __launch_bounds__(FOLD_FR_THREADS) void k_fold_fr(const uint32_t* __restrict__ w, uint32_t n, const uint32_t* __restrict__ rho, const uint8_t* __restrict__ live,
-                                                             uint32_t count, uint32_t* __restrict__ t, uint32_t* __restrict__ S, uint32_t* __restrict__ dead) {
+__global__ __launch_bounds__(FOLD_FR_THREADS) void k_fold_fr(const uint32_t* __restrict__ w, uint32_t n, const uint32_t* __restrict__ rho, uint32_t rho_per_item,
+                                                             uint32_t rho_at, const uint8_t* __restrict__ live, uint32_t count, uint32_t* __restrict__ t,
+                                                             uint32_t* __restrict__ S, uint32_t* __restrict__ dead) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[FOLD_FR_THREADS * 8];
     __shared__ uint32_t ndead;
     const uint32_t k = blockIdx.x, lane = threadIdx.x;
@@ -240,7 +283,7 @@ __global__ __launch_bounds__(FOLD_FR_THREADS) void k_fold_fr(const uint32_t* __r
     uint32_t mine = 0;
     for (uint32_t i = lane; i < count; i += FOLD_FR_THREADS) {
         if (!live[i]) { mine++; continue; }
-        const uint4 e = reinterpret_cast<const uint4*>(rho)[i];
+        const uint4 e = reinterpret_cast<const uint4*>(rho)[(size_t)rho_per_item * i + rho_at];
         Fr r = fe_zero<FrParams>();
         r.v[0] = e.x; r.v[1] = e.y; r.v[2] = e.z; r.v[3] = e.w;
         if (k < n) r = fe_mul(fe_to_mont(r), fe_load<FrParams>(w + 8 * ((size_t)n * i + k)));          // (rho R) w R^-1 = rho w
@@ -258,7 +301,7 @@ __global__ __launch_bounds__(FOLD_FR_THREADS) void k_fold_fr(const uint32_t* __r
     }
     if (lane == 0) {
         uint32_t* dst = k < n ? t + 8 * (size_t)k : S;
-        fe_store(dst, fe_add(acc, fe_load<FrParams>(dst)));
+        if (dst) fe_store(dst, fe_add(acc, fe_load<FrParams>(dst)));
         if (k == n) *dead += ndead;
     }
 }
@@ -271,6 +314,38 @@ __global__ __launch_bounds__(64) void k_fold_key_pairs(const uint8_t* __restrict
     aff_store<Fp>(q1 + 96 * i, g1_negated(xyzz_to_aff(xyzz_load<Fp>(p + 192 * i))));
     copy_point<192>(q2 + 192 * i, key2 + 192 * i);
     off[i] = 3 * i;
+}
+// Pinocchio's nine pairs of the key's side, one lane each, in the order of the folded equation (include/zkmi355x.h):
+//   (S_av, av) (-(S_one2 + S_yio), one2) (S_ay, ay) (S_gm2, gm2) (-S_bgm2, bgm2) (-S_yt, yt) | (aw, T_aw) (-one, T_one) (-bgm, T_bgm)
+// s1: the eight running sums of FOLD_PINOCCHIO_G1's segments, s2: the three of FOLD_PINOCCHIO_G2's (dense XYZZ).  sums: seven dense XYZZ points
+// S_av | S_one2 | S_ay | S_gm2 | S_bgm2 | S_yt | S_yio; the last is there already (the short product's), the first six are written here, un-negated, S_one2
+// as the proofs' part alone -- its three parts and S_yio are added by the complete addition.  Negations are done as points.  off: the offsets of ONE
+// product over the ten Miller values that lie together (the running product, then these nine).
+__global__ __launch_bounds__(64) void k_fold_key_pairs_pinocchio(const uint8_t* __restrict__ s1, const uint8_t* __restrict__ s2, const uint8_t* __restrict__ key1,
+                                                                 const uint8_t* __restrict__ key2, uint8_t* __restrict__ sums, uint8_t* __restrict__ q1,
+                                                                 uint8_t* __restrict__ q2, uint32_t* __restrict__ off) {
+    const uint32_t i = threadIdx.x;
+    if (i >= 9) return;
+    if (i < 2) off[i] = 10 * i;
+    if (i < 6) {
+        const uint32_t seg = i == 0 ? 0 : i + 2;                 // S_one2 takes segments 1, 2, 3
+        const uint32_t k2 = i == 0 ? 1 : i == 1 ? 0 : i;         // key2 = one2 | av | ay | gm2 | bgm2 | yt
+        Xyzz<Fp> s = xyzz_load<Fp>(s1 + 192 * (i == 1 ? 1 : seg));
+        if (i == 1) {
+            xyzz_add(s, xyzz_load<Fp>(s1 + 192 * 2));
+            xyzz_add(s, xyzz_load<Fp>(s1 + 192 * 3));
+        }
+        xyzz_store<Fp>(sums + 192 * i, s);
+        if (i == 1) xyzz_add(s, xyzz_load<Fp>(sums + 192 * 6));
+        const Aff<Fp> a = xyzz_to_aff(s);
+        aff_store<Fp>(q1 + 96 * i, i == 1 || i >= 4 ? g1_negated(a) : a);
+        copy_point<192>(q2 + 192 * i, key2 + 192 * k2);
+    } else {
+        const uint32_t k1 = i == 6 ? 1 : i == 7 ? 0 : 2;         // key1 = one | aw | bgm
+        const Aff<Fp> a = aff_load<Fp>(key1 + 96 * k1);
+        aff_store<Fp>(q1 + 96 * i, i == 6 ? a : g1_negated(a));
+        aff_store<Fp2>(q2 + 192 * i, xyzz_to_aff(xyzz_load<Fp2>(s2 + 384 * (i - 6))));
+    }
 }
 // *all_ok = 1 iff no item was rejected, `want` was an element of Fp12 and the 576 bytes of both sides agree
 __global__ void k_fold_verdict(const uint8_t* __restrict__ lhs, const uint8_t* __restrict__ rhs, const uint32_t* __restrict__ dead, const uint32_t* __restrict__ bad,
@@ -304,9 +379,10 @@ struct ResidentVk {
     DevBuf in, b1, b2, a1, a2, verdict, flags, sums, q1, q2, off, miller, gt;
     uint8_t* host = nullptr;                  // pinned: [proofs | scalars | rho] in, [ok | code | all_ok] out
     size_t host_bytes = 0;
-    // the folded verifier (Groth16): workspaces for `fold_cap` proofs, and the state a call carries from slab to slab
+    // the folded verifier: workspaces for `fold_cap` proofs, and the state a call carries from slab to slab
     uint32_t fold_cap = 0;
-    DevBuf fa, fc, fsum, fm, fm2, fold;       // [rho] A dense affine | [rho] C and the running sum, XYZZ | partial sums | Miller values | tree levels | FoldState
+    DevBuf fa, fc, fsum, fm, fm2, fold;       // the Miller loops' G1 points, dense affine | the G1 multiples and the running sums, XYZZ segments | partial sums | Miller values | tree levels | the state
+    DevBuf fa2, fc2;                          // Pinocchio: the Miller loops' G2 points | the G2 multiples and the running sums
     ~ResidentVk() {
         for (const std::vector<ShortBases*>& list : io)
             for (ShortBases* b : list) short_bases_free(b);
@@ -328,6 +404,22 @@ enum : size_t {
     F_T = F_BYTES + 192,                      // t: n_io x 32 B
 };
 static_assert(F_SUMS % 16 == 0 && F_T % 16 == 0, "the state's points and scalars are read 16 bytes at a time");
+// The same for a Pinocchio key (everything from PF_SUMS1 on is zeroed when a call begins)
+enum : size_t {
+    PF_MILLER = 0,                            // ten raw Miller values: the running product, then the nine key pairs'
+    PF_SUMS1 = 10 * PAIRING_RAW_BYTES,        // the running sums of FOLD_PINOCCHIO_G1's eight segments, XYZZ
+    PF_SUMS2 = PF_SUMS1 + 8 * 192,            // ... of FOLD_PINOCCHIO_G2's three
+    PF_OUT1 = PF_SUMS2 + 3 * 384,             // S_av | S_one2 | S_ay | S_gm2 | S_bgm2 | S_yt | S_yio, XYZZ (k_fold_key_pairs_pinocchio)
+    PF_OFF = PF_OUT1 + 7 * 192,               // the offsets of the one product: 0, 10
+    PF_DEAD = PF_OFF + 8,                     // rejected proofs so far
+    PF_BAD = PF_DEAD + 4,                     // stays 0: `want` is the encoding of 1
+    PF_ONE = PF_BAD + 4,                      // a `live` byte for the one short product (16 B with its padding)
+    PF_GT = PF_ONE + 16,                      // lhs, 576 B
+    PF_BYTES = PF_GT + 576,                   // the ten sums in the ABI's encoding: 7 x 96 B, then 3 x 192 B
+    PF_T = PF_BYTES + 7 * 96 + 3 * 192,       // t: n_io x 32 B
+};
+static_assert(PF_SUMS1 % 16 == 0 && PF_OFF % 16 == 0 && PF_T % 16 == 0, "the state's points and scalars are read 16 bytes at a time");
+static constexpr size_t FOLD_RHO_BYTES[2] = {16, 80};          // per proof, by protocol: one coefficient / five
 static const VkPlan& plan_of(const ResidentVk& k) { return k.protocol == 0 ? PLAN_GROTH16 : PLAN_PINOCCHIO; }
 
 // a range of its own (handle_table.h); like resident bases, a live verification key pins the device list
@@ -400,9 +492,9 @@ static int vk_reserve(ResidentVk& k, uint32_t c, hipStream_t s) {
     if (c <= k.cap) return ZK_OK;
     HIPCHK(hipStreamSynchronize(s));
     const VkPlan& p = plan_of(k);
-    // what the folded call adds (Groth16 keys only; a Pinocchio key's workspaces are what they were): 16 B of rho per proof, all_ok behind the codes
-    const size_t fold = k.protocol == 0 ? 1 : 0;
-    const size_t n = c, in_bytes = ((size_t)p.stride + 32 * k.n_io + 16 * fold) * n, out_bytes = 2 * n + 16 * fold;
+    // what the folded call adds: rho behind the public inputs (16 B per proof under a Groth16 key, 80 B under a Pinocchio key), all_ok behind the codes
+    const size_t fold = 1;
+    const size_t n = c, in_bytes = ((size_t)p.stride + 32 * k.n_io + FOLD_RHO_BYTES[k.protocol]) * n, out_bytes = 2 * n + 16 * fold;
     const uint32_t nsum1 = k.protocol == 0 ? 1 : 2, nsum2 = k.protocol == 0 ? 0 : 1;
     k.cap = 0;
     ZKCHK(k.in.alloc(in_bytes));
@@ -431,14 +523,19 @@ static int vk_reserve(ResidentVk& k, uint32_t c, hipStream_t s) {
 // The workspaces of the folded call on top of vk_reserve's
 static int vk_reserve_fold(ResidentVk& k, uint32_t c, hipStream_t s) {
     ZKCHK(vk_reserve(k, c, s));
-    if (!k.fold.p) ZKCHK(k.fold.alloc(F_T + 32 * k.n_io));
+    if (!k.fold.p) ZKCHK(k.fold.alloc((k.protocol == 0 ? F_T : PF_T) + 32 * k.n_io));
     if (c <= k.fold_cap) return ZK_OK;
     HIPCHK(hipStreamSynchronize(s));
-    const size_t n = c, nsum = (n + FOLD_SUM_THREADS) / FOLD_SUM_THREADS;          // partial sums of n + 1 points
+    const size_t n = c, nsum = (n + FOLD_SUM_THREADS) / FOLD_SUM_THREADS;          // partial sums of n + 1 points, per segment
+    const size_t seg1 = k.protocol == 0 ? FOLD_GROTH16.nseg : FOLD_PINOCCHIO_G1.nseg, seg2 = k.protocol == 0 ? 0 : FOLD_PINOCCHIO_G2.nseg;
     k.fold_cap = 0;
     ZKCHK(k.fa.alloc(96 * n));
-    ZKCHK(k.fc.alloc(192 * (n + 1)));
-    ZKCHK(k.fsum.alloc(192 * (nsum + (nsum + FOLD_SUM_THREADS - 1) / FOLD_SUM_THREADS)));
+    ZKCHK(k.fc.alloc(192 * seg1 * (n + 1)));
+    if (seg2) {
+        ZKCHK(k.fa2.alloc(192 * n));
+        ZKCHK(k.fc2.alloc(384 * seg2 * (n + 1)));
+    }
+    ZKCHK(k.fsum.alloc((192 * seg1 > 384 * seg2 ? 192 * seg1 : 384 * seg2) * (nsum + (nsum + FOLD_SUM_THREADS - 1) / FOLD_SUM_THREADS)));          // G1 and G2 take turns
     ZKCHK(k.fm.alloc(pairing_miller_bytes(n + 1)));
     ZKCHK(k.fm2.alloc(pairing_miller_bytes(pairing_tree_scratch(n + 1))));
     k.fold_cap = c;
@@ -447,7 +544,7 @@ static int vk_reserve_fold(ResidentVk& k, uint32_t c, hipStream_t s) {
 
 // where the front half of a slab leaves its results
 struct SlabFront {
-    size_t pb, sb;                            // bytes of the proofs and of the public inputs in k.in and k.host
+    size_t pb, sb, rb;                        // bytes of the proofs, of the public inputs and of rho in k.in and k.host
     const uint32_t *d_sc, *d_rho;             // the public inputs and the folded call's rho on the device
     uint8_t *bad, *live, *d_ok, *code;        // k.flags
 };
@@ -455,7 +552,7 @@ struct SlabFront {
 // the subgroup and range tests, one code and one live byte per proof
 static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t c, SlabFront& f, hipStream_t s) {
     const VkPlan& p = plan_of(k);
-    const size_t n = c, pb = (size_t)p.stride * n, sb = 32 * k.n_io * n, rb = rho ? 16 * n : 0;
+    const size_t n = c, pb = (size_t)p.stride * n, sb = 32 * k.n_io * n, rb = rho ? FOLD_RHO_BYTES[k.protocol] * n : 0;
     memcpy(k.host, proofs, pb);
     if (sb) memcpy(k.host + pb, io_scalars, sb);
     if (rb) memcpy(k.host + pb + sb, rho, rb);
@@ -463,7 +560,7 @@ static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t
     uint8_t *d_in = k.in.as<uint8_t>(), *bad = k.flags.as<uint8_t>(), *live = bad + n, *code = bad + 3 * n;
     uint8_t *v1 = k.verdict.as<uint8_t>(), *v2 = v1 + p.n1 * n;
     const uint32_t* d_sc = reinterpret_cast<const uint32_t*>(d_in + pb);
-    f = SlabFront{pb, sb, d_sc, reinterpret_cast<const uint32_t*>(d_in + pb + sb), bad, live, bad + 2 * n, code};
+    f = SlabFront{pb, sb, rb, d_sc, reinterpret_cast<const uint32_t*>(d_in + pb + sb), bad, live, bad + 2 * n, code};
     HIPCHK(hipMemsetAsync(bad, 0, n, s));
     hipLaunchKernelGGL(k_vk_gather, grid_for(n * (6 * p.n1 + 12 * p.n2), 256), dim3(256), 0, s, (const uint8_t*)d_in, c, p, k.b1.as<uint8_t>(), k.b2.as<uint8_t>());
     {
@@ -566,43 +663,93 @@ static int vk_verify_once(std::unique_ptr<ResidentVk> k, Fill fill, const uint8_
     return rc;
 }
 
+// nseg segments of m dense XYZZ points each (m apart) at src -> their nseg sums, next to each other at dst: trees of k_fold_sum, level after level, the
+// partial sums alternating between the halves of k.fsum
+template <class F> static int vk_fold_sums(ResidentVk& k, const uint8_t* src, uint32_t m, uint32_t nseg, uint8_t* dst, hipStream_t s) {
+    constexpr size_t XB = FieldOps<F>::WORDS * 16;
+    const uint32_t first = (m + FOLD_SUM_THREADS - 1) / FOLD_SUM_THREADS;
+    uint8_t* part[2] = {k.fsum.as<uint8_t>(), k.fsum.as<uint8_t>() + XB * nseg * first};
+    uint32_t stride = m;
+    for (int lvl = 0;; lvl ^= 1) {
+        const uint32_t blocks = (m + FOLD_SUM_THREADS - 1) / FOLD_SUM_THREADS;
+        uint8_t* out = blocks == 1 ? dst : part[lvl];
+        hipLaunchKernelGGL(k_fold_sum<F>, dim3(blocks, nseg), dim3(FOLD_SUM_THREADS), 0, s, src, m, stride, out, blocks);
+        if (blocks == 1) break;
+        src = out;
+        m = stride = blocks;
+    }
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+
 // One slab of the folded call: the front half, then the slab's share of both sides folded into the state
 static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t c, bool first, bool last, int32_t* status,
                         uint8_t* all_ok, hipStream_t s) {
     const size_t n = c;
+    const bool pin = k.protocol == 1;
     SlabFront f;
     ZKCHK(vk_slab_front(k, io_scalars, proofs, rho, c, f, s));
     uint8_t* st = k.fold.as<uint8_t>();
-    uint32_t* run = reinterpret_cast<uint32_t*>(st + F_MILLER);
-    {
-        ScopedTimer t("verify_fold_scale", s);
-        // a1 = A | C per proof
-        hipLaunchKernelGGL(k_fold_scale, grid_for(2 * n, 64), dim3(64), 0, s, (const uint8_t*)k.a1.as<uint8_t>(), 2u, 0u, 1u, f.d_rho, (const uint8_t*)f.live, c,
-                           k.fa.as<uint8_t>(), k.fc.as<uint8_t>());
-        HIPCHK(hipMemcpyAsync(k.fc.as<uint8_t>() + 192 * n, st + F_SUM_C, 192, hipMemcpyDeviceToDevice, s));          // the running sum rides along
-        const uint8_t* src = k.fc.as<uint8_t>();
-        uint8_t* part[2] = {k.fsum.as<uint8_t>(), k.fsum.as<uint8_t>() + 192 * ((n + FOLD_SUM_THREADS) / FOLD_SUM_THREADS)};
-        int lvl = 0;
-        for (uint32_t m = c + 1;; lvl ^= 1) {
-            const uint32_t blocks = (m + FOLD_SUM_THREADS - 1) / FOLD_SUM_THREADS;
-            uint8_t* dst = blocks == 1 ? st + F_SUM_C : part[lvl];
-            hipLaunchKernelGGL(k_fold_sum, dim3(blocks), dim3(FOLD_SUM_THREADS), 0, s, src, m, dst);
-            if (blocks == 1) break;
-            src = dst;
-            m = blocks;
+    uint32_t* run = reinterpret_cast<uint32_t*>(st + (pin ? PF_MILLER : F_MILLER));
+    const uint8_t* live = f.live;
+    const uint8_t* miller2 = k.a2.as<uint8_t>();          // Groth16: the pairs ([rho_i] A_i, B_i)
+    if (pin) {
+        // vio and wio per proof, as the per-proof call forms them (zero bytes, the identity, when n_io = 0); yio is folded into t instead
+        uint8_t *vio = k.sums.as<uint8_t>(), *wio = vio + 384 * n;
+        if (!k.n_io) HIPCHK(hipMemsetAsync(k.sums.p, 0, 768 * n, s));
+        else {
+            ZKCHK(vk_io_sum(k, 0, f.d_sc, live, c, vio, s));
+            ZKCHK(vk_io_sum(k, 2, f.d_sc, live, c, wio, s));
         }
-        hipLaunchKernelGGL(k_fold_fr, dim3((unsigned)k.n_io + 1), dim3(FOLD_FR_THREADS), 0, s, f.d_sc, (uint32_t)k.n_io, f.d_rho, (const uint8_t*)f.live, c,
+        {
+            ScopedTimer t("verify_fold_scale_g2", s);
+            hipLaunchKernelGGL(k_fold_scale<Fp2>, grid_for(FOLD_PINOCCHIO_G2.njobs * n + FOLD_PINOCCHIO_G2.nseg, 64), dim3(64), 0, s, (const uint8_t*)k.a2.as<uint8_t>(),
+                               FOLD_PINOCCHIO_G2, (const uint8_t*)wio, f.d_rho, live, c, (const uint8_t*)(st + PF_SUMS2), k.fa2.as<uint8_t>(), k.fc2.as<uint8_t>());
+            HIPCHK(hipGetLastError());
+        }
+        ScopedTimer t("verify_fold_scale", s);
+        hipLaunchKernelGGL(k_fold_scale<Fp>, grid_for(FOLD_PINOCCHIO_G1.njobs * n + FOLD_PINOCCHIO_G1.nseg, 64), dim3(64), 0, s, (const uint8_t*)k.a1.as<uint8_t>(),
+                           FOLD_PINOCCHIO_G1, (const uint8_t*)vio, f.d_rho, live, c, (const uint8_t*)(st + PF_SUMS1), k.fa.as<uint8_t>(), k.fc.as<uint8_t>());
+        HIPCHK(hipGetLastError());
+        ZKCHK(vk_fold_sums<Fp2>(k, k.fc2.as<uint8_t>(), c + 1, FOLD_PINOCCHIO_G2.nseg, st + PF_SUMS2, s));
+        ZKCHK(vk_fold_sums<Fp>(k, k.fc.as<uint8_t>(), c + 1, FOLD_PINOCCHIO_G1.nseg, st + PF_SUMS1, s));
+        hipLaunchKernelGGL(k_fold_fr, dim3((unsigned)k.n_io + 1), dim3(FOLD_FR_THREADS), 0, s, f.d_sc, (uint32_t)k.n_io, f.d_rho, 5u, 4u, live, c,
+                           reinterpret_cast<uint32_t*>(st + PF_T), (uint32_t*)nullptr, reinterpret_cast<uint32_t*>(st + PF_DEAD));
+        HIPCHK(hipGetLastError());
+        miller2 = k.fa2.as<uint8_t>();                    // the pairs ([rho_i4](vio_i + vv_i), wio_i + ww_i)
+    } else {
+        ScopedTimer t("verify_fold_scale", s);
+        // a1 = A | C per proof; the running sum rides along behind the [rho_i] C_i
+        hipLaunchKernelGGL(k_fold_scale<Fp>, grid_for(FOLD_GROTH16.njobs * n + FOLD_GROTH16.nseg, 64), dim3(64), 0, s, (const uint8_t*)k.a1.as<uint8_t>(), FOLD_GROTH16,
+                           (const uint8_t*)nullptr, f.d_rho, live, c, (const uint8_t*)(st + F_SUM_C), k.fa.as<uint8_t>(), k.fc.as<uint8_t>());
+        HIPCHK(hipGetLastError());
+        ZKCHK(vk_fold_sums<Fp>(k, k.fc.as<uint8_t>(), c + 1, FOLD_GROTH16.nseg, st + F_SUM_C, s));
+        hipLaunchKernelGGL(k_fold_fr, dim3((unsigned)k.n_io + 1), dim3(FOLD_FR_THREADS), 0, s, f.d_sc, (uint32_t)k.n_io, f.d_rho, 1u, 0u, live, c,
                            reinterpret_cast<uint32_t*>(st + F_T), reinterpret_cast<uint32_t*>(st + F_S), reinterpret_cast<uint32_t*>(st + F_DEAD));
         HIPCHK(hipGetLastError());
     }
-    // the pairs ([rho_i] A_i, B_i).  A rejected proof's A is the identity here (k_fold_scale), and k_miller writes 1 for a pair with an identity on
-    // either side whatever the other holds: its loop has no inversion and no branch on data.  Such a proof's B is what the decoder left -- the identity
-    // for a bad encoding or a point off the curve, else a point of the curve, possibly outside the subgroup -- never bytes that are no point
-    ZKCHK(pairing_miller_device(k.fa.as<uint8_t>(), k.a2.as<uint8_t>(), n, k.fm.as<uint32_t>(), s));
+    // A rejected proof's G1 point is the identity here (k_fold_scale), and k_miller writes 1 for a pair with an identity on either side whatever the
+    // other holds: its loop has no inversion and no branch on data.  Under a Groth16 key such a proof's B is what the decoder left -- the identity for
+    // a bad encoding or a point off the curve, else a point of the curve, possibly outside the subgroup -- never bytes that are no point; under a
+    // Pinocchio key its G2 point is the identity too
+    ZKCHK(pairing_miller_device(k.fa.as<uint8_t>(), miller2, n, k.fm.as<uint32_t>(), s));
     if (!first) HIPCHK(hipMemcpyAsync(k.fm.as<uint8_t>() + pairing_miller_bytes(n), run, pairing_miller_bytes(1), hipMemcpyDeviceToDevice, s));
     ZKCHK(pairing_tree_product_device(k.fm.as<uint32_t>(), c + (first ? 0 : 1), k.fm2.as<uint32_t>(), run, s));
     size_t out = n;
-    if (last) {
+    if (last && pin) {
+        // S_yio = sum_k t_k yy_io_k (zero bytes, the identity, when n_io = 0), the key's nine pairs, the one final exponentiation, the comparison with 1
+        if (k.n_io) ZKCHK(vk_io_sum(k, 1, reinterpret_cast<const uint32_t*>(st + PF_T), st + PF_ONE, 1, st + PF_OUT1 + 6 * 192, s));
+        hipLaunchKernelGGL(k_fold_key_pairs_pinocchio, dim3(1), dim3(64), 0, s, (const uint8_t*)(st + PF_SUMS1), (const uint8_t*)(st + PF_SUMS2),
+                           (const uint8_t*)k.key1.as<uint8_t>(), (const uint8_t*)k.key2.as<uint8_t>(), st + PF_OUT1, k.q1.as<uint8_t>(), k.q2.as<uint8_t>(),
+                           reinterpret_cast<uint32_t*>(st + PF_OFF));
+        HIPCHK(hipGetLastError());
+        ZKCHK(pairing_miller_device(k.q1.as<uint8_t>(), k.q2.as<uint8_t>(), 9, run + pairing_miller_bytes(1) / 4, s));
+        ZKCHK(pairing_final_exp_device(run, reinterpret_cast<const uint32_t*>(st + PF_OFF), 1, st + PF_GT, s));
+        hipLaunchKernelGGL(k_fold_verdict, dim3(1), dim3(64), 0, s, (const uint8_t*)(st + PF_GT), (const uint8_t*)k.want.as<uint8_t>(),
+                           reinterpret_cast<const uint32_t*>(st + PF_DEAD), reinterpret_cast<const uint32_t*>(st + PF_BAD), f.code + n);
+        HIPCHK(hipGetLastError());
+        out = n + 1;
+    } else if (last) {
         // sum_k t_k ltgm_io_k (zero bytes, the identity, when n_io = 0), the key's two pairs, the one final exponentiation, ab^S, the comparison
         if (k.n_io) ZKCHK(vk_io_sum(k, 0, reinterpret_cast<const uint32_t*>(st + F_T), st + F_ONE, 1, st + F_SUMS, s));
         hipLaunchKernelGGL(k_fold_key_pairs, dim3(1), dim3(64), 0, s, (const uint8_t*)(st + F_SUMS), (const uint8_t*)k.key2.as<uint8_t>(), k.q1.as<uint8_t>(),
@@ -616,7 +763,7 @@ static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t*
         HIPCHK(hipGetLastError());
         out = n + 1;
     }
-    uint8_t* h_out = k.host + f.pb + f.sb + 16 * n;
+    uint8_t* h_out = k.host + f.pb + f.sb + f.rb;
     HIPCHK(hipMemcpyAsync(h_out, f.code, out, hipMemcpyDeviceToHost, s));          // codes | all_ok
     HIPCHK(hipStreamSynchronize(s));
     if (status)
@@ -625,20 +772,23 @@ static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t*
     return ZK_OK;
 }
 
-// zk_groth16_verify_folded and zk_selftest_groth16_fold: `debug` = lhs 576 | rhs 576 | sum_io 96 | sum_c 96, or null
-static int vk_fold(uint64_t handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status, uint8_t* debug) {
+// zk_groth16_verify_folded, zk_pinocchio_verify_folded and their hooks.  `debug`, or null: Groth16 lhs 576 | rhs 576 | sum_io 96 | sum_c 96; Pinocchio
+// lhs 576 | the seven G1 sums 7 x 96 | the three G2 sums 3 x 192
+static int vk_fold(uint64_t handle, int protocol, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status,
+                   uint8_t* debug) {
     // what needs no handle comes first: these are refused before the table or the device is looked at
     if (!all_ok) ZK_FAIL(ZK_ERR_ARG, "verify_folded: null argument");
     if (count > VK_MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "verify_folded: more than 2^24 proofs in one call");
     if (count && (!proofs || !rho)) ZK_FAIL(ZK_ERR_ARG, "verify_folded: null argument");
-    for (uint32_t i = 0; i < count; i++) {
+    const size_t rho_bytes = FOLD_RHO_BYTES[protocol];
+    for (size_t i = 0; i < rho_bytes / 16 * count; i++) {
         uint8_t any = 0;
-        for (int b = 0; b < 16; b++) any |= rho[16 * (size_t)i + b];
-        if (!any) ZK_FAIL(ZK_ERR_ARG, "verify_folded: a coefficient rho_i is zero");
+        for (int b = 0; b < 16; b++) any |= rho[16 * i + b];
+        if (!any) ZK_FAIL(ZK_ERR_ARG, protocol == 0 ? "verify_folded: a coefficient rho_i is zero" : "verify_folded: one of a proof's five coefficients rho is zero");
     }
     ResidentVk* kp;
     if (handle && !g_vk.find(handle)) ZKCHK(ensure_init());          // without a device no handle exists: say that, not that this one is unknown
-    ZKCHK(vk_lookup(handle, 0, &kp));
+    ZKCHK(vk_lookup(handle, protocol, &kp));
     if (!count) {
         *all_ok = 1;
         return ZK_OK;
@@ -649,18 +799,25 @@ static int vk_fold(uint64_t handle, const uint8_t* io_scalars, const uint8_t* pr
     hipStream_t s = ctx().stream;
     ZKCHK(vk_reserve_fold(k, count < k.slab ? count : k.slab, s));
     uint8_t* st = k.fold.as<uint8_t>();
-    HIPCHK(hipMemsetAsync(st + F_SUMS, 0, F_T + 32 * k.n_io - F_SUMS, s));
-    HIPCHK(hipMemsetAsync(st + F_ONE, 1, 1, s));
+    const size_t stride = plan_of(k).stride;
+    if (protocol == 0) HIPCHK(hipMemsetAsync(st + F_SUMS, 0, F_T + 32 * k.n_io - F_SUMS, s));
+    else HIPCHK(hipMemsetAsync(st + PF_SUMS1, 0, PF_T + 32 * k.n_io - PF_SUMS1, s));
+    HIPCHK(hipMemsetAsync(st + (protocol == 0 ? F_ONE : PF_ONE), 1, 1, s));
     uint8_t verdict = 0;
     for (uint32_t lo = 0; lo < count; lo += k.slab) {
         const uint32_t c = count - lo < k.slab ? count - lo : k.slab;
-        ZKCHK(vk_fold_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + 384 * (size_t)lo, rho + 16 * (size_t)lo, c, lo == 0, lo + c == count,
+        ZKCHK(vk_fold_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, rho + rho_bytes * lo, c, lo == 0, lo + c == count,
                            status ? status + lo : nullptr, &verdict, s));
     }
     *all_ok = verdict;
-    if (debug) {
+    if (debug && protocol == 0) {
         ZKCHK(points_xyzz_to_bytes_dev(CURVE_G1, st + F_SUMS, 2, st + F_BYTES, s));
         HIPCHK(hipMemcpyAsync(debug, st + F_GT, 1152 + 192, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    } else if (debug) {
+        ZKCHK(points_xyzz_to_bytes_dev(CURVE_G1, st + PF_OUT1, 7, st + PF_BYTES, s));
+        ZKCHK(points_xyzz_to_bytes_dev(CURVE_G2, st + PF_SUMS2, 3, st + PF_BYTES + 7 * 96, s));
+        HIPCHK(hipMemcpyAsync(debug, st + PF_GT, PF_T - PF_GT, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return ZK_OK;
@@ -742,18 +899,32 @@ int zk_pinocchio_verify_resident(uint64_t handle, const uint8_t* io_scalars, con
     return vk_verify(handle, 1, io_scalars, proofs, count, ok, status);
 }
 int zk_groth16_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status) {
-    return vk_fold(vk_handle, io_scalars, proofs, rho, count, all_ok, status, nullptr);
+    return vk_fold(vk_handle, 0, io_scalars, proofs, rho, count, all_ok, status, nullptr);
+}
+int zk_pinocchio_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status) {
+    return vk_fold(vk_handle, 1, io_scalars, proofs, rho, count, all_ok, status, nullptr);
 }
 int zk_selftest_groth16_fold(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, uint8_t lhs_gt[576],
                              uint8_t rhs_gt[576], uint8_t sum_c[96], uint8_t sum_io[96], int32_t* status) {
     if (!count || !lhs_gt || !rhs_gt || !sum_c || !sum_io) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_groth16_fold: null argument or no proofs");
     uint8_t out[1152 + 192];
     int all_ok = 0;
-    ZKCHK(vk_fold(vk_handle, io_scalars, proofs, rho, count, &all_ok, status, out));
+    ZKCHK(vk_fold(vk_handle, 0, io_scalars, proofs, rho, count, &all_ok, status, out));
     memcpy(lhs_gt, out, 576);
     memcpy(rhs_gt, out + 576, 576);
     memcpy(sum_io, out + 1152, 96);
     memcpy(sum_c, out + 1248, 96);
+    return ZK_OK;
+}
+int zk_selftest_pinocchio_fold(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, uint8_t lhs_gt[576],
+                               uint8_t sums_g1[7 * 96], uint8_t sums_g2[3 * 192], int32_t* status) {
+    if (!count || !lhs_gt || !sums_g1 || !sums_g2) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_pinocchio_fold: null argument or no proofs");
+    uint8_t out[576 + 7 * 96 + 3 * 192];
+    int all_ok = 0;
+    ZKCHK(vk_fold(vk_handle, 1, io_scalars, proofs, rho, count, &all_ok, status, out));
+    memcpy(lhs_gt, out, 576);
+    memcpy(sums_g1, out + 576, 7 * 96);
+    memcpy(sums_g2, out + 576 + 7 * 96, 3 * 192);
     return ZK_OK;
 }
 }

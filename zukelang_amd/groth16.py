@@ -96,9 +96,10 @@ class ResidentVKey:
         """Are ALL of these proofs good?  One folded pairing equation for the batch (zk_groth16_verify_folded) instead of one per proof: True, or False
         when any proof is bad -- verify_many then says which.  rho: one non-zero 128-bit coefficient per proof.  Leave it None: 16 bytes per proof are
         then drawn from `secrets` here, after the proofs are fixed.  A caller that passes its own takes over the contract of include/zkmi355x.h -- drawn
-        after the proofs are fixed, unpredictable to whoever made them -- without which a bad batch can be made to pass.  Groth16 keys only."""
+        after the proofs are fixed, unpredictable to whoever made them -- without which a bad batch can be made to pass.  This class folds under Groth16
+        keys; what pinocchio.VKey.resident() returns is a subclass that overrides this with Pinocchio's fold (five coefficients per proof)."""
         if self._call != "zk_groth16_verify_resident":
-            raise NotImplementedError("verify_all: the folded check exists for Groth16 keys only; this is a Pinocchio key (use verify_many)")
+            raise NotImplementedError("verify_all: this class folds under Groth16 keys; for a Pinocchio key use what pinocchio.VKey.resident() returns")
         count, io_all, pr_all = self._batch("verify_all", input_outputs, proofs)
         if rho is None:
             rho = [_draw_rho() for _ in range(count)]
@@ -118,7 +119,7 @@ class ResidentVKey:
         per-proof call as well.  Off by default: the call is then exactly the per-proof one."""
         if fold_first:
             if self._call != "zk_groth16_verify_resident":
-                raise NotImplementedError("verify_many(fold_first=True): the folded check exists for Groth16 keys only; this is a Pinocchio key")
+                raise NotImplementedError("verify_many(fold_first=True): this class folds under Groth16 keys; for a Pinocchio key use what pinocchio.VKey.resident() returns")
             proofs, input_outputs = list(proofs), list(input_outputs)
             if self.verify_all(input_outputs, proofs):
                 return ([True] * len(proofs), [0] * len(proofs)) if return_status else [True] * len(proofs)

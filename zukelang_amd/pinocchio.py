@@ -10,6 +10,7 @@ Key and proof layouts are those of include/zkmi355x.h.  An unsatisfied witness r
 (QAP.ml:134).  `verify` (13 pairings, :254-420) is outside the accelerated path (scope row f1).
 """
 import ctypes as C
+import secrets
 from dataclasses import dataclass
 
 import numpy as np
@@ -26,6 +27,55 @@ class PKey:
     g2: np.ndarray   # ww | waw | si2 | wt | wawt
 
 
+def _draw_rho_row():
+    """Five times 16 bytes from the operating system's generator as little-endian integers; a zero is drawn again"""
+    row = []
+    while len(row) < 5:
+        r = int.from_bytes(secrets.token_bytes(16), "little")
+        if r:
+            row.append(r)
+    return row
+
+
+class PinocchioResidentVKey(ResidentVKey):
+    """What VKey.resident() returns: the resident key of groth16.ResidentVKey with the folded check of zk_pinocchio_verify_folded.  A proof is a Proof
+    or its 960 bytes."""
+
+    def __init__(self, handle, n_io):
+        super().__init__(handle, n_io, lambda p: bytes(p if isinstance(p, (bytes, bytearray)) else p.to_bytes()), 960, "zk_pinocchio_verify_resident")
+
+    def verify_all(self, input_outputs, proofs, rho=None, return_status=False):
+        """Are ALL of these proofs good?  One folded pairing equation for the batch (zk_pinocchio_verify_folded) instead of five per proof: True, or
+        False when any proof is bad -- verify_many then says which.  rho: one row of FIVE coefficients 0 < rho < 2^128 per proof, one per equation of
+        Verify.f.  Leave it None: the rows are then drawn from `secrets` here, after the proofs are fixed.  A caller that passes its own takes over the
+        contract of include/zkmi355x.h -- drawn after the proofs are fixed, unpredictable to whoever made them, five independent ones per proof --
+        without which a bad batch, or a single bad proof, can be made to pass."""
+        count, io_all, pr_all = self._batch("verify_all", input_outputs, proofs)
+        if rho is None:
+            rho = [_draw_rho_row() for _ in range(count)]
+        try:
+            rho = [[int(r) for r in row] for row in rho]
+        except TypeError:
+            raise ValueError("verify_all: need one row of five coefficients per proof") from None
+        if len(rho) != count or any(len(row) != 5 or any(not 0 < r < 1 << 128 for r in row) for row in rho):
+            raise ValueError("verify_all: need one row of five coefficients 0 < rho < 2^128 per proof")
+        rho_all = np.frombuffer(b"".join(r.to_bytes(16, "little") for row in rho for r in row), dtype=np.uint8)
+        all_ok = C.c_int(0)
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        _lib.check(_lib.lib().zk_pinocchio_verify_folded(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
+                                                         _p(rho_all) if count else None, C.c_uint32(count), C.byref(all_ok),
+                                                         status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return (bool(all_ok.value), [int(x) for x in status[:count]]) if return_status else bool(all_ok.value)
+
+    def verify_many(self, input_outputs, proofs, return_status=False, fold_first=False):
+        """fold_first: ask verify_all first (rho drawn here) and answer all-true when it says so; only a batch that holds a bad proof pays for the
+        per-proof call as well.  Off by default: the call is then exactly the per-proof one."""
+        proofs, input_outputs = list(proofs), list(input_outputs)
+        if fold_first and self.verify_all(input_outputs, proofs):
+            return ([True] * len(proofs), [0] * len(proofs)) if return_status else [True] * len(proofs)
+        return super().verify_many(input_outputs, proofs, return_status=return_status)
+
+
 @dataclass
 class VKey:
     g1: np.ndarray   # one | aw | bgm | vv_io | yy_io
@@ -40,7 +90,7 @@ class VKey:
             raise AssertionError("Variable not found")
         h = C.c_uint64(0)
         _lib.check(_lib.lib().zk_pinocchio_vk_upload(_p(g1), _p(g2), C.c_size_t(n_io), C.byref(h)))
-        return ResidentVKey(h.value, n_io, lambda p: bytes(p.to_bytes()), 960, "zk_pinocchio_verify_resident")
+        return PinocchioResidentVKey(h.value, n_io)
 
 
 @dataclass
