@@ -515,6 +515,35 @@ int zk_pinocchio_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars /* 
                                const uint8_t* rho /* count * 80: rho_i0 .. rho_i4, 16 B little-endian each */, uint32_t count,
                                int* all_ok, int32_t* status /* count, may be NULL */);
 
+/* ---- the same four calls on proofs in their COMPRESSED wire form (zukelang_amd/csrc/verify_resident.hip) ----------------------
+ * The reference's proof is a record of compressed points (groth16.ml:110-114, pinocchio.ml:195-208; to_compressed_bytes, curve.ml:199-219): 48 B per
+ * G1 point, 96 B per G2 point, in declaration order -- Groth16 A 48 | B 96 | C 48 = 192 B; Pinocchio vv 48 | ww 96 | yy 48 | h 48 | vavv 48 | waww 96 |
+ * yayy 48 | bvwy 48 = 480 B.  These calls take the proofs as they arrive and decompress them on the device, in the same call: one H2D copy of
+ * proofs | public inputs (| rho) at the compressed stride, one decompression launch per group straight out of that buffer -- one lane per point, the
+ * square root by ONE power (p - 3) / 4 in Fp and TWO in Fp2, no inversion -- then the handle's subgroup test, by endomorphism, and from there the
+ * very code of the uncompressed call.  Signatures, argument checks and their order, handle checks, count = 0, count > 2^24, the no-GPU case
+ * (ZK_ERR_HIP) and the slabs of 8192 proofs are those of the twin without _compressed; everything the twin refuses before the device is touched is
+ * refused here before the device is touched.
+ *   status[i] is the code zk_g1_decompress / zk_g2_decompress returns for the FIRST bad point of proof i, in the order a verifier meets them (A, B, C;
+ *   vv, ww, yy, h, vavv, waww, yayy, bvwy): ZK_ERR_ARG for a bad encoding (the compression bit missing, a coordinate >= p, the infinity bit on
+ *   anything but C0 00 .. 00), ZK_ERR_NOT_ON_CURVE for an abscissa that is on no point of the curve or a point outside the subgroup; otherwise
+ *   ZK_ERR_SCALAR_RANGE for a public input >= r; otherwise 0.  For a proof whose points all decode, ok[i] and status[i] are byte for byte what the
+ *   uncompressed call returns on the same handle for the decompressed proof, and *all_ok follows the same rule.  The folded calls keep THE CONTRACT
+ *   FOR rho above, unchanged.  Kernel families: verify_point_decompress (the decompression launches), then the twin's (the subgroup test stays under
+ *   verify_point_checks).
+ *   zk_groth16_verify_many / zk_pinocchio_verify_many, whose key lives for one call, have no compressed form: a caller with proofs off the wire
+ *   checks a stream of them under one key and has every reason to hold a handle. */
+int zk_groth16_verify_resident_compressed(uint64_t handle, const uint8_t* io_scalars /* count * n_io * 32 */,
+                                          const uint8_t* proofs /* count * 192: A 48 | B 96 | C 48 */, uint32_t count, uint8_t* ok /* count */,
+                                          int32_t* status /* count, may be NULL */);
+int zk_pinocchio_verify_resident_compressed(uint64_t handle, const uint8_t* io_scalars /* count * n_io * 32 */,
+                                            const uint8_t* proofs /* count * 480: vv 48 | ww 96 | yy 48 | h 48 | vavv 48 | waww 96 | yayy 48 | bvwy 48 */,
+                                            uint32_t count, uint8_t* ok /* count */, int32_t* status /* count, may be NULL */);
+int zk_groth16_verify_folded_compressed(uint64_t vk_handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 192 */,
+                                        const uint8_t* rho /* count * 16 */, uint32_t count, int* all_ok, int32_t* status /* count, may be NULL */);
+int zk_pinocchio_verify_folded_compressed(uint64_t vk_handle, const uint8_t* io_scalars /* count * n_io * 32 */, const uint8_t* proofs /* count * 480 */,
+                                          const uint8_t* rho /* count * 80 */, uint32_t count, int* all_ok, int32_t* status /* count, may be NULL */);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------
  * With profiling on, kernel families are bracketed by HIP events on the stream they run on;
  * zk_profile_get returns the summed milliseconds and launch count since the last reset. */
@@ -563,6 +592,12 @@ int zk_selftest_fp12(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8
  * run).  verdict[i] = 0 good (the identity included) | 2 bad encoding | 1 not on the curve | 4 on the curve, outside the subgroup.  A null pointer,
  * n = 0, another group or method -> ZK_ERR_ARG before the device is touched. */
 int zk_selftest_subgroup(int group, int method, const uint8_t* points, size_t n, uint8_t* verdict);
+/* The front half of a compressed slab on bare points (tests/test_gpu_point_decompress.py): n compressed points of group 0 (G1, 48 B) or 1 (G2, 96 B)
+ * through the very kernels the *_compressed verifiers launch -- the decompression, then the subgroup test by endomorphism.  verdict[i] = 0 good (the
+ * identity included) | 2 bad encoding | 1 the abscissa is on no point of the curve | 4 on the curve, outside the subgroup.  out[i] = the decoded point
+ * in the ABI's uncompressed bytes (96 / 192 B) when the verdict is 0 or 4, zero bytes otherwise.  A null pointer, n = 0 or another group -> ZK_ERR_ARG
+ * before the device is touched. */
+int zk_selftest_point_decompress(int group, const uint8_t* in /* n * 48 | n * 96 */, size_t n, uint8_t* out /* n * 96 | n * 192 */, uint8_t* verdict);
 /* Every form of the device's group law on bare operands (tests/test_gpu_group_law.py), each run by a kernel of the translation unit that builds the
  * form for production, with that unit's flags.  group 0 = G1, 1 = G2 (on lane pairs).  a[i]: an XYZZ point as four field elements x, y, zz, zzz
  * (x_affine = x / zz, y_affine = y / zzz, zz^3 = zzz^2; zz = 0 is the identity whatever x and y are), each 48 B big-endian -- in G2 96 B, imaginary

@@ -325,6 +325,24 @@ let zk_selftest_pinocchio_fold =
     (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> ptr int32_t
    @-> returning int)
 
+(* The four verifiers on proofs in their compressed wire form (include/zkmi355x.h): 192 bytes per Groth16 proof, 480 per Pinocchio proof -- the
+   to_compressed_bytes of the proof record's fields in declaration order -- decompressed on the device in the call that verifies them. *)
+let zk_groth16_verify_resident_compressed =
+  fn "zk_groth16_verify_resident_compressed"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
+
+let zk_pinocchio_verify_resident_compressed =
+  fn "zk_pinocchio_verify_resident_compressed"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
+
+let zk_groth16_verify_folded_compressed =
+  fn "zk_groth16_verify_folded_compressed"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ptr int @-> ptr int32_t @-> returning int)
+
+let zk_pinocchio_verify_folded_compressed =
+  fn "zk_pinocchio_verify_folded_compressed"
+    (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ptr int @-> ptr int32_t @-> returning int)
+
 let vk_free (h : Unsigned.UInt64.t) = ignore (zk_vk_free h)
 
 let groth16_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =

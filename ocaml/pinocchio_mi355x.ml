@@ -367,6 +367,40 @@ module Make (C : Curve.S) = struct
         check (zk_pinocchio_verify_folded t.handle (bytes_start io_all) (bytes_start proofs) (bytes_start rho) (u32 count) all_ok no_status));
       Ctypes.( !@ ) all_ok <> 0
 
+    (* The same two questions about proofs still in their wire form: each proof as the 480 bytes vv | ww | yy | h | vavv | waww | yayy | bvwy
+       of its record's fields under to_compressed_bytes -- what the proof's JSON holds, before of_compressed_bytes_exn.  The points are decompressed and
+       checked on the device in the same call; a proof with a point that does not decode is false, as a proof that of_compressed_bytes_exn refuses
+       never reaches verify. *)
+    let compressed_jobs (t : t) (jobs : (Fr.t Var.Map.t * bytes) list) =
+      List.iter
+        (fun (io, p) ->
+          assert (Var.Set.equal (Var.Map.domain io) t.domain);
+          assert (Bytes.length p = 480))
+        jobs;
+      (fr_bytes (List.concat_map (fun (io, _) -> values io) jobs), Mi355x.cat (List.map snd jobs))
+
+    let verify_many_compressed (t : t) (jobs : (Fr.t Var.Map.t * bytes) list) : bool list =
+      let io_all, proofs = compressed_jobs t jobs in
+      let count = List.length jobs in
+      let ok = Bytes.make (max count 1) (Char.chr 0) in
+      Mi355x.(
+        check (zk_pinocchio_verify_resident_compressed t.handle (bytes_start io_all) (bytes_start proofs) (u32 count) (bytes_start ok) no_status));
+      List.init count (fun i -> Bytes.get ok i <> Char.chr 0)
+
+    let verify_all_compressed rng (t : t) (jobs : (Fr.t Var.Map.t * bytes) list) : bool =
+      let io_all, proofs = compressed_jobs t jobs in
+      let count = List.length jobs in
+      let rec draw () =
+        let b = Bytes.sub (Fr.to_bytes (Fr.gen rng)) 0 16 in
+        if Bytes.equal b (Bytes.make 16 (Char.chr 0)) then draw () else b
+      in
+      let rho = Mi355x.cat (List.init (5 * count) (fun _ -> draw ())) in
+      let all_ok = Ctypes.allocate Ctypes.int 0 in
+      Mi355x.(
+        check
+          (zk_pinocchio_verify_folded_compressed t.handle (bytes_start io_all) (bytes_start proofs) (bytes_start rho) (u32 count) all_ok no_status));
+      Ctypes.( !@ ) all_ok <> 0
+
     let free (t : t) = Mi355x.vk_free t.handle
   end
 

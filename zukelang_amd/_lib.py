@@ -28,8 +28,9 @@ EXPORTS = [
     "zk_pairing_product_many", "zk_groth16_verify_many", "zk_pinocchio_verify_many",
     "zk_groth16_vk_upload", "zk_pinocchio_vk_upload", "zk_vk_info", "zk_vk_free", "zk_groth16_verify_resident", "zk_pinocchio_verify_resident",
     "zk_groth16_verify_folded", "zk_pinocchio_verify_folded",
+    "zk_groth16_verify_resident_compressed", "zk_pinocchio_verify_resident_compressed", "zk_groth16_verify_folded_compressed", "zk_pinocchio_verify_folded_compressed",
     "zk_profile_enable", "zk_profile_reset", "zk_profile_get", "zk_profile_names", "zk_profile_counter", "zk_sync",
-    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_fp2_lanewise", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_pinocchio_fold", "zk_selftest_group",
+    "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_fp2_lanewise", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_pinocchio_fold", "zk_selftest_group", "zk_selftest_point_decompress",
 ]
 
 
@@ -84,6 +85,15 @@ PIN_FOLD_PROTOTYPES = {
     "zk_pinocchio_verify_folded": [C.c_uint64, _P8, _P8, _P8, C.c_uint32, C.POINTER(C.c_int), _PI32],
     "zk_selftest_pinocchio_fold": [C.c_uint64, _P8, _P8, _P8, C.c_uint32, _P8, _P8, _P8, _PI32],
 }
+# the same verifiers on proofs in their compressed wire form and the decompression hook (tests/test_verify_compressed_surface.py holds them to the
+# header).  Again a table of their own: the tables above are each held to exactly their entries.
+COMPRESSED_PROTOTYPES = {
+    "zk_groth16_verify_resident_compressed": [C.c_uint64, _P8, _P8, C.c_uint32, _P8, _PI32],
+    "zk_pinocchio_verify_resident_compressed": [C.c_uint64, _P8, _P8, C.c_uint32, _P8, _PI32],
+    "zk_groth16_verify_folded_compressed": [C.c_uint64, _P8, _P8, _P8, C.c_uint32, C.POINTER(C.c_int), _PI32],
+    "zk_pinocchio_verify_folded_compressed": [C.c_uint64, _P8, _P8, _P8, C.c_uint32, C.POINTER(C.c_int), _PI32],
+    "zk_selftest_point_decompress": [C.c_int, _P8, C.c_size_t, _P8, _P8],
+}
 # the group law's hook (tests/test_group_law_surface.py holds it to the header).  Again a table of its own.
 GROUP_PROTOTYPES = {
     "zk_selftest_group": [C.c_int, C.c_int, C.c_int, _P8, _P8, C.c_size_t, _P8],
@@ -108,7 +118,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

@@ -134,6 +134,13 @@ enum SubgroupTest { SUBGROUP_NONE, SUBGROUP_ORDER, SUBGROUP_ENDO };
 // decode + curve check + `test` with one verdict byte per point (verdict_order.h: 0 good | 2 encoding | 1 curve | 4 subgroup); rejected points become the
 // identity.  The verifiers' decoder: zero bytes without the infinity bit are off the curve here (msm_points.hip: point_decode)
 int points_decode_verdicts(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, uint8_t* d_verdict, SubgroupTest test, hipStream_t s);
+// Its two halves for points that arrive COMPRESSED (48 / 96 B), each one launch.  The first reads `per` <= 6 points of each of `items` items where they
+// lie in the item's bytes -- point q of item j at d_in + stride j + off[q], all multiples of 16 -- and writes the dense affine list (point per j + q; a
+// rejected point is the identity) and one verdict byte per point, 0 | 2 | 1: square roots by the power (p - 3) / 4.  The second sets verdict 4 on the
+// points of the list that `test` finds outside the subgroup.
+int points_decompress_verdicts(Curve curve, void* d_affine, const void* d_in, uint64_t items, uint32_t per, uint32_t stride, const uint32_t* off, uint8_t* d_verdict,
+                               hipStream_t s);
+int points_subgroup_verdicts(Curve curve, const void* d_affine, uint64_t n, uint8_t* d_verdict, SubgroupTest test, hipStream_t s);
 // n1 G1 and n2 G2 points (host bytes) through it under the timer family `family`: dense affine points on the device in a1 / a2 (allocated here: the caller
 // keeps them or lets them go) and one verdict per point on the host.  Waits for the stream.
 int points_decode_two_lists(const uint8_t* g1, uint64_t n1, const uint8_t* g2, uint64_t n2, const char* family, SubgroupTest test, DevBuf& a1, DevBuf& a2,
@@ -163,6 +170,7 @@ int points_selftest_subgroup(Curve curve, SubgroupTest test, const uint8_t* poin
 // n ZCash-COMPRESSED points (host, 48 / 96 B) -> uncompressed (host, 96 / 192 B): square roots, curve and subgroup checks on the device (msm_points.hip)
 int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, hipStream_t s);
 int points_selftest_sqrt(int field, const uint8_t* a, uint64_t n, uint8_t* root, uint8_t* is_square, hipStream_t s);          // zk_selftest_sqrt
+int points_selftest_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* verdict, hipStream_t s);         // zk_selftest_point_decompress
 // ---- zk_selftest_group: every form of the group law on bare operands, one kernel per translation unit that builds the form (group_selftest.cuh says
 // why and what the buffers hold).  The numbers are the `form` argument of the C-ABI.
 enum GroupForm {

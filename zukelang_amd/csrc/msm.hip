@@ -448,6 +448,14 @@ int zk_selftest_subgroup(int group, int method, const uint8_t* points, size_t n,
     DeviceScope ds(0);
     return points_selftest_subgroup(group ? CURVE_G2 : CURVE_G1, method ? SUBGROUP_ENDO : SUBGROUP_ORDER, points, n, verdict, ctx().stream);
 }
+// the decompression launch and the subgroup launch of a resident key's compressed slab front (verify_resident.hip) on bare points
+int zk_selftest_point_decompress(int group, const uint8_t* in, size_t n, uint8_t* out, uint8_t* verdict) {
+    if (!in || !out || !verdict || !n || (group != 0 && group != 1))
+        ZK_FAIL(ZK_ERR_ARG, "zk_selftest_point_decompress: null argument, no points, or a group other than 0 (G1) / 1 (G2)");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    return points_selftest_decompress(group ? CURVE_G2 : CURVE_G1, in, n, out, verdict, ctx().stream);
+}
 int zk_g1_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G1, scalars, n, out); }
 int zk_g2_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G2, scalars, n, out); }
 int zk_g1_powers(uint32_t d, const uint8_t s[32], uint8_t* out) { return powers_api(CURVE_G1, d, s, out); }

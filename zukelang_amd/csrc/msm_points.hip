@@ -134,26 +134,42 @@ __global__ __launch_bounds__(64) void k_proof_to_bytes(const uint8_t* g1, uint32
 // ------------------------------------------------------------------ of_compressed_bytes_exn over whole lists (curve.ml:199-212; round 5)
 // The reference's JSON holds every key point COMPRESSED (Bls12_381.G1/G2.to_compressed_bytes): a 2^20-constraint key is five million square roots and
 // subgroup checks on the way in -- half an hour of one host core through zk_g1/g2_decompress, a second here.  One lane per point: x from its 48 / 96
-// big-endian bytes, y = sqrt(x^3 + b) by the power (p + 1) / 4 (p = 3 mod 4; in Fp2 through the norm), the sign bit's choice of root, then the
+// big-endian bytes, y = sqrt(x^3 + b) by the power (p - 3) / 4 (p = 3 mod 4; in Fp2 two of them, through the norm), the sign bit's choice of root, then the
 // subgroup check and the encoder above.  Same verdicts as the host functions: kind 2 = bad encoding (compression bit missing, coordinate >= p, infinity
 // bit on a string that is not C0 00 .. 00), 1 = x is not the abscissa of a curve point, 4 = outside the subgroup (k_subgroup_check).  A list fails with
 // the verdict of its FIRST bad element, as a reader that decodes the elements in order does: every bad lane files index << 3 | kind under atomicMin.
 FF_INLINE void first_failure(unsigned long long* first, uint64_t i, int kind) { atomicMin(first, (unsigned long long)(i << 3) | (unsigned long long)kind); }
-__device__ static const uint32_t FP_SQRT_EXP[12] = {0xffffeaabu, 0xee7fbfffu, 0xac54ffffu, 0x07aaffffu, 0x3dac3d89u, 0xd9cc34a8u,
-                                                    0x3ce144afu, 0xd91dd2e1u, 0x90d2eb35u, 0x92c6e9edu, 0x8e5ff9a6u, 0x0680447au};      // (p + 1) / 4, 379 bits
+__device__ static const uint32_t FP_ROOT_EXP[12] = {0xffffeaaau, 0xee7fbfffu, 0xac54ffffu, 0x07aaffffu, 0x3dac3d89u, 0xd9cc34a8u,
+                                                    0x3ce144afu, 0xd91dd2e1u, 0x90d2eb35u, 0x92c6e9edu, 0x8e5ff9a6u, 0x0680447au};      // (p - 3) / 4, 379 bits
 __device__ static const uint32_t FP_HALF_PM1[12] = {0xffffd555u, 0xdcff7fffu, 0x58a9ffffu, 0x0f55ffffu, 0x7b587b12u, 0xb3986950u,
                                                     0x79c2895fu, 0xb23ba5c2u, 0x21a5d66bu, 0x258dd3dbu, 0x1cbff34du, 0x0d0088f5u};      // (p - 1) / 2
 template <int A> FF_INLINE FpB<2> fp_red2(const FpB<A>& a) { return fe_mul(a, fp_one()); }          // the same value below 2 p
-__device__ __noinline__ FpB<2> fp_pow_sqrt(const FpB<2>& a) {          // a^((p + 1) / 4): the exponent is a constant, every lane takes the same branches
-    FpB<2> acc = fp_one();
-    for (int i = 378; i >= 0; i--) {
+FF_INLINE FpB<2> fp_half() {                               // 1/2 = (p + 1) / 2, a constant: no inversion
+    FpWords h;
+#pragma unroll
+    for (int k = 0; k < 12; k++) h.w[k] = FP_HALF_PM1[k];
+    h.w[0] += 1;                                           // the low word of (p - 1) / 2 ends in ...d555: no carry
+    return fp_to_mont(h);
+}
+FF_INLINE FpB<2> fp_select(bool c, const FpB<2>& a, const FpB<2>& b) {
+    FpB<2> r;
+#pragma unroll
+    for (int i = 0; i < FPL; i++) r.v[i] = c ? a.v[i] : b.v[i];
+    return r;
+}
+// THE power of the square roots: a^((p - 3) / 4).  The exponent is a constant, every lane takes the same branches.  With w = a^((p - 3) / 4):
+//   w a = a^((p + 1) / 4), a square root of a when a is a square (p = 3 mod 4);   w^2 a = a^((p - 1) / 2), the quadratic character of a;
+//   w = 1 / (w a) when that character is 1 -- the inverse of the root comes with the root.
+__device__ __noinline__ FpB<2> fp_pow_root(const FpB<2>& a) {
+    FpB<2> acc = a;                                        // bit 378
+    for (int i = 377; i >= 0; i--) {
         acc = fe_sqr(acc);
-        if ((FP_SQRT_EXP[i >> 5] >> (i & 31)) & 1u) acc = fe_mul(acc, a);
+        if ((FP_ROOT_EXP[i >> 5] >> (i & 31)) & 1u) acc = fe_mul(acc, a);
     }
     return acc;
 }
-FF_INLINE bool fp_sqrt_dev(FpB<2>& out, const FpB<2>& a) {
-    out = fp_pow_sqrt(a);
+FF_INLINE bool fp_sqrt_dev(FpB<2>& out, const FpB<2>& a) {          // one power
+    out = fe_mul(fp_pow_root(a), a);
     return fe_eq(fe_sqr(out), a);
 }
 template <int A> FF_INLINE bool fp_is_large(const FpB<A>& y) {          // canonical integer of y > (p - 1) / 2: the ZCash sign of a coordinate
@@ -168,81 +184,104 @@ template <int A> FF_INLINE bool fp_is_large(const FpB<A>& y) {          // canon
 // imaginary part, and to the real part when the imaginary part is zero.  The decompression kernels and zk_selftest_sqrt both decide here.
 FF_INLINE bool y_is_larger(const FpB<2>& y) { return fp_is_large(y); }
 FF_INLINE bool y_is_larger(const Fp2B<2>& y) { return fe_is_zero(y.c1) ? fp_is_large(y.c0) : fp_is_large(y.c1); }
-// a square root of a in Fp2 = Fp[u] / (u^2 + 1) (either one: the caller fixes the sign); false: a is not a square
+// a square root of a in Fp2 = Fp[u] / (u^2 + 1) (either one: the caller fixes the sign); false: a is not a square.  TWO powers, one after the other,
+// no inversion, and no branch on data stands around either power: what depends on a is chosen among computed values.
+//   a1 != 0:  n = a0^2 + a1^2,  s = n^((p + 1) / 4)  (s^2 = n when a is a square: its norm is one),  t = (a0 + s) / 2,  w = t^((p - 3) / 4),
+//             chi = w^2 t.  chi = 1: sqrt(t) = w t and 1 / sqrt(t) = w, the root is (w t, a1 w / 2).  chi = -1: (w t)^2 = -t, and
+//             (a1 w / 2)^2 - (w t)^2 = (4 t^2 - a1^2) / (4 t) = a0,  2 (a1 w / 2)(-w t) = a1: the root is (a1 w / 2, -w t).
+//   a1 == 0:  the first power runs on a0 instead of n: w a0 is a root of a0 (character 1: the root is real) or of -a0 (the root is (w a0) u).  The
+//             second power runs all the same and its result is dropped.
+// Whatever went wrong on the way -- n no square, t = 0 -- shows in the last line: root^2 == a.
 FF_INLINE bool fp2_sqrt_dev(Fp2B<2>& out, const Fp2B<2>& a) {
-    if (fe_is_zero(a.c1)) {
-        FpB<2> r;
-        if (fp_sqrt_dev(r, a.c0)) { out = {r, fp_zero()}; return true; }
-        if (fp_sqrt_dev(r, fp_red2(fe_neg(a.c0)))) { out = {fp_zero(), r}; return true; }          // (r u)^2 = -r^2
-        return false;
+    const bool real = fe_is_zero(a.c1);
+    const FpB<2> in1 = fp_select(real, a.c0, fp_red2(fe_add(fe_sqr(a.c0), fe_sqr(a.c1))));
+    const FpB<2> w1 = fp_pow_root(in1);
+    const FpB<2> s = fe_mul(w1, in1);
+    const FpB<2> half = fp_half();
+    const FpB<2> t = fe_mul(fe_add(a.c0, s), half);
+    const FpB<2> w2 = fp_pow_root(t);
+    if (real) {
+        if (fe_eq(fe_mul(fe_sqr(w1), a.c0), fp_one())) out = {s, fp_zero()};
+        else out = {fp_zero(), s};
+    } else {
+        const FpB<2> wt = fe_mul(w2, t), other = fe_mul(fe_mul(a.c1, w2), half);
+        if (fe_eq(fe_mul(fe_sqr(w2), t), fp_one())) out = {wt, other};
+        else out = {other, fp_red2(fe_neg(wt))};
     }
-    FpB<2> s;
-    if (!fp_sqrt_dev(s, fp_red2(fe_add(fe_sqr(a.c0), fe_sqr(a.c1))))) return false;                 // the norm of a square is a square
-    const FpB<2> half = fe_inv(fe_dbl(fp_one()));
-    FpB<2> x0;
-    if (!fp_sqrt_dev(x0, fe_mul(fe_add(a.c0, s), half)) && !fp_sqrt_dev(x0, fe_mul(fe_sub(a.c0, s), half))) return false;
-    const FpB<2> x1 = fe_mul(a.c1, fe_inv(fe_dbl(x0)));
-    out = {x0, x1};
     const Fp2B<4> sq = fe_sqr(out);
     return fe_eq(sq.c0, a.c0) && fe_eq(sq.c1, a.c1);
 }
-__global__ __launch_bounds__(128) void k_decompress_g1(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, unsigned long long* first) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    alignas(16) uint8_t xb[48];
-    for (int k = 0; k < 48; k++) xb[k] = in[48 * i + k];
+// THE decompressor, one per group: the 48 / 96 wire bytes of a point (xb, a 16-byte aligned copy the function may overwrite) -> the affine point
+// (the identity when rejected) and its kind, 0 good | 2 bad encoding | 1 the abscissa is on no curve point.  The flag rules stand here and nowhere
+// else: the list kernels (k_decompress_*, which file the first failure of a list) and the verifiers' verdict kernel (k_decompress_verdict) call it.
+FF_INLINE uint8_t point_decompress(Aff<Fp>& out, uint8_t* xb) {
     const uint8_t f0 = xb[0];
+    out = aff_inf<Fp>();
+    if (!(f0 & 0x80)) return 2;
+    if (f0 & 0x40) return canonical_infinity(xb, 48, 0xC0) ? 0 : 2;
     xb[0] &= 0x1f;
-    Aff<Fp> out = aff_inf<Fp>();
-    if (!(f0 & 0x80)) first_failure(first, i, 2);
-    else if (f0 & 0x40) {
-        xb[0] = f0;
-        if (!canonical_infinity(xb, 48, 0xC0)) first_failure(first, i, 2);
-    } else {
-        const FpWords xw = fpw_from_be(xb);
-        if (!fpw_canonical(xw)) first_failure(first, i, 2);
-        else {
-            const FpB<2> x = fp_to_mont(xw);
-            const FpB<2> rhs = fp_red2(fe_add(fe_mul(fe_sqr(x), x), FieldOps<Fp>::curve_b()));
-            FpB<2> y;
-            if (!fp_sqrt_dev(y, rhs)) first_failure(first, i, 1);
-            else {
-                if (y_is_larger(y) != ((f0 & 0x20) != 0)) y = fp_red2(fe_neg(y));
-                out = {x, y};
-            }
-        }
-    }
-    aff_store<Fp>(dense + 96 * i, out);
+    const FpWords xw = fpw_from_be(xb);
+    if (!fpw_canonical(xw)) return 2;
+    const FpB<2> x = fp_to_mont(xw);
+    const FpB<2> rhs = fp_red2(fe_add(fe_mul(fe_sqr(x), x), FieldOps<Fp>::curve_b()));
+    FpB<2> y;
+    if (!fp_sqrt_dev(y, rhs)) return 1;
+    if (y_is_larger(y) != ((f0 & 0x20) != 0)) y = fp_red2(fe_neg(y));
+    out = {x, y};
+    return 0;
 }
-__global__ __launch_bounds__(128) void k_decompress_g2(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, unsigned long long* first) {
+FF_INLINE uint8_t point_decompress(Aff<Fp2>& out, uint8_t* xb) {          // xb: x.c1 (with the flags) | x.c0
+    const uint8_t f0 = xb[0];
+    out = aff_inf<Fp2>();
+    if (!(f0 & 0x80)) return 2;
+    if (f0 & 0x40) return canonical_infinity(xb, 96, 0xC0) ? 0 : 2;
+    xb[0] &= 0x1f;
+    const FpWords x1w = fpw_from_be(xb), x0w = fpw_from_be(xb + 48);
+    if (!fpw_canonical(x1w) || !fpw_canonical(x0w)) return 2;
+    const Fp2B<2> x = {fp_to_mont(x0w), fp_to_mont(x1w)};
+    const auto cube = fe_mul(fe_sqr(x), x);
+    const Fp2 b = FieldOps<Fp2>::curve_b();
+    const Fp2B<2> rhs = {fp_red2(fe_add(cube.c0, b.c0)), fp_red2(fe_add(cube.c1, b.c1))};
+    Fp2B<2> y;
+    if (!fp2_sqrt_dev(y, rhs)) return 1;
+    if (y_is_larger(y) != ((f0 & 0x20) != 0)) y = {fp_red2(fe_neg(y.c0)), fp_red2(fe_neg(y.c1))};
+    out = {Fp2(x), Fp2(y)};
+    return 0;
+}
+// the point's wire bytes (a multiple of 16, at a 16-byte aligned address) -> the lane's copy
+template <int BYTES> FF_INLINE void wire_load(uint8_t* xb, const uint8_t* __restrict__ src) {
+#pragma unroll
+    for (int k = 0; k < BYTES / 16; k++) reinterpret_cast<uint4*>(xb)[k] = reinterpret_cast<const uint4*>(src)[k];
+}
+// a list of compressed points: dense affine out, and the list's first failure
+template <class F> __global__ __launch_bounds__(128) void k_decompress(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, unsigned long long* first) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    alignas(16) uint8_t xb[96];          // x.c1 (with the flags) | x.c0
-    for (int k = 0; k < 96; k++) xb[k] = in[96 * i + k];
-    const uint8_t f0 = xb[0];
-    xb[0] &= 0x1f;
-    Aff<Fp2> out = aff_inf<Fp2>();
-    if (!(f0 & 0x80)) first_failure(first, i, 2);
-    else if (f0 & 0x40) {
-        xb[0] = f0;
-        if (!canonical_infinity(xb, 96, 0xC0)) first_failure(first, i, 2);
-    } else {
-        const FpWords x1w = fpw_from_be(xb), x0w = fpw_from_be(xb + 48);
-        if (!fpw_canonical(x1w) || !fpw_canonical(x0w)) first_failure(first, i, 2);
-        else {
-            const Fp2B<2> x = {fp_to_mont(x0w), fp_to_mont(x1w)};
-            const auto cube = fe_mul(fe_sqr(x), x);
-            const Fp2 b = FieldOps<Fp2>::curve_b();
-            const Fp2B<2> rhs = {fp_red2(fe_add(cube.c0, b.c0)), fp_red2(fe_add(cube.c1, b.c1))};
-            Fp2B<2> y;
-            if (!fp2_sqrt_dev(y, rhs)) first_failure(first, i, 1);
-            else {
-                if (y_is_larger(y) != ((f0 & 0x20) != 0)) y = {fp_red2(fe_neg(y.c0)), fp_red2(fe_neg(y.c1))};
-                out = {Fp2(x), Fp2(y)};
-            }
-        }
-    }
-    aff_store<Fp2>(dense + 192 * i, out);
+    constexpr int CB = FieldOps<F>::WORDS * 4, B = FieldOps<F>::WORDS * 8;
+    alignas(16) uint8_t xb[CB];
+    wire_load<CB>(xb, in + (size_t)CB * i);
+    Aff<F> out;
+    const uint8_t kind = point_decompress(out, xb);
+    if (kind) first_failure(first, i, kind);
+    aff_store<F>(dense + (size_t)B * i, out);
+}
+// The verifiers' form (verify_resident.hip): `per` points of every item -- a proof -- read where they lie in the item's wire bytes, point q of item j
+// at in + stride j + off[q], into the dense list dense[per j + q] with one verdict byte each.  Strides and offsets are multiples of 16.
+struct WireSlots {
+    uint32_t per, stride;
+    uint32_t off[6];
+};
+template <class F> __global__ __launch_bounds__(128) void k_decompress_verdict(uint8_t* __restrict__ dense, const uint8_t* __restrict__ in, uint64_t n, WireSlots w,
+                                                                              uint8_t* __restrict__ verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int CB = FieldOps<F>::WORDS * 4, B = FieldOps<F>::WORDS * 8;
+    const uint64_t item = i / w.per;
+    alignas(16) uint8_t xb[CB];
+    wire_load<CB>(xb, in + (size_t)w.stride * item + w.off[i - item * w.per]);
+    Aff<F> out;
+    verdict[i] = point_decompress(out, xb);
+    aff_store<F>(dense + (size_t)B * i, out);
 }
 
 // zk_selftest_sqrt: the square roots and the sign rule above on bare field elements, one lane per element, as k_decompress_* call them.
@@ -524,14 +563,36 @@ int points_bytes_to_affine(Curve curve, void* d_aff, const void* d_bytes, uint64
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
-int points_decode_verdicts(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, uint8_t* d_verdict, SubgroupTest test, hipStream_t s) {
+int points_subgroup_verdicts(Curve curve, const void* d_aff, uint64_t n, uint8_t* d_verdict, SubgroupTest test, hipStream_t s) {
     if (!n) return ZK_OK;
     for_curve(curve, [&](auto f) {
         using F = FIELD_OF(f);
         const dim3 grid = grid_for(n, 128);
-        hipLaunchKernelGGL(k_bytes_to_affine_verdict<F>, grid, dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
         if (test == SUBGROUP_ORDER) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_verdict<F, SUBGROUP_ORDER>), grid, dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
         if (test == SUBGROUP_ENDO) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_verdict<F, SUBGROUP_ENDO>), grid, dim3(128), 0, s, (const uint8_t*)d_aff, n, d_verdict);
+    });
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+int points_decode_verdicts(Curve curve, void* d_aff, const void* d_bytes, uint64_t n, uint8_t* d_verdict, SubgroupTest test, hipStream_t s) {
+    if (!n) return ZK_OK;
+    for_curve(curve, [&](auto f) {
+        hipLaunchKernelGGL(k_bytes_to_affine_verdict<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_bytes, n, d_verdict);
+    });
+    return points_subgroup_verdicts(curve, d_aff, n, d_verdict, test, s);
+}
+int points_decompress_verdicts(Curve curve, void* d_aff, const void* d_in, uint64_t items, uint32_t per, uint32_t stride, const uint32_t* off, uint8_t* d_verdict,
+                               hipStream_t s) {
+    if (!items || !per) return ZK_OK;
+    if (per > 6 || stride % 16) ZK_FAIL(ZK_ERR_ARG, "points_decompress_verdicts: at most 6 points per item, at strides of 16 bytes");
+    WireSlots w{per, stride, {}};
+    for (uint32_t q = 0; q < per; q++) {
+        if (off[q] % 16 || off[q] + aff_bytes(curve) / 2 > stride) ZK_FAIL(ZK_ERR_ARG, "points_decompress_verdicts: a point lies outside its item or off a 16-byte boundary");
+        w.off[q] = off[q];
+    }
+    const uint64_t n = items * per;
+    for_curve(curve, [&](auto f) {
+        hipLaunchKernelGGL(k_decompress_verdict<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_in, n, w, d_verdict);
     });
     HIPCHK(hipGetLastError());
     return ZK_OK;
@@ -669,7 +730,7 @@ int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, 
     HIPCHK(hipMemsetAsync(flag.as<uint8_t>() + 8, 0xFF, 8, s));
     unsigned long long* first = (unsigned long long*)(flag.as<uint8_t>() + 8);
     HIPCHK(hipMemcpyAsync(din.p, in, cb * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(curve == CURVE_G1 ? k_decompress_g1 : k_decompress_g2, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, first);
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_decompress<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, dense.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), n, first); });
     launch_subgroup_check(curve, dense.p, n, flag.as<int>(), first, s);
     HIPCHK(hipGetLastError());
     ZKCHK(points_affine_to_bytes(curve, dout.p, dense.p, n, s));
@@ -683,6 +744,28 @@ int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, 
         if (kind == 1) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "decompress: an abscissa is not on the curve");
         ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "decompress: a point is on the curve but outside the prime-order subgroup");
     }
+    return ZK_OK;
+}
+
+// zk_selftest_point_decompress: n compressed points (host) through the slab front's two launches -- k_decompress_verdict, then k_subgroup_verdict by
+// endomorphism -- -> one verdict each and the decoded point in the ABI's bytes (verdict 0 or 4; zero bytes for a point the decoder rejected)
+int points_selftest_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* verdict, hipStream_t s) {
+    const size_t cb = aff_bytes(curve) / 2, ub = aff_bytes(curve);
+    const uint32_t off0 = 0;
+    DevBuf din, dense, dout, dv;
+    ZKCHK(din.alloc(cb * n));
+    ZKCHK(dense.alloc(ub * n));
+    ZKCHK(dout.alloc(ub * n));
+    ZKCHK(dv.alloc(n));
+    HIPCHK(hipMemcpyAsync(din.p, in, cb * n, hipMemcpyHostToDevice, s));
+    ZKCHK(points_decompress_verdicts(curve, dense.p, din.p, n, 1, (uint32_t)cb, &off0, dv.as<uint8_t>(), s));
+    ZKCHK(points_subgroup_verdicts(curve, dense.p, n, dv.as<uint8_t>(), SUBGROUP_ENDO, s));
+    ZKCHK(points_affine_to_bytes(curve, dout.p, dense.p, n, s));
+    HIPCHK(hipMemcpyAsync(out, dout.p, ub * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(verdict, dv.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < n; i++)
+        if (verdict[i] == 1 || verdict[i] == 2) memset(out + ub * i, 0, ub);
     return ZK_OK;
 }
 

@@ -32,6 +32,15 @@ struct VkPlan {
 static const VkPlan PLAN_GROTH16 = {384, 2, 1, 3, 1, {0, 288, 0, 0, 0, 0}, {96, 0}, 3, {0, 0x80, 1, 0, 0, 0, 0, 0}};                          // A | B | C
 static const VkPlan PLAN_PINOCCHIO = {960, 6, 2, 13, 5, {0, 288, 384, 480, 768, 864}, {96, 576}, 8, {0, 0x80, 1, 2, 3, 0x81, 4, 5}};         // vv ww yy h vavv waww yayy bvwy
 
+// The same points where a proof arrives COMPRESSED, as the reference's proof record holds them (48 B per G1 point, 96 B per G2 point, in the order
+// above): the proof's stride and the offsets that stand for off1 / off2.  Half of the plan's, every one a multiple of 16.
+struct VkWire {
+    uint32_t stride;
+    uint32_t off1[6], off2[2];
+};
+static const VkWire WIRE_GROTH16 = {192, {0, 144, 0, 0, 0, 0}, {48, 0}};
+static const VkWire WIRE_PINOCCHIO = {480, {0, 144, 192, 240, 384, 432}, {48, 288}};
+
 // Proof i's code: its first bad point's verdict in the plan's order, else 8 when one of its public inputs is >= r (bad[i]), else 0.  The verdict lists
 // are laid out per proof: G1 point q of proof i at v1[n1 i + q], G2 point q at v2[n2 i + q].
 ZK_HOST_DEVICE inline uint8_t proof_code(const VkPlan& p, const uint8_t* v1, const uint8_t* v2, const uint8_t* bad, uint32_t i) {

@@ -20,6 +20,9 @@
 //                wio + ww added here; a rejected proof gets identity pairs
 //              6 k_miller, k_final_exp (pairing_dev.hip, unchanged), k_vk_compare against the 576 bytes of `ab` / of 1
 //              7 one D2H copy: ok | code
+//            The *_compressed calls bring the proofs as the reference's proof record holds them (192 / 480 B: 48 B per G1 point, 96 B per G2 point).
+//            Steps 1-2 become: one H2D copy at that stride; one decompression launch per group, straight out of the slab buffer into the dense lists
+//            and the verdict bytes (k_decompress_verdict, timer family verify_point_decompress); k_subgroup_verdict.  The rest is the same code.
 // The verdicts are those of the host verifiers (pairing_host.hip), and the same under both subgroup tests: one predicate
 // (tests/test_subgroup_criterion.py, tests/test_gpu_subgroup_endo.py).  Nothing here reads an option.
 //
@@ -421,6 +424,8 @@ enum : size_t {
 static_assert(PF_SUMS1 % 16 == 0 && PF_OFF % 16 == 0 && PF_T % 16 == 0, "the state's points and scalars are read 16 bytes at a time");
 static constexpr size_t FOLD_RHO_BYTES[2] = {16, 80};          // per proof, by protocol: one coefficient / five
 static const VkPlan& plan_of(const ResidentVk& k) { return k.protocol == 0 ? PLAN_GROTH16 : PLAN_PINOCCHIO; }
+// a call's proofs lie `stride` bytes apart: the plan's, or the wire form's when the call brings compressed proofs (wire != null)
+static size_t proof_stride(const ResidentVk& k, const VkWire* wire) { return wire ? wire->stride : plan_of(k).stride; }
 
 // a range of its own (handle_table.h); like resident bases, a live verification key pins the device list
 static HandleTable<ResidentVk>& g_vk = *new HandleTable<ResidentVk>(HANDLES_VERIFICATION_KEY, "unknown verification key handle");
@@ -549,10 +554,13 @@ struct SlabFront {
     uint8_t *bad, *live, *d_ok, *code;        // k.flags
 };
 // proofs [0, c) of a slab, steps 1-3 of the file's header: the H2D copy (rho behind the public inputs when the folded call brings one), the decoder,
-// the subgroup and range tests, one code and one live byte per proof
-static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t c, SlabFront& f, hipStream_t s) {
+// the subgroup and range tests, one code and one live byte per proof.  wire != null: the proofs are compressed.  The copy moves them at their own stride
+// (192 / 480 B, less than the workspaces were sized for) and ONE launch per group takes every point from where it lies in the slab buffer to the dense
+// affine lists a1 / a2 and its verdict byte (points_decompress_verdicts): no gather, no 96 / 192-byte form in between, and nothing decoded twice.  The
+// subgroup test then runs on those lists as it does behind the other decoder, and everything behind it is shared.
+static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, const VkWire* wire, uint32_t c, SlabFront& f, hipStream_t s) {
     const VkPlan& p = plan_of(k);
-    const size_t n = c, pb = (size_t)p.stride * n, sb = 32 * k.n_io * n, rb = rho ? FOLD_RHO_BYTES[k.protocol] * n : 0;
+    const size_t n = c, pb = proof_stride(k, wire) * n, sb = 32 * k.n_io * n, rb = rho ? FOLD_RHO_BYTES[k.protocol] * n : 0;
     memcpy(k.host, proofs, pb);
     if (sb) memcpy(k.host + pb, io_scalars, sb);
     if (rb) memcpy(k.host + pb + sb, rho, rb);
@@ -562,8 +570,17 @@ static int vk_slab_front(ResidentVk& k, const uint8_t* io_scalars, const uint8_t
     const uint32_t* d_sc = reinterpret_cast<const uint32_t*>(d_in + pb);
     f = SlabFront{pb, sb, rb, d_sc, reinterpret_cast<const uint32_t*>(d_in + pb + sb), bad, live, bad + 2 * n, code};
     HIPCHK(hipMemsetAsync(bad, 0, n, s));
-    hipLaunchKernelGGL(k_vk_gather, grid_for(n * (6 * p.n1 + 12 * p.n2), 256), dim3(256), 0, s, (const uint8_t*)d_in, c, p, k.b1.as<uint8_t>(), k.b2.as<uint8_t>());
-    {
+    if (wire) {
+        {
+            ScopedTimer t("verify_point_decompress", s);
+            ZKCHK(points_decompress_verdicts(CURVE_G2, k.a2.p, d_in, n, p.n2, wire->stride, wire->off2, v2, s));
+            ZKCHK(points_decompress_verdicts(CURVE_G1, k.a1.p, d_in, n, p.n1, wire->stride, wire->off1, v1, s));
+        }
+        ScopedTimer t(k.checks.family, s);
+        ZKCHK(points_subgroup_verdicts(CURVE_G2, k.a2.p, p.n2 * n, v2, k.checks.test, s));
+        ZKCHK(points_subgroup_verdicts(CURVE_G1, k.a1.p, p.n1 * n, v1, k.checks.test, s));
+    } else {
+        hipLaunchKernelGGL(k_vk_gather, grid_for(n * (6 * p.n1 + 12 * p.n2), 256), dim3(256), 0, s, (const uint8_t*)d_in, c, p, k.b1.as<uint8_t>(), k.b2.as<uint8_t>());
         ScopedTimer t(k.checks.family, s);
         ZKCHK(points_decode_verdicts(CURVE_G2, k.a2.p, k.b2.p, p.n2 * n, v2, k.checks.test, s));
         ZKCHK(points_decode_verdicts(CURVE_G1, k.a1.p, k.b1.p, p.n1 * n, v1, k.checks.test, s));
@@ -587,12 +604,13 @@ static int vk_io_sum(ResidentVk& k, int q, const uint32_t* d_sc, const uint8_t* 
 }
 
 // proofs [0, c) of a slab: everything of the file's header, steps 1-7 (front: steps 1-3 are already enqueued and left this)
-static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t c, const SlabFront* front, uint8_t* ok, int32_t* status, hipStream_t s) {
+static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const VkWire* wire, uint32_t c, const SlabFront* front, uint8_t* ok, int32_t* status,
+                   hipStream_t s) {
     const VkPlan& p = plan_of(k);
     const size_t n = c;
     SlabFront f;
     if (front) f = *front;
-    else ZKCHK(vk_slab_front(k, io_scalars, proofs, nullptr, c, f, s));
+    else ZKCHK(vk_slab_front(k, io_scalars, proofs, nullptr, wire, c, f, s));
     const size_t pb = f.pb, sb = f.sb;
     const uint32_t* d_sc = f.d_sc;
     uint8_t *live = f.live, *d_ok = f.d_ok;
@@ -625,16 +643,17 @@ static int vk_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proo
 }
 
 // count >= 1 proofs under key k, slab after slab (the arguments are checked).  first: the front half of the first slab, where it is already enqueued
-static int vk_run(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, const SlabFront* first, uint8_t* ok, int32_t* status, hipStream_t s) {
+static int vk_run(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const VkWire* wire, uint32_t count, const SlabFront* first, uint8_t* ok, int32_t* status,
+                  hipStream_t s) {
     ZKCHK(vk_reserve(k, count < k.slab ? count : k.slab, s));
-    const size_t stride = plan_of(k).stride;
+    const size_t stride = proof_stride(k, wire);
     for (uint32_t lo = 0; lo < count; lo += k.slab) {
         const uint32_t c = count - lo < k.slab ? count - lo : k.slab;
-        ZKCHK(vk_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, c, lo ? nullptr : first, ok + lo, status ? status + lo : nullptr, s));
+        ZKCHK(vk_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, wire, c, lo ? nullptr : first, ok + lo, status ? status + lo : nullptr, s));
     }
     return ZK_OK;
 }
-static int vk_verify(uint64_t handle, int protocol, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
+static int vk_verify(uint64_t handle, int protocol, const uint8_t* io_scalars, const uint8_t* proofs, const VkWire* wire, uint32_t count, uint8_t* ok, int32_t* status) {
     ResidentVk* kp;
     ZKCHK(vk_lookup(handle, protocol, &kp));
     if (!count) return ZK_OK;
@@ -642,7 +661,7 @@ static int vk_verify(uint64_t handle, int protocol, const uint8_t* io_scalars, c
     if (!proofs || !ok || (k.n_io && !io_scalars)) ZK_FAIL(ZK_ERR_ARG, "verify_resident: null argument");
     if (count > VK_MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "verify_resident: more than 2^24 proofs in one call");
     DeviceScope ds(0);
-    return vk_run(k, io_scalars, proofs, count, nullptr, ok, status, ctx().stream);
+    return vk_run(k, io_scalars, proofs, wire, count, nullptr, ok, status, ctx().stream);
 }
 // A *_verify_many call (the arguments are checked, the device is current): the key of vk_new lives for this call and is in no table -- it draws no handle
 // number, does not count among the live handles and does not pin the device list.  `fill` is its protocol's *_vk_fill.  The first slab's proof points are
@@ -655,9 +674,9 @@ static int vk_verify_once(std::unique_ptr<ResidentVk> k, Fill fill, const uint8_
     const uint32_t c = count < k->slab ? count : k->slab;
     SlabFront f;
     int rc = vk_reserve(*k, c, s);
-    if (!rc) rc = vk_slab_front(*k, io_scalars, proofs, nullptr, c, f, s);
+    if (!rc) rc = vk_slab_front(*k, io_scalars, proofs, nullptr, nullptr, c, f, s);
     if (!rc) rc = fill(*k, s_key);
-    if (!rc) rc = vk_run(*k, io_scalars, proofs, count, &f, ok, status, s);
+    if (!rc) rc = vk_run(*k, io_scalars, proofs, nullptr, count, &f, ok, status, s);
     (void)hipStreamSynchronize(s_key);
     (void)hipStreamSynchronize(s);
     return rc;
@@ -683,12 +702,12 @@ template <class F> static int vk_fold_sums(ResidentVk& k, const uint8_t* src, ui
 }
 
 // One slab of the folded call: the front half, then the slab's share of both sides folded into the state
-static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t c, bool first, bool last, int32_t* status,
-                        uint8_t* all_ok, hipStream_t s) {
+static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, const VkWire* wire, uint32_t c, bool first, bool last,
+                        int32_t* status, uint8_t* all_ok, hipStream_t s) {
     const size_t n = c;
     const bool pin = k.protocol == 1;
     SlabFront f;
-    ZKCHK(vk_slab_front(k, io_scalars, proofs, rho, c, f, s));
+    ZKCHK(vk_slab_front(k, io_scalars, proofs, rho, wire, c, f, s));
     uint8_t* st = k.fold.as<uint8_t>();
     uint32_t* run = reinterpret_cast<uint32_t*>(st + (pin ? PF_MILLER : F_MILLER));
     const uint8_t* live = f.live;
@@ -773,9 +792,9 @@ static int vk_fold_slab(ResidentVk& k, const uint8_t* io_scalars, const uint8_t*
 }
 
 // zk_groth16_verify_folded, zk_pinocchio_verify_folded and their hooks.  `debug`, or null: Groth16 lhs 576 | rhs 576 | sum_io 96 | sum_c 96; Pinocchio
-// lhs 576 | the seven G1 sums 7 x 96 | the three G2 sums 3 x 192
-static int vk_fold(uint64_t handle, int protocol, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status,
-                   uint8_t* debug) {
+// lhs 576 | the seven G1 sums 7 x 96 | the three G2 sums 3 x 192.  wire != null: the proofs are compressed (vk_slab_front)
+static int vk_fold(uint64_t handle, int protocol, const uint8_t* io_scalars, const uint8_t* proofs, const VkWire* wire, const uint8_t* rho, uint32_t count, int* all_ok,
+                   int32_t* status, uint8_t* debug) {
     // what needs no handle comes first: these are refused before the table or the device is looked at
     if (!all_ok) ZK_FAIL(ZK_ERR_ARG, "verify_folded: null argument");
     if (count > VK_MAX_PROOFS) ZK_FAIL(ZK_ERR_ARG, "verify_folded: more than 2^24 proofs in one call");
@@ -799,14 +818,14 @@ static int vk_fold(uint64_t handle, int protocol, const uint8_t* io_scalars, con
     hipStream_t s = ctx().stream;
     ZKCHK(vk_reserve_fold(k, count < k.slab ? count : k.slab, s));
     uint8_t* st = k.fold.as<uint8_t>();
-    const size_t stride = plan_of(k).stride;
+    const size_t stride = proof_stride(k, wire);
     if (protocol == 0) HIPCHK(hipMemsetAsync(st + F_SUMS, 0, F_T + 32 * k.n_io - F_SUMS, s));
     else HIPCHK(hipMemsetAsync(st + PF_SUMS1, 0, PF_T + 32 * k.n_io - PF_SUMS1, s));
     HIPCHK(hipMemsetAsync(st + (protocol == 0 ? F_ONE : PF_ONE), 1, 1, s));
     uint8_t verdict = 0;
     for (uint32_t lo = 0; lo < count; lo += k.slab) {
         const uint32_t c = count - lo < k.slab ? count - lo : k.slab;
-        ZKCHK(vk_fold_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, rho + rho_bytes * lo, c, lo == 0, lo + c == count,
+        ZKCHK(vk_fold_slab(k, k.n_io ? io_scalars + 32 * k.n_io * (size_t)lo : nullptr, proofs + stride * lo, rho + rho_bytes * lo, wire, c, lo == 0, lo + c == count,
                            status ? status + lo : nullptr, &verdict, s));
     }
     *all_ok = verdict;
@@ -893,23 +912,38 @@ int zk_vk_free(uint64_t handle) {
 }
 
 int zk_groth16_verify_resident(uint64_t handle, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
-    return vk_verify(handle, 0, io_scalars, proofs, count, ok, status);
+    return vk_verify(handle, 0, io_scalars, proofs, nullptr, count, ok, status);
 }
 int zk_pinocchio_verify_resident(uint64_t handle, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
-    return vk_verify(handle, 1, io_scalars, proofs, count, ok, status);
+    return vk_verify(handle, 1, io_scalars, proofs, nullptr, count, ok, status);
 }
 int zk_groth16_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status) {
-    return vk_fold(vk_handle, 0, io_scalars, proofs, rho, count, all_ok, status, nullptr);
+    return vk_fold(vk_handle, 0, io_scalars, proofs, nullptr, rho, count, all_ok, status, nullptr);
 }
 int zk_pinocchio_verify_folded(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok, int32_t* status) {
-    return vk_fold(vk_handle, 1, io_scalars, proofs, rho, count, all_ok, status, nullptr);
+    return vk_fold(vk_handle, 1, io_scalars, proofs, nullptr, rho, count, all_ok, status, nullptr);
+}
+// the same four calls on proofs in their compressed wire form: one more argument on the way down, and the slab's front half decompresses
+int zk_groth16_verify_resident_compressed(uint64_t handle, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
+    return vk_verify(handle, 0, io_scalars, proofs, &WIRE_GROTH16, count, ok, status);
+}
+int zk_pinocchio_verify_resident_compressed(uint64_t handle, const uint8_t* io_scalars, const uint8_t* proofs, uint32_t count, uint8_t* ok, int32_t* status) {
+    return vk_verify(handle, 1, io_scalars, proofs, &WIRE_PINOCCHIO, count, ok, status);
+}
+int zk_groth16_verify_folded_compressed(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok,
+                                        int32_t* status) {
+    return vk_fold(vk_handle, 0, io_scalars, proofs, &WIRE_GROTH16, rho, count, all_ok, status, nullptr);
+}
+int zk_pinocchio_verify_folded_compressed(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, int* all_ok,
+                                          int32_t* status) {
+    return vk_fold(vk_handle, 1, io_scalars, proofs, &WIRE_PINOCCHIO, rho, count, all_ok, status, nullptr);
 }
 int zk_selftest_groth16_fold(uint64_t vk_handle, const uint8_t* io_scalars, const uint8_t* proofs, const uint8_t* rho, uint32_t count, uint8_t lhs_gt[576],
                              uint8_t rhs_gt[576], uint8_t sum_c[96], uint8_t sum_io[96], int32_t* status) {
     if (!count || !lhs_gt || !rhs_gt || !sum_c || !sum_io) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_groth16_fold: null argument or no proofs");
     uint8_t out[1152 + 192];
     int all_ok = 0;
-    ZKCHK(vk_fold(vk_handle, 0, io_scalars, proofs, rho, count, &all_ok, status, out));
+    ZKCHK(vk_fold(vk_handle, 0, io_scalars, proofs, nullptr, rho, count, &all_ok, status, out));
     memcpy(lhs_gt, out, 576);
     memcpy(rhs_gt, out + 576, 576);
     memcpy(sum_io, out + 1152, 96);
@@ -921,7 +955,7 @@ int zk_selftest_pinocchio_fold(uint64_t vk_handle, const uint8_t* io_scalars, co
     if (!count || !lhs_gt || !sums_g1 || !sums_g2) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_pinocchio_fold: null argument or no proofs");
     uint8_t out[576 + 7 * 96 + 3 * 192];
     int all_ok = 0;
-    ZKCHK(vk_fold(vk_handle, 1, io_scalars, proofs, rho, count, &all_ok, status, out));
+    ZKCHK(vk_fold(vk_handle, 1, io_scalars, proofs, nullptr, rho, count, &all_ok, status, out));
     memcpy(lhs_gt, out, 576);
     memcpy(sums_g1, out + 576, 7 * 96);
     memcpy(sums_g2, out + 576 + 7 * 96, 3 * 192);

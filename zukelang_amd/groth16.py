@@ -66,12 +66,14 @@ def _draw_rho():
 class ResidentVKey:
     """A verification key decoded and checked ONCE and kept on the device (include/zkmi355x.h, "verification keys resident on the device";
     csrc/verify_resident.hip): what VKey.resident() returns, for Groth16 and Pinocchio alike.  verify_many gives the lists Groth16.verify_many /
-    pinocchio.verify_many give under the same key; a defective KEY raises where this object is made.  One host thread; close() (or `with`) frees it."""
+    pinocchio.verify_many give under the same key; a defective KEY raises where this object is made.  One host thread; close() (or `with`) frees it.
+    compressed=True on verify_many / verify_all: the proofs are in the reference's wire form (192 / 480 B of compressed points: the bytes themselves, or
+    a Proof, which goes through to_compressed()) and the *_compressed calls of the library decompress them on the device, in the same call."""
 
     def __init__(self, handle, n_io, proof_bytes, proof_len, call):
         self.handle, self.n_io, self._proof_bytes, self._proof_len, self._call = handle, n_io, proof_bytes, proof_len, call
 
-    def _batch(self, what, input_outputs, proofs):
+    def _batch(self, what, input_outputs, proofs, compressed=False):
         """The checks of the object itself, before the library sees anything: (count, public inputs, proofs) as two byte arrays."""
         if not self.handle:
             raise ValueError("%s: the resident key is closed" % what)
@@ -87,12 +89,16 @@ class ResidentVKey:
             ios.append(io)
         count = len(proofs)
         io_all = np.frombuffer(b"".join(ios), dtype=np.uint8)
-        pr_all = np.frombuffer(b"".join(self._proof_bytes(p) for p in proofs), dtype=np.uint8)
-        if len(pr_all) != self._proof_len * count:
-            raise ValueError("%s: a proof is not %d bytes" % (what, self._proof_len))
+        if compressed:
+            chunks, want = [bytes(p) if isinstance(p, (bytes, bytearray, np.ndarray)) else p.to_compressed() for p in proofs], self._proof_len // 2
+        else:
+            chunks, want = [self._proof_bytes(p) for p in proofs], self._proof_len
+        if any(len(c) != want for c in chunks):
+            raise ValueError("%s: a proof is not %d bytes" % (what, want))
+        pr_all = np.frombuffer(b"".join(chunks), dtype=np.uint8)
         return count, io_all, pr_all
 
-    def verify_all(self, input_outputs, proofs, rho=None, return_status=False):
+    def verify_all(self, input_outputs, proofs, rho=None, return_status=False, compressed=False):
         """Are ALL of these proofs good?  One folded pairing equation for the batch (zk_groth16_verify_folded) instead of one per proof: True, or False
         when any proof is bad -- verify_many then says which.  rho: one non-zero 128-bit coefficient per proof.  Leave it None: 16 bytes per proof are
         then drawn from `secrets` here, after the proofs are fixed.  A caller that passes its own takes over the contract of include/zkmi355x.h -- drawn
@@ -100,7 +106,7 @@ class ResidentVKey:
         keys; what pinocchio.VKey.resident() returns is a subclass that overrides this with Pinocchio's fold (five coefficients per proof)."""
         if self._call != "zk_groth16_verify_resident":
             raise NotImplementedError("verify_all: this class folds under Groth16 keys; for a Pinocchio key use what pinocchio.VKey.resident() returns")
-        count, io_all, pr_all = self._batch("verify_all", input_outputs, proofs)
+        count, io_all, pr_all = self._batch("verify_all", input_outputs, proofs, compressed)
         if rho is None:
             rho = [_draw_rho() for _ in range(count)]
         rho = [int(r) for r in rho]
@@ -109,24 +115,24 @@ class ResidentVKey:
         rho_all = np.frombuffer(b"".join(r.to_bytes(16, "little") for r in rho), dtype=np.uint8)
         all_ok = C.c_int(0)
         status = np.zeros(max(count, 1), dtype=np.int32)
-        _lib.check(_lib.lib().zk_groth16_verify_folded(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
-                                                       _p(rho_all) if count else None, C.c_uint32(count), C.byref(all_ok),
-                                                       status.ctypes.data_as(C.POINTER(C.c_int32))))
+        call = _lib.lib().zk_groth16_verify_folded_compressed if compressed else _lib.lib().zk_groth16_verify_folded
+        _lib.check(call(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
+                        _p(rho_all) if count else None, C.c_uint32(count), C.byref(all_ok), status.ctypes.data_as(C.POINTER(C.c_int32))))
         return (bool(all_ok.value), [int(x) for x in status[:count]]) if return_status else bool(all_ok.value)
 
-    def verify_many(self, input_outputs, proofs, return_status=False, fold_first=False):
+    def verify_many(self, input_outputs, proofs, return_status=False, fold_first=False, compressed=False):
         """fold_first: ask verify_all first (rho drawn here) and answer all-true when it says so; only a batch that holds a bad proof pays for the
         per-proof call as well.  Off by default: the call is then exactly the per-proof one."""
         if fold_first:
             if self._call != "zk_groth16_verify_resident":
                 raise NotImplementedError("verify_many(fold_first=True): this class folds under Groth16 keys; for a Pinocchio key use what pinocchio.VKey.resident() returns")
             proofs, input_outputs = list(proofs), list(input_outputs)
-            if self.verify_all(input_outputs, proofs):
+            if self.verify_all(input_outputs, proofs, compressed=compressed):
                 return ([True] * len(proofs), [0] * len(proofs)) if return_status else [True] * len(proofs)
-        count, io_all, pr_all = self._batch("verify_many", input_outputs, proofs)
+        count, io_all, pr_all = self._batch("verify_many", input_outputs, proofs, compressed)
         ok = np.zeros(max(count, 1), dtype=np.uint8)
         status = np.zeros(max(count, 1), dtype=np.int32)
-        _lib.check(getattr(_lib.lib(), self._call)(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
+        _lib.check(getattr(_lib.lib(), self._call + ("_compressed" if compressed else ""))(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
                                                    C.c_uint32(count), _p(ok), status.ctypes.data_as(C.POINTER(C.c_int32))))
         res = [bool(x) for x in ok[:count]]
         return (res, [int(x) for x in status[:count]]) if return_status else res

@@ -39,18 +39,18 @@ def _draw_rho_row():
 
 class PinocchioResidentVKey(ResidentVKey):
     """What VKey.resident() returns: the resident key of groth16.ResidentVKey with the folded check of zk_pinocchio_verify_folded.  A proof is a Proof
-    or its 960 bytes."""
+    or its 960 bytes; with compressed=True a Proof or its 480 wire bytes."""
 
     def __init__(self, handle, n_io):
         super().__init__(handle, n_io, lambda p: bytes(p if isinstance(p, (bytes, bytearray)) else p.to_bytes()), 960, "zk_pinocchio_verify_resident")
 
-    def verify_all(self, input_outputs, proofs, rho=None, return_status=False):
+    def verify_all(self, input_outputs, proofs, rho=None, return_status=False, compressed=False):
         """Are ALL of these proofs good?  One folded pairing equation for the batch (zk_pinocchio_verify_folded) instead of five per proof: True, or
         False when any proof is bad -- verify_many then says which.  rho: one row of FIVE coefficients 0 < rho < 2^128 per proof, one per equation of
         Verify.f.  Leave it None: the rows are then drawn from `secrets` here, after the proofs are fixed.  A caller that passes its own takes over the
         contract of include/zkmi355x.h -- drawn after the proofs are fixed, unpredictable to whoever made them, five independent ones per proof --
         without which a bad batch, or a single bad proof, can be made to pass."""
-        count, io_all, pr_all = self._batch("verify_all", input_outputs, proofs)
+        count, io_all, pr_all = self._batch("verify_all", input_outputs, proofs, compressed)
         if rho is None:
             rho = [_draw_rho_row() for _ in range(count)]
         try:
@@ -62,18 +62,18 @@ class PinocchioResidentVKey(ResidentVKey):
         rho_all = np.frombuffer(b"".join(r.to_bytes(16, "little") for row in rho for r in row), dtype=np.uint8)
         all_ok = C.c_int(0)
         status = np.zeros(max(count, 1), dtype=np.int32)
-        _lib.check(_lib.lib().zk_pinocchio_verify_folded(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
-                                                         _p(rho_all) if count else None, C.c_uint32(count), C.byref(all_ok),
-                                                         status.ctypes.data_as(C.POINTER(C.c_int32))))
+        call = _lib.lib().zk_pinocchio_verify_folded_compressed if compressed else _lib.lib().zk_pinocchio_verify_folded
+        _lib.check(call(C.c_uint64(self.handle), _p(io_all) if self.n_io and count else None, _p(pr_all) if count else None,
+                        _p(rho_all) if count else None, C.c_uint32(count), C.byref(all_ok), status.ctypes.data_as(C.POINTER(C.c_int32))))
         return (bool(all_ok.value), [int(x) for x in status[:count]]) if return_status else bool(all_ok.value)
 
-    def verify_many(self, input_outputs, proofs, return_status=False, fold_first=False):
+    def verify_many(self, input_outputs, proofs, return_status=False, fold_first=False, compressed=False):
         """fold_first: ask verify_all first (rho drawn here) and answer all-true when it says so; only a batch that holds a bad proof pays for the
         per-proof call as well.  Off by default: the call is then exactly the per-proof one."""
         proofs, input_outputs = list(proofs), list(input_outputs)
-        if fold_first and self.verify_all(input_outputs, proofs):
+        if fold_first and self.verify_all(input_outputs, proofs, compressed=compressed):
             return ([True] * len(proofs), [0] * len(proofs)) if return_status else [True] * len(proofs)
-        return super().verify_many(input_outputs, proofs, return_status=return_status)
+        return super().verify_many(input_outputs, proofs, return_status=return_status, compressed=compressed)
 
 
 @dataclass

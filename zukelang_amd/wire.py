@@ -227,6 +227,24 @@ def groth16_proof_of_json(data):
     return Proof(g1_of_json(d["a"]), g2_of_json(d["b"]), g1_of_json(d["c"]))
 
 
+def _proof_bytes_of_json(data, fields):
+    """The record's point strings, concatenated in declaration order: what the library's *_compressed verifiers take.  Only the shape is checked -- every
+    field a JSON string of 48 / 96 bytes; the points themselves are decoded, once, on the device."""
+    d = loads(data)
+    out = []
+    for f, g in fields:
+        _need(isinstance(d[f], (bytes, bytearray)), "a point is a JSON string")
+        _need(len(d[f]) == 48 * g, "a compressed G%d point is %d bytes" % (g, 48 * g))
+        out.append(bytes(d[f]))
+    return b"".join(out)
+
+
+@_reader
+def groth16_proof_bytes_of_json(data):
+    """A JSON proof -> its 192 wire bytes a | b | c for ResidentVKey.verify_many(..., compressed=True): no square root and no library call here."""
+    return _proof_bytes_of_json(data, (("a", 1), ("b", 2), ("c", 1)))
+
+
 def groth16_vkey_to_json(vk, io_vars):
     """io_vars: the (name, id) of the public variables in key order (Var.Map order = the order of vk.ltgm_io)."""
     lt = bytes(vk.ltgm_io)
@@ -287,6 +305,12 @@ def pinocchio_proof_of_json(data):
     from .pinocchio import Proof
     d = loads(data)
     return Proof(*[(g1_of_json if g == 1 else g2_of_json)(d[f]) for f, g in _PIN_FIELDS])
+
+
+@_reader
+def pinocchio_proof_bytes_of_json(data):
+    """A JSON proof -> its 480 wire bytes, the eight points in declaration order, for verify_many(..., compressed=True): no library call here."""
+    return _proof_bytes_of_json(data, _PIN_FIELDS)
 
 
 def fr_to_json(x):
