@@ -563,6 +563,28 @@ int zk_bench_field_mul(int kind, uint32_t iters, double* gmul_per_s);
  * integers) the device evaluates 23 base-field expressions through the lazy-reduction code paths of the group law and
  * returns them fully reduced (23 x 48 B per pair, little-endian); pairs (2k, 2k+1) also act as one Fp2 operand pair. */
 int zk_selftest_fp(const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
+/* The scalar field on 8 x 32-bit words (tests/test_gpu_fr_field.py): the Fe<FrParams> functions of csrc/ff.cuh -- the arithmetic of the sparse products,
+ * the R1CS check, the factorial tables, the keygen scans and every to/from-Montgomery pass -- one lane per element.  a, b: 32-byte little-endian integers.
+ * op 0: a_i, b_i < r (anything else -> ZK_ERR_ARG), taken into Montgomery form on the device; out: 14 x 32 B per pair, little-endian, canonical, out of
+ *   Montgomery form:   0 a + b   1 a - b   2 b - a   3 a b   4 a^2   5 -a   6 2a (fe_dbl)   7 1 / a (0 for 0)   8 fe_from_mont(fe_to_mont(a))
+ *   9 fe_from_u32 of a's low word   10 a b + a a + b b, accumulated term by term as a row of zk_fr_spmv is   11 flags: bit 0 fe_is_zero(a), bit 1 fe_eq(a, b)
+ *   12 a through the 9 x 29-bit form and back, fr9_canon_pack(fr9_unpack(a R))   13 a b as the NTT kernels multiply, fr9_mul(unpack(a R), unpack(32 b R)),
+ *   with the factor convention of csrc/fr29.cuh, packed canonically.
+ * op 1: any 256-bit a_i; b is not read and may be NULL; out: 1 byte per element, fe_is_canonical(a_i) = (a_i < r).
+ * A null pointer, n = 0, another op -> ZK_ERR_ARG before the device is touched. */
+int zk_selftest_fr(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
+/* The scalar field of the NTT kernels on bare limbs (tests/test_gpu_fr_field.py): the fr9_* functions of csrc/fr29.cuh on lazily reduced integers of
+ * 9 limbs of 29 bits, so the caller chooses the representation and can put a butterfly at the bounds of the stage schedule (csrc/ntt_lds.cuh), which no
+ * input of zk_fr_ntt does.  operands: n x 3 values u, v, w of 9 words each (27 words per lane).  u, and v where the op reads it, are weakly normalised:
+ * limbs 0..7 at most 2^29 + 7, top limb at most that of 64 r, (64 r) >> 232.  w, where the op reads it, is a factor as memory holds one: limbs 0..7 at
+ * most 2^29 - 1 and a value below r.  Keeping the VALUE bounds of each function (csrc/fr29.cuh) is the caller's part.  out: raw limbs, not reduced further:
+ *   op 0  fr9_canon_pack(u), 8 words          op 1  fr9_reduce_weak(u), 9 words          op 2  fr9_mul(u, v), 9 words
+ *   op 3  the forward butterfly in the order of lds_ntt_stages<false>, 5 x 9 words: x = fr9_add(u, v) | fr9_reduce_weak(x) | fr9_mul(fr9_sub_raw<5>(u, v), w) |
+ *         fr9_mul(fr9_sub<5>(u, v), w) | fr9_sub<5>(u, v) (the span-2 stage)
+ *   op 4  the inverse butterfly, 3 x 9 words: t = fr9_mul(v, w) | fr9_add(u, t) | fr9_sub<2>(u, t)
+ *   op 5  fr9_pack_exact(fr9_unpack(x)), 8 words, x = the first 8 words of u taken as ANY 256-bit value (no limb rule applies).
+ * A null pointer, n = 0, another op, a limb or a top limb out of range, a w with inexact limbs or a value >= r -> ZK_ERR_ARG before the device is touched. */
+int zk_selftest_fr29(int op, const uint32_t* operands, size_t n, uint32_t* out);
 /* The paired field products (tests/test_gpu_fp_paired.py): two or three independent products of the group law run side by side where the products are
  * expanded in place.  operands: n x 4 values a, b, c, d as their 14 limbs of 29 bits in a 16-word slot each (64 words per lane), weakly normalised --
  * every limb at most 2^29 + 7, top limb at most 64 * 13 (every value below the at-rest bound 64 p qualifies) -- so the caller chooses the representation.

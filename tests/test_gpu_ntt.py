@@ -15,14 +15,16 @@ def _rand_fr(n, seed):
     return bytes(RC.random_fr_bytes(n, seed))
 
 
-@pytest.mark.parametrize("log_n", [0, 1, 2, 3, 5, 8, 10, 11, 12, 13, 16])
+@pytest.mark.parametrize("log_n", [0, 1, 2, 3, 5, 8, 10, 11, 12, 13, 16, 6, 7, 9, 15, 17, 19])
 def test_fft_matches_oracle(log_n):
+    """Every pass plan of ntt.hip: one tile of fewer than 1024 elements with an odd or an even stage count (6, 7, 9), one strided pass of 5 or 7 stages
+    in front of the tile (15, 17), and 19 -- the smallest size with two strided passes of unequal length (5 + 4 stages, row steps 2^5 and 2^6)."""
     data = _rand_fr(1 << log_n, 100 + log_n)
     assert bytes(FFT_Fr.fft(data, log_n)) == O.fr_ntt(data, log_n, False)
     assert bytes(FFT_Fr.ifft(data)) == O.fr_ntt(data, log_n, True)
 
 
-@pytest.mark.parametrize("log_n", [4, 10, 12, 14])
+@pytest.mark.parametrize("log_n", [4, 10, 12, 14, 19])
 def test_fft_extreme_values(log_n):
     """Largest residues everywhere (and sparse mixes of 0, 1, r - 1): the lazily reduced 29-bit-limb butterflies
     (csrc/fr29.cuh) run at the top of their value bounds."""
@@ -30,7 +32,10 @@ def test_fft_extreme_values(log_n):
     top = (RC.FR_MODULUS - 1).to_bytes(32, "little")
     rnd = random.Random(7 + log_n)
     pool = [top, bytes(32), (1).to_bytes(32, "little"), (RC.FR_MODULUS - 2).to_bytes(32, "little"), ((1 << 254) + 5).to_bytes(32, "little")]
-    for data in (top * n, b"".join(rnd.choice(pool) for _ in range(n)), b"".join(top if i & 1 else bytes(32) for i in range(n))):
+    patterns = [top * n, b"".join(rnd.choice(pool) for _ in range(n)), b"".join(top if i & 1 else bytes(32) for i in range(n))]
+    if log_n == 19:          # the uneven two-pass plan: the oracle's six transforms of 2^19 cost more than any other case of this file, so without the alternating pattern
+        patterns = patterns[:2]
+    for data in patterns:
         assert bytes(FFT_Fr.fft(data, log_n)) == O.fr_ntt(data, log_n, False)
         assert bytes(FFT_Fr.ifft(data)) == O.fr_ntt(data, log_n, True)
 
@@ -98,6 +103,40 @@ def test_polynomial_mul_matches_oracle(na, nb):
     a, b = _rand_fr(na, 5000 + na), _rand_fr(nb, 6000 + nb)
     assert bytes(FFT_Fr.polynomial_mul(a, b)) == O.poly_mul(a, b)
     assert bytes(FFT_Fr.polynomial_mul(b, a)) == O.poly_mul(a, b)
+
+
+def _horner(coeffs, x):
+    acc = 0
+    for c in reversed(coeffs):
+        acc = (acc * x + c) % RC.FR_MODULUS
+    return acc
+
+
+@pytest.mark.parametrize("na,nb", [(9000, 5000), (20000, 9001), (70000, 50001), (300000, 100000), (262145, 1), (262144, 262145)])
+def test_polynomial_mul_large_by_evaluation(na, nb):
+    """zk_fr_poly_mul beyond the reach of the schoolbook oracle: transforms of 2^14, 2^15, 2^17 and 2^19 (the data-form table of ntt_mul_table, k_ntt_mid
+    between strided passes), (262145, 1) one coefficient past 2^18 and na + nb - 1 = 2^19 exactly.  c(x) = a(x) b(x) mod r at two points from a fixed
+    seed (a wrong coefficient survives one evaluation with probability below 2^19 / r), the two end coefficients exactly, one middle coefficient by
+    its defining sum, and the length."""
+    P = RC.FR_MODULUS
+    n = na + nb - 1
+    assert 1 << ((n - 1).bit_length()) in (1 << 14, 1 << 15, 1 << 17, 1 << 19)
+    a, b = RC.fr_ints(_rand_fr(na, 15000 + na)), RC.fr_ints(_rand_fr(nb, 16000 + nb))
+    a[0], b[0] = a[0] or 1, b[0] or 1
+    a[-1], b[-1] = a[-1] or 1, b[-1] or 1                     # no trailing zero: the normalized product has every one of its n coefficients
+    got = bytes(FFT_Fr.polynomial_mul(RC.fr_bytes(a), RC.fr_bytes(b)))
+    assert len(got) == 32 * n
+    c = RC.fr_ints(got)
+    assert all(v < P for v in c[:: max(1, n // 1024)])
+    assert c[0] == a[0] * b[0] % P and c[n - 1] == a[-1] * b[-1] % P
+    k = n // 2 + 1
+    assert c[k] == sum(a[i] * b[k - i] for i in range(max(0, k - nb + 1), min(na, k + 1))) % P
+    rnd = random.Random(0xE7A1 + na)
+    for _ in range(2):
+        x = rnd.randrange(2, P)
+        assert _horner(c, x) == _horner(a, x) * _horner(b, x) % P
+    if nb == 1:
+        assert c == [v * b[0] % P for v in a]
 
 
 def test_polynomial_mul_normalizes_like_the_reference():

@@ -31,6 +31,7 @@ EXPORTS = [
     "zk_groth16_verify_resident_compressed", "zk_pinocchio_verify_resident_compressed", "zk_groth16_verify_folded_compressed", "zk_pinocchio_verify_folded_compressed",
     "zk_profile_enable", "zk_profile_reset", "zk_profile_get", "zk_profile_names", "zk_profile_counter", "zk_sync",
     "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_fp2_lanewise", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_pinocchio_fold", "zk_selftest_group", "zk_selftest_point_decompress",
+    "zk_selftest_fr", "zk_selftest_fr29",
 ]
 
 
@@ -103,7 +104,12 @@ FP_PAIR_PROTOTYPES = {
     "zk_selftest_fp_paired": [C.POINTER(C.c_uint32), C.c_size_t, _P8],
     "zk_selftest_fp2_lanewise": [C.POINTER(C.c_uint32), C.c_size_t, _P8],
 }
-KEY_FORMS = {"tau_powers": 0, "lagrange": 1}          # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
+# the scalar field's hooks (tests/test_fr_selftest_surface.py holds them to the header)
+FR_PROTOTYPES = {
+    "zk_selftest_fr": [C.c_int, _P8, _P8, C.c_size_t, _P8],
+    "zk_selftest_fr29": [C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)],
+}
+KEY_FORMS = {"tau_powers": 0, "lagrange": 1}         # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
 
 _lib = None
 
@@ -118,7 +124,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

@@ -104,7 +104,7 @@ FF_INLINE Fr9 fr9_mul(const Fr9& a, const Fr9& b) {
     return r;
 }
 // value < 64 r -> the same value mod r, below 2r, exact limbs.  q = floor(top / ((r >> 232) + 1)) never exceeds
-// the true quotient and falls short of it by at most one (scripts/proto/fr29_model.py checks the extremes).
+// the true quotient and falls short of it by at most one (tests/fr29_model.py, tests/test_fr29_model.py check the extremes).
 FF_INLINE Fr9 fr9_reduce_weak(const Fr9& a) {
     uint32_t t[FR29_L];
 #pragma unroll
