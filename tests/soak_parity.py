@@ -52,8 +52,11 @@ while time.time() < t_end:
         assert got == ref, ("resident-path MSM mismatch", G.__name__, n)
     n_msm += 1
     # ---- Groth16 at a random size, both key forms
-    n = 2 * rnd.randrange(1, 1500)
-    cs, w = RC.iterated_cubic(n, rnd.randrange(1, P.R))
+    n = rnd.randrange(2, 3000)
+    if n % 2 == 0:
+        cs, w = RC.iterated_cubic(n, rnd.randrange(1, P.R))
+    else:          # odd constraint counts: the general family (iterated_cubic has an even number of gates)
+        cs, w = RC.random_r1cs(n, n + n // 4, rnd.randrange(1 << 30), nnz=(1, 4))
     toxic = [rnd.randrange(1, P.R) for _ in range(5)]
     it = iter(toxic)
     pk, vk = Groth16.keygen(lambda: next(it), cs, lagrange=True)

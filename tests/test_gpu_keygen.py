@@ -11,6 +11,7 @@ import pytest
 
 import oracle_lib as O
 import ref_programs as RP
+from nonpow2_cases import product_formula          # the plain product formula in Python integers: the reference of zk_fr_lagrange_at below
 from oracle import pyref as P
 from zukelang_amd import _lib
 from zukelang_amd import pinocchio as PIN
@@ -38,28 +39,6 @@ def lagrange_at(n, first, x):
     z = np.zeros(32, dtype=np.uint8)
     _lib.check(_lib.lib().zk_fr_lagrange_at(n, first, _p(RC.fr_bytes([x])), _p(out), _p(z)))
     return RC.fr_ints(out), RC.fr_ints(z)[0]
-
-
-def product_formula(n, first, x, idx):
-    """l_i(x) = prod_{j != i} (x - p_j) / (p_i - p_j) over the points p_j = first + j, for the indices `idx`, and Z(x): plain products, one
-    modular inversion per value.  O(n) per value through prefix / suffix products of the numerators computed ONCE."""
-    d = [(x - first - j) % R for j in range(n)]
-    pre = [1] * (n + 1)
-    for j in range(n):
-        pre[j + 1] = pre[j] * d[j] % R
-    suf = [1] * (n + 1)
-    for j in range(n - 1, -1, -1):
-        suf[j] = suf[j + 1] * d[j] % R
-    fact = [1] * (n + 1)
-    for j in range(1, n + 1):
-        fact[j] = fact[j - 1] * j % R
-    vals = {}
-    for i in idx:
-        den = fact[i] * fact[n - 1 - i] % R                       # prod_{j<i} (i - j) * |prod_{j>i} (i - j)|
-        if (n - 1 - i) & 1:
-            den = R - den
-        vals[i] = pre[i] * suf[i + 1] % R * pow(den, R - 2, R) % R
-    return vals, pre[n]
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 64, 257, 4096, (1 << 16) + 3])
