@@ -247,6 +247,45 @@ int zk_groth16_keygen(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, 
 /* The key's resident base pool (group 1 or 2) as uncompressed points, in pool order: what was uploaded, or the derived Lagrange-form pool.
  * out == NULL: only *count. */
 int zk_groth16_pool_points(uint64_t handle, int group, uint8_t* out, size_t capacity_points, size_t* count);
+/* ---- keys and base lists in WIRE form: 48 B per G1 point, 96 B per G2 point ------------------------------------------------------------
+ * Every key the reference writes holds its points compressed (to_compressed_bytes: groth16.ml:24-34, pinocchio.ml:37-60 through curve.ml:199-219).
+ * The calls below take and give those bytes as they stand; the points are decoded ON THE DEVICE straight into the list the window tables are built
+ * from -- one copy up at the compressed stride, the decompressor of zk_g1/g2_decompress_batch, the subgroup test, 8 bytes back -- instead of
+ * zk_g1/g2_decompress_batch + zk_*_pk_upload (three trips over the bus per point, two subgroup tests).  Pool layouts, point counts and the
+ * ZK_ERR_DOMAIN rules are those of the uncompressed calls; a handle made here cannot be told apart from one made there from the same points
+ * (pool bytes, proof bytes, every prove / derive / shard entry point, zk_msm_resident*), on every device list on which those work: each device
+ * decodes its own slice.
+ *   Point checks (of_compressed_bytes_exn, curve.ml:199-212), the verdicts of zk_g1/g2_decompress_batch: compression flag missing, infinity bit on a
+ *   string that is not C0 00 .. 00, coordinate >= p -> ZK_ERR_ARG; abscissa on no curve point, point outside the prime-order subgroup ->
+ *   ZK_ERR_NOT_ON_CURVE.  The call returns the verdict of the FIRST bad point: the G1 list before the G2 list before h_lagrange.  No handle then.
+ *   THE IDENTITY is C0 00 .. 00 and nothing else.  The all-zero string that the uncompressed uploads accept as the identity carries no compression
+ *   flag: here it is a bad encoding (ZK_ERR_ARG).
+ *   The subgroup test is the one by the curve's endomorphisms (2 x 63 doublings in G1, 63 in G2; the resident verification keys' test), the same
+ *   answer as [r] P = O on every point of the curve.  ZK_KEY_SUBGROUP_CHECK=0 means what it means at upload: no subgroup test, no folded windows.
+ *   Null L / R / O / mid / pools / handle or an unknown form -> ZK_ERR_ARG before the device is touched; without a GPU -> ZK_ERR_HIP.
+ * zk_groth16_pk_upload_compressed: form = ZK_KEY_FORM_TAU_POWERS is zk_groth16_pk_upload, ZK_KEY_FORM_LAGRANGE is zk_groth16_pk_upload_lagrange (its
+ *   lengths, and its caller's promise that the points are the key's Lagrange form).
+ * zk_pinocchio_pk_upload_compressed (below): h_lagrange = NULL is zk_pinocchio_pk_upload, else zk_pinocchio_pk_upload_lagrange (n points of 48 B;
+ *   ZK_ERR_ARG under a device list of several entries, as there).  si[0] must be the generator's wire bytes.  The n + 1 G2 points between waw and the
+ *   two appended points are not read, as in the uncompressed call.
+ * zk_bases_upload_compressed: zk_bases_upload.
+ * zk_*_pool_points_compressed: zk_*_pool_points (out == NULL / capacity / count alike) with every point as zk_g1/g2_compress gives it, the identity as
+ *   C0 00 .. 00.  With the uploads it is the key-cache round trip: derive once (zk_*_pk_derive_lagrange), store the compressed pools, later load them
+ *   with form = ZK_KEY_FORM_LAGRANGE (Groth16: both pools) / h_lagrange (Pinocchio: the first n points of pool 5).
+ * Measured on one MI355X, host wall time from the compressed bytes to a handle that has produced one oracle-equal proof, best of five, the two routes
+ * alternating (profiles/key_load_compressed.json): Groth16 2^20 (4.19 M points) 0.693 s against 1.804 s for zk_g1/g2_decompress_batch x 2 +
+ * zk_groth16_pk_upload (spread of that route's five timings 0.022 s), 0.505 s under ZK_KEY_SUBGROUP_CHECK=0; Groth16 2^16 82 ms against 190 ms
+ * (spread 8 ms); Pinocchio 2^18 0.498 s against 1.321 s (spread 0.017 s).  Device time at 2^20 by family (zk_profile_get): key_decompress 46 ms,
+ * subgroup_check 180 ms, msm_precompute 374 ms.  zk_groth16_pool_points_compressed at 2^20: 87 ms, against 486 ms for zk_groth16_pool_points + host
+ * compression.  Kernels (profiles/key_wire_kernel_resources.txt; no spills): k_decompress 108 / 178 VGPRs and 80 / 144 B of scratch per lane (G1 / G2),
+ * k_subgroup_check by endomorphism 248 / 256 VGPRs and 1168 / 1872 B, k_compress 84 / 128 VGPRs and no scratch.  Timer families: key_decompress,
+ * key_compress; the subgroup launch stays in subgroup_check. */
+int zk_groth16_pk_upload_compressed(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                                    const uint8_t* pk_g1 /* points * 48 */, size_t pk_g1_points,
+                                    const uint8_t* pk_g2 /* points * 96 */, size_t pk_g2_points,
+                                    uint32_t form /* ZK_KEY_FORM_TAU_POWERS | ZK_KEY_FORM_LAGRANGE */, uint64_t* handle);
+int zk_bases_upload_compressed(int group, const uint8_t* points, size_t n, uint64_t* handle);
+int zk_groth16_pool_points_compressed(uint64_t handle, int group, uint8_t* out, size_t capacity_points, size_t* count);
 int zk_groth16_pk_free(uint64_t handle);
 
 /* Groth16.prove rng qap pkey sol with r, s supplied by the caller in the order the reference
@@ -379,6 +418,11 @@ int zk_pinocchio_keygen(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R
  * The h pool by key form:  compact (default): si (n + 1 points); after zk_pinocchio_pk_derive_lagrange [lambda_t(s)] (n-1) | [Z(s)] | [1] | [s^(n-1)];
  *                          full:              si | v_all | w_all;   after the derivation [lambda_t(s)] | [Z(s)] | [1] | v_all | w_all. */
 int zk_pinocchio_pool_points(uint64_t handle, int pool, uint8_t* out, size_t capacity_points, size_t* count);
+/* The wire forms ("keys and base lists in WIRE form" above; pinocchio.ml:37-60 through curve.ml:199-219) */
+int zk_pinocchio_pk_upload_compressed(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                                      const uint8_t* pk_g1 /* points * 48 */, size_t pk_g1_points, const uint8_t* pk_g2 /* points * 96 */, size_t pk_g2_points,
+                                      const uint8_t* h_lagrange /* n * 48, or NULL */, uint64_t* handle);
+int zk_pinocchio_pool_points_compressed(uint64_t handle, int pool, uint8_t* out, size_t capacity_points, size_t* count);
 int zk_pinocchio_pk_free(uint64_t handle);
 int zk_pinocchio_prove(uint64_t handle, const uint8_t* sol, const uint8_t dv[32], const uint8_t dw[32],
                        const uint8_t dy[32], uint8_t proof[960]);

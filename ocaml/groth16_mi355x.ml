@@ -130,6 +130,22 @@ module Make (C : Curve.S) = struct
   (* a key whose bytes exist on the host -- read from JSON, or generated while the device list had several entries -- enters the library here *)
   let register = upload
 
+  (* The same from the record's COMPRESSED strings as they stand in the JSON (zk_groth16_pk_upload_compressed): g1 = a | d1 | b1 | ti1 | tiztd | ltd_mid
+     and g2 = b2 | d2 | ti2, 48 / 96 B per point, decoded and checked on the device -- no of_compressed_bytes_exn per point on the host and no
+     uncompressed copy.  lagrange: the strings are the pools of a derived key (Mi355x.pool_points_compressed after zk_groth16_pk_derive_lagrange).
+     The handle is registered under pkey like any other. *)
+  let upload_compressed ?(lagrange = false) (vars : Var.t list) (l, r, o) n (pkey : pkey) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
+    let var_at = Array.of_list vars in
+    let m = Array.length var_at in
+    let mid = Bytes.init m (fun i -> if Var.Map.mem var_at.(i) pkey.ltd_mid then '\001' else '\000') in
+    let h = Mi355x.groth16_upload_compressed ~form:(if lagrange then 1 else 0) ~n ~m l r o ~mid ~g1 ~g2 in
+    Gc.finalise (fun _ -> ignore (Mi355x.zk_groth16_pk_free h)) pkey;
+    Handles.replace handles pkey h;
+    h
+
+  let pool_compressed (h : Unsigned.UInt64.t) ~(group : int) : bytes =
+    Mi355x.pool_points_compressed Mi355x.zk_groth16_pool_points_compressed h ~pool:group ~point_bytes:(if group = 1 then 48 else 96)
+
   let handle_of (qap : qap) (pkey : pkey) =
     match Handles.find_opt handles pkey with
     | Some h -> h

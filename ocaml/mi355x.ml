@@ -387,6 +387,66 @@ let zk_pinocchio_pk_upload_lagrange =
     (uint32_t @-> uint32_t @-> ptr csr @-> ptr csr @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> size_t
    @-> ocaml_bytes @-> ptr uint64_t @-> returning int)
 
+(* ---- keys and base lists in WIRE form (include/zkmi355x.h, "keys and base lists in WIRE form"): the compressed strings of the reference's JSON
+   (to_compressed_bytes, curve.ml:199-219), 48 B per G1 point and 96 B per G2 point, decoded and checked on the device.  The identity is C0 00 .. 00
+   only; the library returns the verdict of the first bad point (Not_on_curve / Invalid_argument through `check`). *)
+let zk_groth16_pk_upload_compressed =
+  fn "zk_groth16_pk_upload_compressed"
+    (uint32_t @-> uint32_t @-> ptr csr @-> ptr csr @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> size_t
+   @-> uint32_t @-> ptr uint64_t @-> returning int)
+
+let zk_pinocchio_pk_upload_compressed =
+  fn "zk_pinocchio_pk_upload_compressed"
+    (uint32_t @-> uint32_t @-> ptr csr @-> ptr csr @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> size_t
+   @-> ptr char @-> ptr uint64_t @-> returning int)
+
+let zk_bases_upload_compressed = fn "zk_bases_upload_compressed" (int @-> ocaml_bytes @-> size_t @-> ptr uint64_t @-> returning int)
+
+let zk_groth16_pool_points_compressed =
+  fn "zk_groth16_pool_points_compressed" (uint64_t @-> int @-> ptr char @-> size_t @-> ptr size_t @-> returning int)
+
+let zk_pinocchio_pool_points_compressed =
+  fn "zk_pinocchio_pool_points_compressed" (uint64_t @-> int @-> ptr char @-> size_t @-> ptr size_t @-> returning int)
+
+(* form: 0 = the tau powers of the reference's key, 1 = the Lagrange-form pools: the header's key forms *)
+let groth16_upload_compressed ?(form = 0) ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
+  let h = allocate uint64_t Unsigned.UInt64.zero in
+  check
+    (zk_groth16_pk_upload_compressed (u32 n) (u32 m) (addr l.c) (addr r.c) (addr o.c) (bytes_start mid) (bytes_start g1)
+       (sz (Bytes.length g1 / 48))
+       (bytes_start g2)
+       (sz (Bytes.length g2 / 96))
+       (u32 form) h);
+  !@h
+
+(* h_lagrange: the n stored h bases of a derived key (48 B each); without them the key starts as uploaded *)
+let pinocchio_upload_compressed ?h_lagrange ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
+  let h = allocate uint64_t Unsigned.UInt64.zero in
+  let hl = Option.map carray_of_bytes h_lagrange in
+  check
+    (zk_pinocchio_pk_upload_compressed (u32 n) (u32 m) (addr l.c) (addr r.c) (addr o.c) (bytes_start mid) (bytes_start g1)
+       (sz (Bytes.length g1 / 48))
+       (bytes_start g2)
+       (sz (Bytes.length g2 / 96))
+       (match hl with Some a -> CArray.start a | None -> null_bytes)
+       h);
+  !@h
+
+(* a resident base list from its wire bytes (zk_bases_upload_compressed) *)
+let resident_upload_compressed ~(g2 : bool) (points : bytes) : Unsigned.UInt64.t =
+  let h = allocate uint64_t Unsigned.UInt64.zero in
+  check (zk_bases_upload_compressed (if g2 then 1 else 0) (bytes_start points) (sz (Bytes.length points / if g2 then 96 else 48)) h);
+  !@h
+
+(* a resident pool in wire form: what *_upload_compressed takes back (the key cache: derive once, store, reload) *)
+let pool_points_compressed stub (h : Unsigned.UInt64.t) ~(pool : int) ~(point_bytes : int) : bytes =
+  let cnt = allocate size_t Unsigned.Size_t.zero in
+  check (stub h pool null_bytes Unsigned.Size_t.zero cnt);          (* out = NULL: the count alone *)
+  let len = Unsigned.Size_t.to_int !@cnt * point_bytes in
+  let out = CArray.make char (max 1 len) in
+  check (stub h pool (CArray.start out) !@cnt cnt);
+  Bytes.init len (fun i -> CArray.get out i)
+
 let pinocchio_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in
   check

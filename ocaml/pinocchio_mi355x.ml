@@ -148,6 +148,21 @@ module Make (C : Curve.S) = struct
   (* a key whose bytes exist on the host -- read from JSON, or generated while the device list had several entries -- enters the library here *)
   let register = upload
 
+  (* The same from the record's COMPRESSED strings as they stand in the JSON (zk_pinocchio_pk_upload_compressed), in the pool order above, 48 / 96 B per
+     point, decoded and checked on the device.  h_lagrange: the n stored h bases of a derived key (the first n points of pool 5 in wire form).  The
+     handle is registered under the key like any other. *)
+  let upload_compressed ?h_lagrange (vars : Var.t list) (l, r, o) n (k : pkey) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
+    let var_at = Array.of_list vars in
+    let m = Array.length var_at in
+    let mid = Bytes.init m (fun i -> if Var.Map.mem var_at.(i) k.vv then '\001' else '\000') in
+    let h = Mi355x.pinocchio_upload_compressed ?h_lagrange ~n ~m l r o ~mid ~g1 ~g2 in
+    Gc.finalise (fun _ -> ignore (Mi355x.zk_pinocchio_pk_free h)) k;
+    Handles.replace handles k h;
+    h
+
+  let pool_compressed (h : Unsigned.UInt64.t) ~(pool : int) : bytes =
+    Mi355x.pool_points_compressed Mi355x.zk_pinocchio_pool_points_compressed h ~pool ~point_bytes:(if pool < 6 then 48 else 96)
+
   let handle_of (qap : qap) (k : pkey) =
     match Handles.find_opt handles k with
     | Some h -> h

@@ -32,6 +32,7 @@ EXPORTS = [
     "zk_profile_enable", "zk_profile_reset", "zk_profile_get", "zk_profile_names", "zk_profile_counter", "zk_sync",
     "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_fp2_lanewise", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_pinocchio_fold", "zk_selftest_group", "zk_selftest_point_decompress",
     "zk_selftest_fr", "zk_selftest_fr29",
+    "zk_groth16_pk_upload_compressed", "zk_pinocchio_pk_upload_compressed", "zk_bases_upload_compressed", "zk_groth16_pool_points_compressed", "zk_pinocchio_pool_points_compressed",
 ]
 
 
@@ -109,6 +110,15 @@ FR_PROTOTYPES = {
     "zk_selftest_fr": [C.c_int, _P8, _P8, C.c_size_t, _P8],
     "zk_selftest_fr29": [C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)],
 }
+# keys and base lists in wire form (tests/test_key_wire_surface.py holds them to the header)
+_PSZ = C.POINTER(C.c_size_t)
+KEY_WIRE_PROTOTYPES = {
+    "zk_groth16_pk_upload_compressed": [C.c_uint32, C.c_uint32, _PCSR, _PCSR, _PCSR, _P8, _P8, C.c_size_t, _P8, C.c_size_t, C.c_uint32, _PH],
+    "zk_pinocchio_pk_upload_compressed": [C.c_uint32, C.c_uint32, _PCSR, _PCSR, _PCSR, _P8, _P8, C.c_size_t, _P8, C.c_size_t, _P8, _PH],
+    "zk_bases_upload_compressed": [C.c_int, _P8, C.c_size_t, _PH],
+    "zk_groth16_pool_points_compressed": [C.c_uint64, C.c_int, _P8, C.c_size_t, _PSZ],
+    "zk_pinocchio_pool_points_compressed": [C.c_uint64, C.c_int, _P8, C.c_size_t, _PSZ],
+}
 KEY_FORMS = {"tau_powers": 0, "lagrange": 1}         # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
 
 _lib = None
@@ -124,7 +134,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int
@@ -136,6 +146,18 @@ def check(rc):
         L = lib()
         raise ZkError(rc, "%s -- %s" % (L.zk_strerror(rc).decode(), L.zk_last_error().decode()))
     return rc
+
+
+def check_points(rc):
+    """check() for the calls that take points in wire form: a point the device decoder refuses (ZK_ERR_ARG, ZK_ERR_NOT_ON_CURVE) raises the ValueError
+    of the JSON readers (wire._point_error), with the library's code and text."""
+    if rc in (-1, -2):
+        from .wire import _point_error
+        try:
+            check(rc)
+        except ZkError as e:
+            raise _point_error(e) from None
+    return check(rc)
 
 
 def set_device_list(devices):

@@ -157,7 +157,7 @@ static uint32_t key_window(uint64_t g1_points, bool in_subgroup) {
 }
 int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
                       const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, bool lagrange, bool shard_of_group,
-                      const void* d_g1, const void* d_g2) {
+                      const void* d_g1, const void* d_g2, bool wire) {
     // d_g1 / d_g2 (both or neither): the pools as dense affine points in device memory, computed by the library itself (keygen.hip) -- pk_g1 / pk_g2 are
     // then not read
     const bool generated = d_g1 && d_g2;
@@ -203,6 +203,9 @@ int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, 
         // from outside; there are none here.
         ZKCHK(msm_bases_from_device_affine(k.g1, CURVE_G1, (const uint8_t*)d_g1 + 96 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, true));
         ZKCHK(msm_bases_from_device_affine(k.g2, CURVE_G2, (const uint8_t*)d_g2 + 192 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, true));
+    } else if (wire) {          // pk_g1 / pk_g2 hold wire bytes (zk_groth16_pk_upload_compressed): this rank's slice is decoded where its tables are built
+        ZKCHK(msm_bases_from_wire(k.g1, CURVE_G1, pk_g1 + 48 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, chk));
+        ZKCHK(msm_bases_from_wire(k.g2, CURVE_G2, pk_g2 + 96 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, chk));
     } else {
         ZKCHK(msm_bases_from_bytes(k.g1, CURVE_G1, pk_g1 + 96 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, chk));
         ZKCHK(msm_bases_from_bytes(k.g2, CURVE_G2, pk_g2 + 192 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, chk));
@@ -220,12 +223,12 @@ int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, 
 // entry behind one handle (groth16_multi.hip).  The explicit shard upload (rank of world: one process per GPU) always builds on the list's first device.
 static int upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
                   const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank,
-                  uint32_t world, uint64_t* handle, bool lagrange = false, bool whole = false) {
+                  uint32_t world, uint64_t* handle, bool lagrange = false, bool whole = false, bool wire = false) {
     if (!handle) ZK_FAIL(ZK_ERR_ARG, "pk_upload: null argument");
     ZKCHK(ensure_init());
-    if (whole && ctx_count() > 1) return group_upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, lagrange, handle);
+    if (whole && ctx_count() > 1) return group_upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, lagrange, handle, wire);
     std::unique_ptr<Groth16Key> key;
-    ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, rank, world, lagrange));
+    ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, rank, world, lagrange, false, nullptr, nullptr, wire));
     *handle = g_keys.add(std::move(key));
     return ZK_OK;
 }
@@ -412,6 +415,22 @@ int zk_groth16_pk_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, const
                                   const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint64_t* handle) {
     return upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, handle, true, true);
 }
+// The key from its wire bytes (include/zkmi355x.h).  A list fails with the verdict of its FIRST bad point, G1 before G2.  The pools are decoded slice by
+// slice where their tables are built (one slice per device of the list), so a refusal says only that some slice holds a bad point; the call then reads
+// the whole lists in order, once, for the verdict of the first one -- work a good key never pays for.
+int zk_groth16_pk_upload_compressed(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                                    const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t form, uint64_t* handle) {
+    if (!handle || !mid || !pk_g1 || !pk_g2 || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_upload_compressed: null argument");
+    if (form != ZK_KEY_FORM_TAU_POWERS && form != ZK_KEY_FORM_LAGRANGE) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_upload_compressed: form must be ZK_KEY_FORM_TAU_POWERS or ZK_KEY_FORM_LAGRANGE");
+    const int rc = upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, handle, form == ZK_KEY_FORM_LAGRANGE, true, true);
+    if (rc != ZK_ERR_ARG && rc != ZK_ERR_NOT_ON_CURVE) return rc;
+    const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
+    const bool chk = !(e_chk && atoi(e_chk) == 0);
+    DeviceScope ds(0);
+    int first = points_wire_check(CURVE_G1, pk_g1, pk_g1_points, chk, ctx().stream);
+    if (first == ZK_OK) first = points_wire_check(CURVE_G2, pk_g2, pk_g2_points, chk, ctx().stream);
+    return first != ZK_OK ? first : rc;
+}
 // ---- derivation in two halves, so that the ranks of a node can share it (one set per rank, broadcast, install) -- and the single-call form on top
 static int derive_precheck(Groth16Key& k, const char* who) {
     if (k.world != 1) ZK_FAIL(ZK_ERR_ARG, "derive: sharded keys hold only a slice of the powers");
@@ -542,10 +561,16 @@ int zk_groth16_pool_points(uint64_t handle, int group, uint8_t* out, size_t capa
     ZKCHK(key_lookup(handle, &k));
     return single_pool_points(*k, group, out, capacity_points, count);
 }
+int zk_groth16_pool_points_compressed(uint64_t handle, int group, uint8_t* out, size_t capacity_points, size_t* count) {
+    if (GroupKey* g = group_lookup(handle)) return group_pool_points(*g, group, out, capacity_points, count, true);
+    Groth16Key* k;
+    ZKCHK(key_lookup(handle, &k));
+    return single_pool_points(*k, group, out, capacity_points, count, true);
+}
 }  // extern "C"
 namespace zk {
-// the key's resident pool slice (all of it for a key held whole) as uncompressed bytes, in pool order
-int single_pool_points(Groth16Key& key, int group, uint8_t* out, size_t capacity_points, size_t* count) {
+// the key's resident pool slice (all of it for a key held whole) as uncompressed bytes -- wire: as wire bytes -- in pool order
+int single_pool_points(Groth16Key& key, int group, uint8_t* out, size_t capacity_points, size_t* count, bool wire) {
     Groth16Key* k = &key;
     if (group != 1 && group != 2) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pool_points: group must be 1 or 2");
     const MsmBases& b = group == 1 ? k->g1 : k->g2;
@@ -554,9 +579,10 @@ int single_pool_points(Groth16Key& key, int group, uint8_t* out, size_t capacity
     if (capacity_points < b.n) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pool_points: buffer too small");
     Ctx& c = ctx();
     DevBuf bytes, dense;
-    ZKCHK(bytes.alloc(aff_bytes(b.curve) * b.n));
     ZKCHK(dense.alloc(aff_bytes(b.curve) * b.n));
     ZKCHK(msm_bases_dense(b, 0, b.n, dense.p, c.stream));
+    if (wire) return points_affine_to_wire(b.curve, dense.p, b.n, out, c.stream);
+    ZKCHK(bytes.alloc(aff_bytes(b.curve) * b.n));
     ZKCHK(points_affine_to_bytes(b.curve, bytes.p, dense.p, b.n, c.stream));
     HIPCHK(hipMemcpyAsync(out, bytes.p, aff_bytes(b.curve) * b.n, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));

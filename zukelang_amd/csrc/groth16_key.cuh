@@ -58,7 +58,7 @@ struct Groth16Key {
 // Builds a key (whole: rank 0 of world 1, or rank's shard) on the CURRENT virtual device; nothing is registered under a handle.
 int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
                       const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, bool lagrange,
-                      bool shard_of_group = false, const void* d_g1 = nullptr, const void* d_g2 = nullptr);
+                      bool shard_of_group = false, const void* d_g1 = nullptr, const void* d_g2 = nullptr, bool wire = false);
 // keygen.hip: a whole key from pools the library generated on the device (dense affine points, pool order), registered under a new handle
 int groth16_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const void* d_g1, size_t g1_points,
                             const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle);
@@ -80,18 +80,18 @@ struct GroupKey;
 GroupKey* group_lookup(uint64_t handle);
 void group_release_all();
 int group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
-                 const uint8_t* pk_g2, size_t pk_g2_points, bool lagrange, uint64_t* handle);
+                 const uint8_t* pk_g2, size_t pk_g2_points, bool lagrange, uint64_t* handle, bool wire = false);
 int group_free(uint64_t handle);
 int group_reserve_slots(GroupKey& g, uint32_t count);
 int group_set_witness(GroupKey& g, const uint8_t* sol);
 int group_prove_async(GroupKey& g, const uint8_t* sol, const uint8_t* r, const uint8_t* s, uint32_t slot);
 int group_prove_wait(GroupKey& g, uint32_t slot, uint8_t proof[384]);
 int group_derive_lagrange(GroupKey& g);
-int group_pool_points(GroupKey& g, int group, uint8_t* out, size_t capacity_points, size_t* count);
+int group_pool_points(GroupKey& g, int group, uint8_t* out, size_t capacity_points, size_t* count, bool wire = false);
 int group_pool_layout(GroupKey& g, uint64_t* p1, uint64_t* p2);
 int group_qap_eval(GroupKey& g, const uint8_t* sol, uint8_t* v_out, uint8_t* w_out, uint8_t* h_out);
 int group_lagrange_pool_sizes(GroupKey& g, uint64_t* g1_points, uint64_t* g2_points);
 int single_qap_eval(Groth16Key& k, const uint8_t* sol, uint8_t* v_out, uint8_t* w_out, uint8_t* h_out);
-int single_pool_points(Groth16Key& k, int group, uint8_t* out, size_t capacity_points, size_t* count);
+int single_pool_points(Groth16Key& k, int group, uint8_t* out, size_t capacity_points, size_t* count, bool wire = false);
 
 }  // namespace zk

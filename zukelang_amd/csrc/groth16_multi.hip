@@ -109,7 +109,7 @@ static void trace(const char* what) {
     }
 }
 int group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
-                 const uint8_t* pk_g2, size_t pk_g2_points, bool lagrange, uint64_t* handle) {
+                 const uint8_t* pk_g2, size_t pk_g2_points, bool lagrange, uint64_t* handle, bool wire) {
     if (!handle || !mid || !pk_g1 || !pk_g2 || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "pk_upload: null argument");
     const size_t N = (size_t)ctx_count();
     auto key = std::make_unique<GroupKey>();
@@ -117,7 +117,7 @@ int group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const
     g.sub.resize(N);
     // every shard checks its own slice of the key points and builds the Fr-stage tables (any device may own a proof's Fr stage)
     const int rc = on_every_device(N, [&](int v) {
-        return groth16_key_build(g.sub[v], n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, (uint32_t)v, (uint32_t)N, lagrange, true);
+        return groth16_key_build(g.sub[v], n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, (uint32_t)v, (uint32_t)N, lagrange, true, nullptr, nullptr, wire);
     });
     if (rc != ZK_OK) {
         g.destroy();
@@ -174,19 +174,19 @@ int group_pool_layout(GroupKey& g, uint64_t* p1, uint64_t* p2) {
     *p2 = g.p2;
     return ZK_OK;
 }
-int group_pool_points(GroupKey& g, int group, uint8_t* out, size_t capacity_points, size_t* count) {
+int group_pool_points(GroupKey& g, int group, uint8_t* out, size_t capacity_points, size_t* count, bool wire) {
     if (group != 1 && group != 2) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pool_points: group must be 1 or 2");
     const uint64_t total = group == 1 ? g.p1 : g.p2;
     if (count) *count = total;
     if (!out) return ZK_OK;
     if (capacity_points < total) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pool_points: buffer too small");
     ZKCHK(g.check_idle("zk_groth16_pool_points: a proof is in flight on this key"));
-    const size_t pb = group == 1 ? 96 : 192;
+    const size_t pb = (group == 1 ? 96 : 192) / (wire ? 2 : 1);
     for (size_t v = 0; v < g.sub.size(); v++) {          // the shards are the pool in order
         DeviceScope ds((int)v);
         Groth16Key& k = *g.sub[v];
         const uint64_t lo = group == 1 ? k.lo1 : k.lo2, hi = group == 1 ? k.hi1 : k.hi2;
-        ZKCHK(single_pool_points(k, group, out + pb * lo, hi - lo, nullptr));
+        ZKCHK(single_pool_points(k, group, out + pb * lo, hi - lo, nullptr, wire));
     }
     return ZK_OK;
 }

@@ -129,6 +129,18 @@ int proof_points_to_bytes_dev(const void* d_g1, uint32_t n1, const uint32_t* off
 // bytes without the infinity bit are the identity here (msm_points.hip: point_decode)
 int points_bytes_to_affine(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, int* d_flag, hipStream_t s);
 int points_affine_to_bytes(Curve curve, void* d_bytes, const void* d_affine, uint64_t n, hipStream_t s);
+// ---- wire form (48 / 96 B per point, to_compressed_bytes): the compressed uploads and read-backs of keys and resident bases
+// host wire bytes -> the dense affine list at d_dense (n points; a rejected point is the identity): one copy up at the compressed stride, THE decompressor
+// (msm_points.hip: point_decompress), the endomorphism subgroup test when asked for, 8 bytes back.  *first = index << 3 | kind of the first bad point
+// (kind 2 encoding | 1 curve | 4 subgroup), all ones when every point is good; wire_verdict turns it into the call's status.  Waits for the stream.
+int points_from_wire(Curve curve, const uint8_t* host_wire, uint64_t n, void* d_dense, bool check_subgroup, hipStream_t s, unsigned long long* first);
+int wire_verdict(unsigned long long first);
+// the verdict alone (nothing kept): the status of the list's first bad point, ZK_OK when there is none
+int points_wire_check(Curve curve, const uint8_t* host_wire, uint64_t n, bool check_subgroup, hipStream_t s);
+// msm_bases_from_bytes for wire bytes: points_from_wire, then the table build over the same dense list
+int msm_bases_from_wire(MsmBases& b, Curve curve, const uint8_t* host_wire, uint64_t n, uint32_t c, bool precomp, hipStream_t s, bool check_subgroup);
+// n dense affine points (device) -> wire bytes (host), the identity as C0 00 .. 00: one launch, one copy down at the compressed stride.  Waits for the stream.
+int points_affine_to_wire(Curve curve, const void* d_affine, uint64_t n, uint8_t* host_out, hipStream_t s);
 // the subgroup tests of msm_points.hip (same answer on every point of the curve): none | [r] P = O, 254 doublings | by the curve's endomorphism, 2 x 63 in G1, 63 in G2
 enum SubgroupTest { SUBGROUP_NONE, SUBGROUP_ORDER, SUBGROUP_ENDO };
 // decode + curve check + `test` with one verdict byte per point (verdict_order.h: 0 good | 2 encoding | 1 curve | 4 subgroup); rejected points become the

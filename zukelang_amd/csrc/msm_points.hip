@@ -265,6 +265,32 @@ template <class F> __global__ __launch_bounds__(128) void k_decompress(uint8_t* 
     if (kind) first_failure(first, i, kind);
     aff_store<F>(dense + (size_t)B * i, out);
 }
+// The way back (to_compressed_bytes, curve.ml:213-219): a dense affine list -> wire bytes, one lane per point.  Out of Montgomery form, x big-endian
+// (G2: x.c1 | x.c0), the sign bit by y_is_larger -- the rule the decompressor reads it by -- and C0 00 .. 00 for the identity; 16-byte stores.
+FF_INLINE void wire_encode(uint8_t* xb, const Aff<Fp>& a) { fpw_to_be(xb, fp_from_mont(a.x)); }
+FF_INLINE void wire_encode(uint8_t* xb, const Aff<Fp2>& a) {
+    fpw_to_be(xb, fp_from_mont(a.x.c1));
+    fpw_to_be(xb + 48, fp_from_mont(a.x.c0));
+}
+FF_INLINE bool wire_sign(const Aff<Fp>& a) { return y_is_larger(fp_red2(a.y)); }
+FF_INLINE bool wire_sign(const Aff<Fp2>& a) { return y_is_larger(Fp2B<2>{fp_red2(a.y.c0), fp_red2(a.y.c1)}); }
+template <class F> __global__ __launch_bounds__(128) void k_compress(uint8_t* __restrict__ out, const uint8_t* __restrict__ dense, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int CB = FieldOps<F>::WORDS * 4, B = FieldOps<F>::WORDS * 8;
+    const Aff<F> a = aff_load<F>(dense + (size_t)B * i);
+    alignas(16) uint8_t xb[CB];
+    if (aff_is_inf(a)) {
+#pragma unroll
+        for (int k = 0; k < CB / 16; k++) reinterpret_cast<uint4*>(xb)[k] = make_uint4(0, 0, 0, 0);
+        xb[0] = 0xC0;
+    } else {
+        wire_encode(xb, a);
+        xb[0] |= wire_sign(a) ? 0xA0 : 0x80;
+    }
+#pragma unroll
+    for (int k = 0; k < CB / 16; k++) reinterpret_cast<uint4*>(out + (size_t)CB * i)[k] = reinterpret_cast<const uint4*>(xb)[k];
+}
 // The verifiers' form (verify_resident.hip): `per` points of every item -- a proof -- read where they lie in the item's wire bytes, point q of item j
 // at in + stride j + off[q], into the dense list dense[per j + q] with one verdict byte each.  Strides and offsets are multiples of 16.
 struct WireSlots {
@@ -398,13 +424,13 @@ template <SubgroupTest T, class F> FF_INLINE bool in_subgroup(const Aff<F>& p) {
 }
 // The kernels read `dense` (affine, on the curve; a point the decoder rejected is stored as the identity and skipped) and report in their caller's way:
 // one flag word per list, bit 4, plus -- `first` may be null -- the list readers' first-failure word of k_decompress_* ...
-template <class F> __global__ __launch_bounds__(128) void k_subgroup_check(const uint8_t* __restrict__ dense, uint64_t n, int* flag, unsigned long long* first) {
+template <class F, SubgroupTest T> __global__ __launch_bounds__(128) void k_subgroup_check(const uint8_t* __restrict__ dense, uint64_t n, int* flag, unsigned long long* first) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     constexpr int B = FieldOps<F>::WORDS * 8;
     const Aff<F> p = aff_load<F>(dense + B * i);
     if (aff_is_inf(p)) return;
-    if (!in_subgroup_order(p)) {
+    if (!in_subgroup<T>(p)) {
         atomicOr(flag, 4);
         if (first) atomicMin(first, (unsigned long long)(i << 3) | 4ull);
     }
@@ -666,8 +692,13 @@ int msm_bases_from_device_affine(MsmBases& b, Curve curve, const void* d_affine,
     ZKCHK(bases_setup(b, curve, n, c, precomp, in_subgroup));
     return curve == CURVE_G1 ? bases_finish<Fp>(b, d_affine, s) : bases_finish<Fp2>(b, d_affine, s);
 }
-static void launch_subgroup_check(Curve curve, const void* d_dense, uint64_t n, int* d_flag, unsigned long long* d_first, hipStream_t s) {
-    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_subgroup_check<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (const uint8_t*)d_dense, n, d_flag, d_first); });
+static void launch_subgroup_check(Curve curve, const void* d_dense, uint64_t n, int* d_flag, unsigned long long* d_first, hipStream_t s, SubgroupTest test = SUBGROUP_ORDER) {
+    for_curve(curve, [&](auto f) {
+        using F = FIELD_OF(f);
+        const dim3 grid = grid_for(n, 128);
+        if (test == SUBGROUP_ENDO) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<F, SUBGROUP_ENDO>), grid, dim3(128), 0, s, (const uint8_t*)d_dense, n, d_flag, d_first);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<F, SUBGROUP_ORDER>), grid, dim3(128), 0, s, (const uint8_t*)d_dense, n, d_flag, d_first);
+    });
 }
 int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, uint64_t n, uint32_t c, bool precomp, hipStream_t s, bool check_subgroup) {
     ZKCHK(bases_setup(b, curve, n, c, precomp, check_subgroup));      // folded digits only for points the [r] P = O test below has passed
@@ -690,6 +721,75 @@ int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, ui
     if (h & 4) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "a key point is on the curve but outside the prime-order subgroup (of_bytes_exn, curve.ml:199-212)");
     ZKCHK((curve == CURVE_G1 ? bases_finish<Fp>(b, dense.p, s) : bases_finish<Fp2>(b, dense.p, s)));
     HIPCHK(hipStreamSynchronize(s));          // `dense` is released on return: the table build has read it
+    return ZK_OK;
+}
+
+// ---- key points and MSM bases from their WIRE bytes (zk_*_pk_upload_compressed, zk_bases_upload_compressed): 48 / 96 B per point up, THE decompressor
+// straight into the dense list the table build reads, the endomorphism subgroup test, 8 bytes back.  No byte re-encoding, no point travels down.
+// *first: index << 3 | kind of the list's first bad point (kind 2 encoding, 1 curve, 4 subgroup), all ones = none.  Synchronises.
+int points_from_wire(Curve curve, const uint8_t* host_wire, uint64_t n, void* d_dense, bool check_subgroup, hipStream_t s, unsigned long long* first) {
+    *first = ~0ull;
+    if (!n) return ZK_OK;
+    const size_t cb = aff_bytes(curve) / 2;
+    DevBuf din, flag;
+    ZKCHK(din.alloc(cb * n));
+    ZKCHK(flag.alloc(16));                                  // the subgroup kernel's flag word | the first failure
+    HIPCHK(hipMemsetAsync(flag.p, 0, 8, s));
+    HIPCHK(hipMemsetAsync(flag.as<uint8_t>() + 8, 0xFF, 8, s));
+    unsigned long long* d_first = (unsigned long long*)(flag.as<uint8_t>() + 8);
+    HIPCHK(hipMemcpyAsync(din.p, host_wire, cb * n, hipMemcpyHostToDevice, s));
+    {
+        ScopedTimer t("key_decompress", s);
+        for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_decompress<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_dense, (const uint8_t*)din.as<uint8_t>(), n, d_first); });
+    }
+    if (check_subgroup) {
+        ScopedTimer t("subgroup_check", s);
+        launch_subgroup_check(curve, d_dense, n, flag.as<int>(), d_first, s, SUBGROUP_ENDO);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(first, d_first, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZK_OK;
+}
+int wire_verdict(unsigned long long first) {
+    if (first == ~0ull) return ZK_OK;
+    const int kind = (int)(first & 7);
+    if (kind == 2) ZK_FAIL(ZK_ERR_ARG, "wire point: the compression flag is not set, a coordinate is >= p, or the infinity bit is set on a string that is not C0 00 .. 00");
+    if (kind == 1) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "wire point: an abscissa is not on the curve");
+    ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "wire point: on the curve but outside the prime-order subgroup (of_compressed_bytes_exn, curve.ml:199-212)");
+}
+int points_wire_check(Curve curve, const uint8_t* host_wire, uint64_t n, bool check_subgroup, hipStream_t s) {
+    if (!n) return ZK_OK;
+    DevBuf dense;
+    unsigned long long first;
+    ZKCHK(dense.alloc(aff_bytes(curve) * n));
+    ZKCHK(points_from_wire(curve, host_wire, n, dense.p, check_subgroup, s, &first));
+    return wire_verdict(first);
+}
+int msm_bases_from_wire(MsmBases& b, Curve curve, const uint8_t* host_wire, uint64_t n, uint32_t c, bool precomp, hipStream_t s, bool check_subgroup) {
+    ZKCHK(bases_setup(b, curve, n, c, precomp, check_subgroup));      // folded digits only for points the subgroup test below has passed
+    DevBuf dense;
+    unsigned long long first;
+    ZKCHK(dense.alloc(aff_bytes(curve) * n));
+    ZKCHK(points_from_wire(curve, host_wire, n, dense.p, check_subgroup, s, &first));
+    ZKCHK(wire_verdict(first));
+    ZKCHK((curve == CURVE_G1 ? bases_finish<Fp>(b, dense.p, s) : bases_finish<Fp2>(b, dense.p, s)));
+    HIPCHK(hipStreamSynchronize(s));          // `dense` is released on return: the table build has read it
+    return ZK_OK;
+}
+// n dense affine points (device) -> their wire bytes (host)
+int points_affine_to_wire(Curve curve, const void* d_aff, uint64_t n, uint8_t* host_out, hipStream_t s) {
+    if (!n) return ZK_OK;
+    const size_t cb = aff_bytes(curve) / 2;
+    DevBuf dw;
+    ZKCHK(dw.alloc(cb * n));
+    {
+        ScopedTimer t("key_compress", s);
+        for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_compress<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, dw.as<uint8_t>(), (const uint8_t*)d_aff, n); });
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host_out, dw.p, cb * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return ZK_OK;
 }
 

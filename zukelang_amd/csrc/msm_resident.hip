@@ -208,7 +208,8 @@ static int res_lookup(uint64_t handle, ResidentBases** out) {
     return ZK_OK;
 }
 
-static int res_upload(int group, const uint8_t* points, size_t n, uint64_t* handle) {
+// wire: `points` holds wire bytes, 48 / 96 per point (zk_bases_upload_compressed)
+static int res_upload(int group, const uint8_t* points, size_t n, uint64_t* handle, bool wire = false) {
     if (!handle || !points) ZK_FAIL(ZK_ERR_ARG, "zk_bases_upload: null argument");
     if (group != 0 && group != 1) ZK_FAIL(ZK_ERR_ARG, "zk_bases_upload: group must be 0 (G1) or 1 (G2)");
     if (n == 0) ZK_FAIL(ZK_ERR_ARG, "zk_bases_upload: empty point list");
@@ -224,7 +225,8 @@ static int res_upload(int group, const uint8_t* points, size_t n, uint64_t* hand
     // handle keeps this verdict (without it no table folds)
     const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
     const bool chk = !(e_chk && atoi(e_chk) == 0);
-    ZKCHK(msm_bases_from_bytes(r.b, r.curve, points, n, msm_auto_window(n, true), true, s, chk));
+    if (wire) ZKCHK(msm_bases_from_wire(r.b, r.curve, points, n, msm_auto_window(n, true), true, s, chk));
+    else ZKCHK(msm_bases_from_bytes(r.b, r.curve, points, n, msm_auto_window(n, true), true, s, chk));
     r.short_max = r.curve == CURVE_G1 ? RESIDENT_SHORT_MAX_G1 : RESIDENT_SHORT_MAX_G2;
     r.ns = n < r.short_max ? n : r.short_max;
     if (r.ns) {
@@ -435,6 +437,7 @@ int short_bases_run(ShortBases& b, const uint32_t* d_scalars, const uint8_t* d_l
 using namespace zk;
 extern "C" {
 int zk_bases_upload(int group, const uint8_t* points, size_t n, uint64_t* handle) { return res_upload(group, points, n, handle); }
+int zk_bases_upload_compressed(int group, const uint8_t* points, size_t n, uint64_t* handle) { return res_upload(group, points, n, handle, true); }
 int zk_bases_info(uint64_t handle, int* group, uint64_t* n, uint64_t* short_max) {
     ResidentBases* r;
     ZKCHK(res_lookup(handle, &r));

@@ -300,8 +300,12 @@ static int pin_decide_shared_sort(PinKey& k, hipStream_t s) {
 // compact_in: -1 = decide here (the upload's consistency check of v_all / w_all against si, header comment: needs the WHOLE h pool, so rank 0 of a
 // group runs it and hands its verdict to the other shards), 0 / 1 = the verdict.
 static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
-                         const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, int compact_in) {
+                         const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, int compact_in,
+                         bool wire = false) {
+    // wire: pk_g1 / pk_g2 hold wire bytes, 48 / 96 per point (zk_pinocchio_pk_upload_compressed): the same regrouping at half the stride, every pool
+    // through msm_bases_from_wire
     if (!mid || !pk_g1 || !pk_g2) ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload: null argument");
+    const size_t B1 = wire ? 48 : 96, B2 = wire ? 96 : 192;
     Ctx& c = ctx();
     auto key = std::make_unique<PinKey>();
     PinKey& k = *key;
@@ -317,14 +321,20 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
     // si[0] must be the generator: ZKCompute.f subtracts `one * dy` -- G1.one, not a point of the key (pinocchio.ml:485) -- and the library lets that term
     // ride on si[0] (the h pool has no base of its own for it).  True of every key KeyGen.generate makes (si[0] = [s^0]); a key that breaks it is refused
     // here rather than proved with other bytes than the reference's.
-    if (memcmp(pk_g1 + 96 * (5 * nm), G1_GENERATOR_BYTES, 96) != 0)
+    // (on the wire the generator is its abscissa under the compression bit: y is the smaller root, so no sign bit)
+    bool si0_is_one = wire ? (pk_g1[48 * (5 * nm)] == (G1_GENERATOR_BYTES[0] | 0x80) && memcmp(pk_g1 + 48 * (5 * nm) + 1, G1_GENERATOR_BYTES + 1, 47) == 0)
+                           : memcmp(pk_g1 + 96 * (5 * nm), G1_GENERATOR_BYTES, 96) == 0;
+    if (!si0_is_one)
         ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload: si[0] is not the G1 generator (the blinding term -dy * one of pinocchio.ml:485 rides on si[0])");
     ZKCHK(frstage_init(k.fr, n, m, L, R, O, c.stream));
     // slices of the flattened key (pinocchio.ml:37-60; layout in include/zkmi355x.h)
-    const uint8_t *VV = pk_g1, *YY = VV + 96 * nm, *VAV = YY + 96 * nm, *YAY = VAV + 96 * nm, *BV = YAY + 96 * nm,
-                  *SI = BV + 96 * nm, *VALL = SI + 96 * (uint64_t)(n + 1), *WALL = VALL + 96 * (uint64_t)m, *ONES = WALL + 96 * (uint64_t)m;
-    const uint8_t *WW = pk_g2, *WAW = WW + 192 * nm, *ONES2 = WAW + 192 * nm + 192 * (uint64_t)(n + 1);
+    const uint8_t *VV = pk_g1, *YY = VV + B1 * nm, *VAV = YY + B1 * nm, *YAY = VAV + B1 * nm, *BV = YAY + B1 * nm,
+                  *SI = BV + B1 * nm, *VALL = SI + B1 * (uint64_t)(n + 1), *WALL = VALL + B1 * (uint64_t)m, *ONES = WALL + B1 * (uint64_t)m;
+    const uint8_t *WW = pk_g2, *WAW = WW + B2 * nm, *ONES2 = WAW + B2 * nm + B2 * (uint64_t)(n + 1);
     std::vector<uint8_t> buf;
+    auto bases = [&](MsmBases& b, Curve cv, const uint8_t* bytes, uint64_t cnt, bool precomp) -> int {
+        return wire ? msm_bases_from_wire(b, cv, bytes, cnt, 0, precomp, c.stream, k.in_subgroup) : msm_bases_from_bytes(b, cv, bytes, cnt, 0, precomp, c.stream, k.in_subgroup);
+    };
     // pool idx = base[0 .. cnt) | extras, of which this shard keeps [lo, hi)
     auto pool1 = [&](int idx, const uint8_t* base, uint64_t cnt, std::initializer_list<const uint8_t*> extras) -> int {
         const uint64_t full = cnt + extras.size();
@@ -333,28 +343,28 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
         const uint64_t lo = k.lo1[idx], hi = k.hi1[idx];
         if (hi == lo) return ZK_OK;
         buf.clear();
-        if (lo < cnt) buf.assign(base + 96 * lo, base + 96 * (hi < cnt ? hi : cnt));
+        if (lo < cnt) buf.assign(base + B1 * lo, base + B1 * (hi < cnt ? hi : cnt));
         uint64_t e = cnt;
         for (auto x : extras) {
-            if (e >= lo && e < hi) buf.insert(buf.end(), x, x + 96);
+            if (e >= lo && e < hi) buf.insert(buf.end(), x, x + B1);
             e++;
         }
-        return msm_bases_from_bytes(k.g1[idx], CURVE_G1, buf.data(), buf.size() / 96, 0, true, c.stream, k.in_subgroup);
+        return bases(k.g1[idx], CURVE_G1, buf.data(), buf.size() / B1, true);
     };
-    ZKCHK(pool1(0, VV, nm, {ONES + 96 * 0}));
-    ZKCHK(pool1(1, YY, nm, {ONES + 96 * 1}));
-    ZKCHK(pool1(2, VAV, nm, {ONES + 96 * 2}));
-    ZKCHK(pool1(3, YAY, nm, {ONES + 96 * 3}));
-    ZKCHK(pool1(4, BV, nm, {ONES + 96 * 4, ONES + 96 * 5, ONES + 96 * 6}));
+    ZKCHK(pool1(0, VV, nm, {ONES + B1 * 0}));
+    ZKCHK(pool1(1, YY, nm, {ONES + B1 * 1}));
+    ZKCHK(pool1(2, VAV, nm, {ONES + B1 * 2}));
+    ZKCHK(pool1(3, YAY, nm, {ONES + B1 * 3}));
+    ZKCHK(pool1(4, BV, nm, {ONES + B1 * 4, ONES + B1 * 5, ONES + B1 * 6}));
     const uint64_t ph_full = (uint64_t)n + 1 + 2 * (uint64_t)m;          // si | v_all | w_all are contiguous in the key
     int compact = compact_in;
     if (compact < 0) compact = 0;
     if (compact_in < 0 && pin_compact_wanted()) {
         // every point is decoded and checked as before (of_bytes_exn); the pool then keeps v_all | w_all only if they fail the check of the header comment
         MsmBases full;
-        ZKCHK(msm_bases_from_bytes(full, CURVE_G1, SI, ph_full, 0, false, c.stream, k.in_subgroup));
+        ZKCHK(bases(full, CURVE_G1, SI, ph_full, false));
         bool ok = false;
-        ZKCHK(pin_compact_check(k.fr, full, n, m, pin_rho_seed(SI, 96 * ph_full, n, m), &ok, c.stream));
+        ZKCHK(pin_compact_check(k.fr, full, n, m, pin_rho_seed(SI, B1 * ph_full, n, m), &ok, c.stream));          // the bytes the caller handed over, wire or not
         compact = ok ? 1 : 0;
     }
     k.compact = compact != 0;
@@ -365,12 +375,12 @@ static int pin_key_build(std::unique_ptr<PinKey>& out, uint32_t n, uint32_t m, c
         const uint64_t lo = k.lo2[idx], hi = k.hi2[idx];
         if (hi == lo) return ZK_OK;
         buf.clear();
-        if (lo < nm) buf.assign(base + 192 * lo, base + 192 * (hi < nm ? hi : nm));
-        if (hi == nm + 1) buf.insert(buf.end(), extra, extra + 192);
-        return msm_bases_from_bytes(k.g2[idx], CURVE_G2, buf.data(), buf.size() / 192, 0, true, c.stream, k.in_subgroup);
+        if (lo < nm) buf.assign(base + B2 * lo, base + B2 * (hi < nm ? hi : nm));
+        if (hi == nm + 1) buf.insert(buf.end(), extra, extra + B2);
+        return bases(k.g2[idx], CURVE_G2, buf.data(), buf.size() / B2, true);
     };
     ZKCHK(pool2(0, WW, ONES2));
-    ZKCHK(pool2(1, WAW, ONES2 + 192));
+    ZKCHK(pool2(1, WAW, ONES2 + B2));
     ZKCHK(pin_decide_shared_sort(k, c.stream));
     ZKCHK(k.mid_idx.alloc(4 * (nm ? nm : 1)));
     if (nm) HIPCHK(hipMemcpyAsync(k.mid_idx.p, mids.data(), 4 * nm, hipMemcpyHostToDevice, c.stream));
@@ -499,15 +509,16 @@ static int pin_check_idle(PinKey& k, const char* who) {
         if (k.slots[i] && k.slots[i]->busy) ZK_FAIL(ZK_ERR_ARG, who);
     return ZK_OK;
 }
-// this shard's slice of pool `pool` (0..5 G1, 6..7 G2) as uncompressed points at out (host)
-static int pin_slice_points(PinKey& k, int pool, uint8_t* out) {
+// this shard's slice of pool `pool` (0..5 G1, 6..7 G2) as uncompressed points -- wire: as wire bytes -- at out (host)
+static int pin_slice_points(PinKey& k, int pool, uint8_t* out, bool wire = false) {
     const MsmBases& b = pool < PIN_G1 ? k.g1[pool] : k.g2[pool - PIN_G1];
     if (!b.n) return ZK_OK;
     Ctx& c = ctx();
     DevBuf bytes, dense;
-    ZKCHK(bytes.alloc(aff_bytes(b.curve) * b.n));
     ZKCHK(dense.alloc(aff_bytes(b.curve) * b.n));
     ZKCHK(msm_bases_dense(b, 0, b.n, dense.p, c.stream));
+    if (wire) return points_affine_to_wire(b.curve, dense.p, b.n, out, c.stream);
+    ZKCHK(bytes.alloc(aff_bytes(b.curve) * b.n));
     ZKCHK(points_affine_to_bytes(b.curve, bytes.p, dense.p, b.n, c.stream));
     HIPCHK(hipMemcpyAsync(out, bytes.p, aff_bytes(b.curve) * b.n, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
@@ -687,7 +698,7 @@ static void pin_release() {
 }
 static CleanupRegistrar g_pin_cleanup(pin_release);
 static int pin_group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
-                            const uint8_t* pk_g2, size_t pk_g2_points, uint64_t* handle) {
+                            const uint8_t* pk_g2, size_t pk_g2_points, uint64_t* handle, bool wire = false) {
     const int N = ctx_count();
     auto grp = std::make_unique<PinGroup>();
     PinGroup& g = *grp;
@@ -699,7 +710,7 @@ static int pin_group_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_cs
     for (int v = 0; v < N && rc == ZK_OK; v++) {
         DeviceScope ds(v);
         try {
-            rc = pin_key_build(g.sub[v], n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, (uint32_t)v, (uint32_t)N, compact);
+            rc = pin_key_build(g.sub[v], n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, (uint32_t)v, (uint32_t)N, compact, wire);
         } catch (const std::exception& e) {
             rc = set_error(ZK_ERR_HIP, e.what(), __FILE__, __LINE__);
         }
@@ -780,6 +791,8 @@ static int pin_group_derive(PinGroup& g) {
 }  // namespace zk
 
 using namespace zk;
+static int pin_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
+                               const uint8_t* pk_g2, size_t pk_g2_points, const uint8_t* h_lagrange, uint64_t* handle, bool wire);
 extern "C" {
 
 int zk_pinocchio_pk_upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
@@ -799,13 +812,18 @@ int zk_pinocchio_pk_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, con
                                     const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, const uint8_t* h_lagrange, uint64_t* handle) {
     if (!handle || !mid || !pk_g1 || !pk_g2 || !h_lagrange || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload_lagrange: null argument");
     ZKCHK(ensure_init());
+    return pin_upload_lagrange(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, h_lagrange, handle, false);
+}
+static int pin_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
+                               const uint8_t* pk_g2, size_t pk_g2_points, const uint8_t* h_lagrange, uint64_t* handle, bool wire) {
     if (ctx_count() > 1) ZK_FAIL(ZK_ERR_ARG, "pinocchio pk_upload_lagrange: single-device keys only (a multi-device key derives its h bases: zk_pinocchio_pk_derive_lagrange)");
     Ctx& c = ctx();
     std::unique_ptr<PinKey> key;
-    ZKCHK(pin_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, -1));
+    ZKCHK(pin_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, -1, wire));
     PinKey& k = *key;
-    MsmBases hl;          // decoding, curve equation and (unless ZK_KEY_SUBGROUP_CHECK=0) [r] P = O, as for every point of the key
-    ZKCHK(msm_bases_from_bytes(hl, CURVE_G1, h_lagrange, n, 0, false, c.stream, k.in_subgroup));
+    MsmBases hl;          // decoding, curve equation and (unless ZK_KEY_SUBGROUP_CHECK=0) the subgroup test, as for every point of the key
+    if (wire) ZKCHK(msm_bases_from_wire(hl, CURVE_G1, h_lagrange, n, 0, false, c.stream, k.in_subgroup));
+    else ZKCHK(msm_bases_from_bytes(hl, CURVE_G1, h_lagrange, n, 0, false, c.stream, k.in_subgroup));
     const uint64_t ph = pin_h_points(n, m, true, k.compact);
     DevBuf pool;
     ZKCHK(pool.alloc(96 * ph));
@@ -817,6 +835,35 @@ int zk_pinocchio_pk_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, con
     ZKCHK(pin_install_derived(k, p, c.stream));
     *handle = g_pin.add(std::move(key));
     return ZK_OK;
+}
+// The evaluation key from its wire bytes (include/zkmi355x.h); h_lagrange != NULL: as zk_pinocchio_pk_upload_lagrange.  The pools are regrouped and decoded
+// one by one (and slice by slice over a device list), so a refusal says only that some pool holds a bad point: the call then reads the lists in the
+// caller's order -- G1, the G2 points the key keeps, h_lagrange -- for the verdict of the FIRST one.  A good key never pays for that pass.
+int zk_pinocchio_pk_upload_compressed(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const uint8_t* pk_g1, size_t pk_g1_points,
+                                      const uint8_t* pk_g2, size_t pk_g2_points, const uint8_t* h_lagrange, uint64_t* handle) {
+    if (!handle || !mid || !pk_g1 || !pk_g2 || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_pk_upload_compressed: null argument");
+    ZKCHK(ensure_init());
+    int rc;
+    if (h_lagrange) rc = pin_upload_lagrange(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, h_lagrange, handle, true);
+    else if (ctx_count() > 1) rc = pin_group_upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, handle, true);
+    else {
+        std::unique_ptr<PinKey> key;
+        rc = pin_key_build(key, n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, -1, true);
+        if (rc == ZK_OK) *handle = g_pin.add(std::move(key));
+    }
+    if (rc != ZK_ERR_ARG && rc != ZK_ERR_NOT_ON_CURVE) return rc;
+    if (h_lagrange && ctx_count() > 1) return rc;
+    uint64_t nm = 0;
+    for (uint32_t i = 0; i < m; i++) nm += mid[i] ? 1 : 0;
+    if (pk_g1_points != 5 * nm + (n + 1) + 2 * (uint64_t)m + 7 || pk_g2_points != 2 * nm + (n + 1) + 2) return rc;
+    const bool chk = key_subgroup_check();
+    DeviceScope ds(0);
+    hipStream_t s = ctx().stream;
+    int first = points_wire_check(CURVE_G1, pk_g1, pk_g1_points, chk, s);
+    if (first == ZK_OK) first = points_wire_check(CURVE_G2, pk_g2, 2 * nm, chk, s);                                     // ww | waw
+    if (first == ZK_OK) first = points_wire_check(CURVE_G2, pk_g2 + 96 * (2 * nm + (n + 1)), 2, chk, s);                // the two appended points
+    if (first == ZK_OK && h_lagrange) first = points_wire_check(CURVE_G1, h_lagrange, n, chk, s);
+    return first != ZK_OK ? first : rc;
 }
 // The h pool of an uploaded key (si | v_all | w_all, or si alone: compact) rewritten for the VALUES of h: [lambda_t(s)]_1 derived from the powers si in the
 // exponent (lagrange_derive.hip: the transposed interpolation over the points n .. 2n-2), [Z(s)]_1 = <si, Z> once, [1] = si[0], and for the compact form
@@ -838,7 +885,7 @@ int zk_pinocchio_pk_derive_lagrange(uint64_t handle) {
     ZKCHK(pin_derive_pool(k, old_dense.as<uint8_t>(), pool, c.stream));
     return pin_install_derived(k, pool.as<uint8_t>(), c.stream);
 }
-int zk_pinocchio_pool_points(uint64_t handle, int pool, uint8_t* out, size_t capacity_points, size_t* count) {
+static int pin_pool_points(uint64_t handle, int pool, uint8_t* out, size_t capacity_points, size_t* count, bool wire) {
     if (pool < 0 || pool >= PIN_G1 + PIN_G2) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_pool_points: pool 0..5 (G1) or 6..7 (G2)");
     if (PinGroup* g = g_pin_groups.find(handle)) {          // the handle holds the whole pools (its devices' slices are an internal matter)
         PinKey& k0 = *g->sub[0];
@@ -847,11 +894,11 @@ int zk_pinocchio_pool_points(uint64_t handle, int pool, uint8_t* out, size_t cap
         if (!out) return ZK_OK;
         if (capacity_points < total) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_pool_points: buffer too small");
         ZKCHK(g->check_idle("zk_pinocchio_pool_points: a proof is in flight on this key"));
-        const size_t pb = pool < PIN_G1 ? 96 : 192;
+        const size_t pb = (pool < PIN_G1 ? 96 : 192) / (wire ? 2 : 1);
         for (size_t v = 0; v < g->sub.size(); v++) {
             DeviceScope ds((int)v);
             PinKey& k = *g->sub[v];
-            ZKCHK(pin_slice_points(k, pool, out + pb * (pool < PIN_G1 ? k.lo1[pool] : k.lo2[pool - PIN_G1])));
+            ZKCHK(pin_slice_points(k, pool, out + pb * (pool < PIN_G1 ? k.lo1[pool] : k.lo2[pool - PIN_G1]), wire));
         }
         return ZK_OK;
     }
@@ -861,7 +908,13 @@ int zk_pinocchio_pool_points(uint64_t handle, int pool, uint8_t* out, size_t cap
     if (count) *count = b.n;
     if (!out) return ZK_OK;
     if (capacity_points < b.n) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_pool_points: buffer too small");
-    return pin_slice_points(*kp, pool, out);
+    return pin_slice_points(*kp, pool, out, wire);
+}
+int zk_pinocchio_pool_points(uint64_t handle, int pool, uint8_t* out, size_t capacity_points, size_t* count) {
+    return pin_pool_points(handle, pool, out, capacity_points, count, false);
+}
+int zk_pinocchio_pool_points_compressed(uint64_t handle, int pool, uint8_t* out, size_t capacity_points, size_t* count) {
+    return pin_pool_points(handle, pool, out, capacity_points, count, true);
 }
 int zk_pinocchio_pk_free(uint64_t handle) {
     if (std::unique_ptr<PinGroup> g = g_pin_groups.take(handle)) {

@@ -159,6 +159,12 @@ class _Group:
         return out.tobytes()
 
     @classmethod
+    def resident_compressed(cls, wire):
+        """`resident` for points in wire form (48 / 96 B each, back to back: zk_bases_upload_compressed): decoded on the device, no uncompressed copy on
+        the host.  The identity is C0 00 .. 00 only; a refused point raises the JSON readers' ValueError."""
+        return ResidentBases(cls, wire, compressed=True)
+
+    @classmethod
     def of_compressed_bytes_many(cls, comp):
         """of_compressed_bytes_exn (curve.ml:199-212) mapped over a list ON THE GPU (zk_g1/g2_decompress_batch): `comp` = the compressed points back
         to back; returns the uncompressed points back to back.  Square roots, curve and subgroup checks per point, as the one-point host call."""
@@ -177,15 +183,19 @@ class ResidentBases:
     then multiplied by many scalar vectors.  apply_powers(cs) = G.apply_powers cs points (curve.ml:112-118) over the first len(cs) points;
     apply_powers_many([cs_0, cs_1, ...]) runs them all in one call.  Free with close() (or a `with` block); dropping the object frees it too."""
 
-    def __init__(self, group, points):
+    def __init__(self, group, points, compressed=False):
         self.group = group
         self.handle = None
         p = _np(points)
-        n = len(p) // group.POINT_BYTES
-        if len(p) != n * group.POINT_BYTES:
+        size = group.COMPRESSED_BYTES if compressed else group.POINT_BYTES
+        n = len(p) // size
+        if len(p) != n * size:
             raise ValueError("resident bases: length is not a multiple of the point size")
         h = C.c_uint64()
-        _lib.check(_lib.lib().zk_bases_upload(C.c_int(0 if group.POINT_BYTES == 96 else 1), _p(p), C.c_size_t(n), C.byref(h)))
+        if compressed:
+            _lib.check_points(_lib.lib().zk_bases_upload_compressed(C.c_int(0 if group.POINT_BYTES == 96 else 1), _p(p), C.c_size_t(n), C.byref(h)))
+        else:
+            _lib.check(_lib.lib().zk_bases_upload(C.c_int(0 if group.POINT_BYTES == 96 else 1), _p(p), C.c_size_t(n), C.byref(h)))
         self.handle = h.value
         nn, sm = C.c_uint64(), C.c_uint64()
         _lib.check(_lib.lib().zk_bases_info(C.c_uint64(self.handle), None, C.byref(nn), C.byref(sm)))

@@ -413,6 +413,25 @@ class Groth16:
         _lib.check(rc)
         self.handle = h
 
+    @classmethod
+    def from_compressed(cls, circuit: R1CS, g1_wire, g2_wire, lagrange=False):
+        """A prover from the key's WIRE bytes (zk_groth16_pk_upload_compressed): the pools of zk_groth16_pk_upload -- lagrange=True: of
+        zk_groth16_pk_upload_lagrange -- with every point as the reference's JSON holds it, 48 / 96 bytes (wire.groth16_pkey_bytes_of_json, or
+        pool_points(compressed=True) of a derived key).  The points are decoded and checked on the device; the identity is C0 00 .. 00 only.  A refused
+        point raises the JSON readers' ValueError."""
+        g1 = np.ascontiguousarray(np.frombuffer(bytes(g1_wire), dtype=np.uint8))
+        g2 = np.ascontiguousarray(np.frombuffer(bytes(g2_wire), dtype=np.uint8))
+        if len(g1) % 48 or len(g2) % 96:
+            raise ValueError("from_compressed: G1 points are 48 bytes, G2 points 96")
+        mid = np.ascontiguousarray(circuit.mid, dtype=np.uint8)
+        L, R, O = _csr(circuit.L), _csr(circuit.R), _csr(circuit.O)
+        h = C.c_uint64()
+        _lib.check_points(_lib.lib().zk_groth16_pk_upload_compressed(circuit.n, circuit.m, C.byref(L), C.byref(R), C.byref(O), _p(mid), _p(g1), len(g1) // 48,
+                                                                     _p(g2), len(g2) // 96, _lib.KEY_FORMS["lagrange" if lagrange else "tau_powers"], C.byref(h)))
+        self = cls.__new__(cls)
+        self.circuit, self.rank, self.world, self._keep, self.handle = circuit, 0, 1, (circuit,), h
+        return self
+
     def derive_lagrange(self):
         """Turns the uploaded reference-format key into its Lagrange form on the device (zk_groth16_pk_derive_lagrange: once per key,
         O(n log^2 n) scalar multiplications, no tau needed); the proofs stay byte-identical, the per-proof basis conversion disappears."""
@@ -470,12 +489,14 @@ class Groth16:
         _lib.check(_lib.lib().zk_groth16_pk_shard(self.handle, C.c_uint32(rank), C.c_uint32(world)))
         self.rank, self.world = rank, world
 
-    def pool_points(self, group):
-        """The resident base pool (1 = G1, 2 = G2) as uncompressed bytes, in pool order."""
+    def pool_points(self, group, compressed=False):
+        """The resident base pool (1 = G1, 2 = G2) as uncompressed bytes, in pool order; compressed=True: in wire form (48 / 96 B per point, encoded
+        on the device: what from_compressed takes back)."""
+        fn = _lib.lib().zk_groth16_pool_points_compressed if compressed else _lib.lib().zk_groth16_pool_points
         cnt = C.c_size_t()
-        _lib.check(_lib.lib().zk_groth16_pool_points(self.handle, C.c_int(group), None, C.c_size_t(0), C.byref(cnt)))
-        out = np.zeros(cnt.value * (96 if group == 1 else 192), dtype=np.uint8)
-        _lib.check(_lib.lib().zk_groth16_pool_points(self.handle, C.c_int(group), _p(out), C.c_size_t(cnt.value), C.byref(cnt)))
+        _lib.check(fn(self.handle, C.c_int(group), None, C.c_size_t(0), C.byref(cnt)))
+        out = np.zeros(cnt.value * (96 if group == 1 else 192) // (2 if compressed else 1), dtype=np.uint8)
+        _lib.check(fn(self.handle, C.c_int(group), _p(out), C.c_size_t(cnt.value), C.byref(cnt)))
         return out
 
     def close(self):

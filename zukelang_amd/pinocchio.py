@@ -198,18 +198,44 @@ class _Prover:
         """A prover whose key starts in its derived form: pkey plus the stored h bases (see `lagrange` above)."""
         return cls(circuit, pkey, lagrange=h_lagrange)
 
+    @classmethod
+    def from_compressed(cls, circuit: R1CS, g1_wire, g2_wire, h_lagrange=None):
+        """A prover from the evaluation key's WIRE bytes (zk_pinocchio_pk_upload_compressed): the pools of zk_pinocchio_pk_upload with every point as the
+        reference's JSON holds it, 48 / 96 bytes (wire.pinocchio_pkey_bytes_of_json); h_lagrange = the stored h bases of a derived key, n points of 48
+        bytes (the first n of pool_points(5, compressed=True)).  Decoded and checked on the device; the identity is C0 00 .. 00 only.  A refused point
+        raises the JSON readers' ValueError."""
+        g1 = np.ascontiguousarray(np.frombuffer(bytes(g1_wire), dtype=np.uint8))
+        g2 = np.ascontiguousarray(np.frombuffer(bytes(g2_wire), dtype=np.uint8))
+        if len(g1) % 48 or len(g2) % 96:
+            raise ValueError("from_compressed: G1 points are 48 bytes, G2 points 96")
+        hl = None
+        if h_lagrange is not None:
+            hl = np.ascontiguousarray(np.frombuffer(bytes(h_lagrange), dtype=np.uint8))
+            if len(hl) != 48 * circuit.n:
+                raise ValueError("h_lagrange: n points [lambda_t(s)] (n-1) | [Z(s)] of 48 bytes each")
+        mid = np.ascontiguousarray(circuit.mid, dtype=np.uint8)
+        L, R, O = _csr(circuit.L), _csr(circuit.R), _csr(circuit.O)
+        h = C.c_uint64()
+        _lib.check_points(_lib.lib().zk_pinocchio_pk_upload_compressed(circuit.n, circuit.m, C.byref(L), C.byref(R), C.byref(O), _p(mid), _p(g1), len(g1) // 48,
+                                                                       _p(g2), len(g2) // 96, None if hl is None else _p(hl), C.byref(h)))
+        self = cls.__new__(cls)
+        self.circuit, self._keep, self.handle = circuit, (circuit,), h
+        return self
+
     def derive_lagrange(self):
         """zk_pinocchio_pk_derive_lagrange: the h pool rewritten for the values of h (bases derived from the key's own powers si on the
         device, once); afterwards every proof skips the basis conversion.  Proof bytes do not change.  Pool 5 becomes
         [lambda_t(s)] (n-1) | [Z(s)] | [1] | [s^(n-1)] (compact, the default) or [lambda_t(s)] | [Z(s)] | [1] | v_all | w_all."""
         _lib.check(_lib.lib().zk_pinocchio_pk_derive_lagrange(self.handle))
 
-    def pool_points(self, pool):
-        """A resident base pool as uncompressed bytes, in pool order: 0..5 the G1 products (5 = the h pool), 6..7 the G2 products."""
+    def pool_points(self, pool, compressed=False):
+        """A resident base pool as uncompressed bytes, in pool order: 0..5 the G1 products (5 = the h pool), 6..7 the G2 products; compressed=True: in
+        wire form (48 / 96 B per point, encoded on the device)."""
+        fn = _lib.lib().zk_pinocchio_pool_points_compressed if compressed else _lib.lib().zk_pinocchio_pool_points
         cnt = C.c_size_t()
-        _lib.check(_lib.lib().zk_pinocchio_pool_points(self.handle, C.c_int(pool), None, C.c_size_t(0), C.byref(cnt)))
-        out = np.zeros(cnt.value * (96 if pool < 6 else 192), dtype=np.uint8)
-        _lib.check(_lib.lib().zk_pinocchio_pool_points(self.handle, C.c_int(pool), _p(out), C.c_size_t(cnt.value), C.byref(cnt)))
+        _lib.check(fn(self.handle, C.c_int(pool), None, C.c_size_t(0), C.byref(cnt)))
+        out = np.zeros(cnt.value * (96 if pool < 6 else 192) // (2 if compressed else 1), dtype=np.uint8)
+        _lib.check(fn(self.handle, C.c_int(pool), _p(out), C.c_size_t(cnt.value), C.byref(cnt)))
         return out
 
     def pool_size(self, pool):

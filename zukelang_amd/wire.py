@@ -292,6 +292,24 @@ def groth16_pkey_of_json(data):
     return PKey(np.frombuffer(g1, dtype=np.uint8), np.frombuffer(g2, dtype=np.uint8)), mid_vars
 
 
+def _wire_list(bs, size):
+    """Point strings -> their bytes back to back; only the shape is checked (a JSON string of `size` bytes each)."""
+    for b in bs:
+        _need(isinstance(b, (bytes, bytearray)), "a point is a JSON string")
+        _need(len(b) == size, "a compressed G%d point is %d bytes" % (size // 48, size))
+    return b"".join(bytes(b) for b in bs)
+
+
+@_reader
+def groth16_pkey_bytes_of_json(data):
+    """A JSON proving key -> (g1_wire, g2_wire, mid_vars): the pools of zk_groth16_pk_upload with every point as the record holds it, 48 / 96 bytes, for
+    Groth16.from_compressed.  No square root and no library call here: the points are decoded, once, on the device."""
+    d = loads(data)
+    g1 = _wire_list([d["a"], d["d1"], d["b1"]] + list(d["ti1"]) + list(d["tiztd"]) + [b[1] for b in d["ltd_mid"]], 48)
+    g2 = _wire_list([d["b2"], d["d2"]] + list(d["ti2"]), 96)
+    return g1, g2, [(b[0][0].decode("latin-1"), b[0][1]) for b in d["ltd_mid"]]
+
+
 # ---- Pinocchio proof (pinocchio.ml:195-208)
 _PIN_FIELDS = (("vv", 1), ("ww", 2), ("yy", 1), ("h", 1), ("vavv", 1), ("waww", 2), ("yayy", 1), ("bvwy", 1))
 
@@ -382,6 +400,23 @@ def pinocchio_pkey_of_json(data):
                      + [d[f] for f in ("vt", "yt", "vavt", "yayt", "vbt", "wbt", "ybt")])
     g2 = g2s_of_json(m2("ww") + m2("waw") + list(d["si2"]) + [d["wt"], d["wawt"]])
     return (PKey(np.frombuffer(g1, dtype=np.uint8), np.frombuffer(g2, dtype=np.uint8)), len(d["si"]) - 1, mid_vars, all_vars)
+
+
+@_reader
+def pinocchio_pkey_bytes_of_json(data):
+    """A JSON evaluation key -> (g1_wire, g2_wire, mid_vars): the flat pools above with every point as the record holds it, 48 / 96 bytes, for
+    pinocchio.ZK / NonZK.from_compressed.  The checks of pinocchio_pkey_of_json on the variable domains; no square root and no library call."""
+    d = loads(data)
+    vars_of = lambda f: [(b[0][0].decode("latin-1"), b[0][1]) for b in d[f]]
+    pts = lambda f: [b[1] for b in d[f]]
+    mid_vars, all_vars = vars_of("vv"), vars_of("v_all")
+    for f in ("ww", "yy", "vav", "waw", "yay", "bvwy"):
+        _need(vars_of(f) == mid_vars, "Pinocchio pkey: the I_mid maps must share one domain")
+    _need(vars_of("w_all") == all_vars, "key / record lengths or variable domains do not match")
+    g1 = _wire_list(pts("vv") + pts("yy") + pts("vav") + pts("yay") + pts("bvwy") + list(d["si"]) + pts("v_all") + pts("w_all")
+                    + [d[f] for f in ("vt", "yt", "vavt", "yayt", "vbt", "wbt", "ybt")], 48)
+    g2 = _wire_list(pts("ww") + pts("waw") + list(d["si2"]) + [d["wt"], d["wawt"]], 96)
+    return g1, g2, mid_vars
 
 
 def pinocchio_vkey_to_json(vk, io_vars):
