@@ -434,6 +434,43 @@ int zk_pinocchio_prove_async(uint64_t handle, const uint8_t* sol, const uint8_t 
                              const uint8_t dy[32], uint32_t slot);
 int zk_pinocchio_prove_wait(uint64_t handle, uint32_t slot, uint8_t proof[960]);
 
+/* ---- a batch of witnesses in one call, the proofs out as WIRE bytes ------------------------------------------------------------------------
+ * Groth16.prove (groth16.ml:123-161,235-237) and ZKCompute.f / Compute.f (pinocchio.ml:427-514) over `count` witnesses on one key, every proof
+ * written as the reference's proof record holds it (groth16.ml:110-114, pinocchio.ml:195-208: compressed points, 48 B per G1 and 96 B per G2 point in
+ * declaration order) -- the bytes zk_*_verify_resident_compressed take and the strings of the record's JSON.  The call keeps `in_flight` proofs in
+ * flight on slots 0 .. in_flight-1 of the handle (allocated as zk_*_reserve_slots allocates them), each in the form that leaves its sums on the
+ * device, collects them in one slab (at most 8192 proofs each) and converts a whole slab at once: one lane per point, one inversion, the sign bit,
+ * one copy to the host.  Per proof the host waits for one event; there is no conversion launch and no copy per proof.
+ *   sols: witness i at sols + i * m * 32, or NULL: the witness made resident by zk_*_set_witness, for every proof.
+ *   rs / blind: the randomness of proof i in the order the reference draws it (groth16.ml:124-125: r | s; pinocchio.ml:428-430: dv | dw | dy; all
+ *     zero gives Compute.f, NonZK.prove).
+ *   in_flight: 1 .. 15; 0 = the library's default, 14 (what the headline rate is measured with); never more than count.  Every slot holds the working
+ *     memory of a proof: a caller short of device memory passes a smaller number.
+ *   proofs: proof i at proofs + i * 192 (A 48 | B 96 | C 48) or + i * 480 (vv 48 | ww 96 | yy 48 | h 48 | vavv 48 | waww 96 | yayy 48 | bvwy 48),
+ *     byte for byte what zk_g1/g2_compress give for the points zk_groth16_prove / zk_pinocchio_prove returns for the same handle, witness and
+ *     randomness; the identity is C0 00 .. 00.
+ *   status[i]: the code that single call would return -- ZK_OK, ZK_ERR_REMAINDER, ZK_ERR_SCALAR_RANGE.  The bytes of a failed proof are ALL ZERO:
+ *     no compression flag, so no verifier takes them for a proof (zk_*_verify_resident_compressed: ZK_ERR_ARG).  A failed proof changes nothing for
+ *     its neighbours.  The call returns ZK_OK when the batch ran, whatever the statuses.
+ * Before the device is touched: null rs / blind, proofs or status, in_flight > 15, count > 2^24 -> ZK_ERR_ARG; count = 0 -> ZK_OK, nothing is touched;
+ * an unknown handle -> ZK_ERR_HANDLE (without a GPU: ZK_ERR_HIP); null sols without a resident witness -> ZK_ERR_ARG; a proof in flight on any slot
+ * of the handle -> ZK_ERR_ARG, and that proof stays collectable.  Afterwards every slot is idle and the single calls give the bytes they gave before.
+ * Every key form of a one-device handle is served (tau powers, Lagrange uploaded, derived, generated, uploaded compressed).  A handle over a device
+ * list of several entries is served with the same bytes, proof by proof through the per-proof path with ONE proof in flight (in_flight is not read),
+ * then the same conversion on the first device.  The shards of the one-process-per-GPU path (zk_groth16_pk_upload_sharded, zk_groth16_pk_shard)
+ * produce partial sums only: ZK_ERR_ARG.  Kernel k_proofs_to_wire (profiles/prove_many_kernel_resources.txt), timer family prove_to_wire. */
+int zk_groth16_prove_many_compressed(uint64_t handle,
+        const uint8_t* sols   /* count * m * 32, or NULL: the resident witness for every proof */,
+        const uint8_t* rs     /* count * 64: r | s of proof i, the order the reference draws them */,
+        uint32_t count, uint32_t in_flight /* 1..15; 0 = library default */,
+        uint8_t* proofs       /* count * 192: A 48 | B 96 | C 48 */,
+        int32_t* status       /* count */);
+int zk_pinocchio_prove_many_compressed(uint64_t handle,
+        const uint8_t* sols, const uint8_t* blind /* count * 96: dv | dw | dy */,
+        uint32_t count, uint32_t in_flight,
+        uint8_t* proofs       /* count * 480: vv | ww | yy | h | vavv | waww | yayy | bvwy */,
+        int32_t* status);
+
 /* ---- verify surface (scope row f1): Curve.S.Pairing.pairing (src/lib/zk/curve.mli:46-54) ---------------
  * Host code (a handful of pairings per proof, as in the reference, where they are calls into its external
  * library): Groth16 verify = 3 pairings (groth16.ml:163-173), Pinocchio Verify.f = 13 (pinocchio.ml:254-420).
@@ -664,6 +701,14 @@ int zk_selftest_subgroup(int group, int method, const uint8_t* points, size_t n,
  * in the ABI's uncompressed bytes (96 / 192 B) when the verdict is 0 or 4, zero bytes otherwise.  A null pointer, n = 0 or another group -> ZK_ERR_ARG
  * before the device is touched. */
 int zk_selftest_point_decompress(int group, const uint8_t* in /* n * 48 | n * 96 */, size_t n, uint8_t* out /* n * 96 | n * 192 */, uint8_t* verdict);
+/* The conversion launch of zk_*_prove_many_compressed on points the caller chooses (tests/test_gpu_prove_many.py): n pairs of an affine point of group
+ * 0 (G1, 96 B) or 1 (G2, 192 B) in the ABI's uncompressed bytes and a scalar 0 < z < r (32 B little-endian).  The device forms the XYZZ point
+ * (x z^2, y z^3, z^2, z^3) -- the all-zero pair stands for the identity (zz = 0) -- and runs k_proofs_to_wire on the n points as a batch of n proofs
+ * of one point each; out[i] = the point's wire bytes, what zk_g1/g2_compress give for (x, y).  Neither curve nor subgroup is checked: a test can feed
+ * coordinates no proof reaches.  A null pointer, n = 0, n >= 2^24 or another group -> ZK_ERR_ARG before the device is touched; a coordinate >= p, z = 0
+ * or z >= r -> ZK_ERR_ARG. */
+int zk_selftest_proof_wire(int group, const uint8_t* affine /* n * 96 | 192 */, const uint8_t* z /* n * 32, 0 < z < r */, size_t n,
+                           uint8_t* out /* n * 48 | 96 */);
 /* Every form of the device's group law on bare operands (tests/test_gpu_group_law.py), each run by a kernel of the translation unit that builds the
  * form for production, with that unit's flags.  group 0 = G1, 1 = G2 (on lane pairs).  a[i]: an XYZZ point as four field elements x, y, zz, zzz
  * (x_affine = x / zz, y_affine = y / zzz, zz^3 = zzz^2; zz = 0 is the identity whatever x and y are), each 48 B big-endian -- in G2 96 B, imaginary

@@ -264,6 +264,16 @@ module Make (C : Curve.S) = struct
     in
     go 0 [] [] jobs
 
+  (* The same batch in ONE library call, the proofs as their wire bytes (zk_groth16_prove_many_compressed): a 48 | b 96 | c 48 per proof, the strings of
+     proof_to_yojson (groth16.ml:110-114) and what Resident.verify_many_compressed takes.  The library keeps the proofs in flight itself; nothing is
+     decoded or compressed on the host. *)
+  let prove_many_compressed (qap : qap) (pkey : pkey) (sol : f Var.Map.t) (jobs : (Fr.t * Fr.t) list) : bytes list =
+    let handle = handle_of qap pkey in
+    if not (Var.Set.equal (Var.Map.domain sol) (Var.Map.domain qap.v)) then assert false;
+    Mi355x.(check (zk_groth16_set_witness handle (bytes_start (fr_bytes (values sol)))));
+    let rnd = Mi355x.cat (List.concat_map (fun (r, s) -> [ Fr.to_bytes r; Fr.to_bytes s ]) jobs) in
+    Mi355x.prove_many_compressed Mi355x.zk_groth16_prove_many_compressed handle ~rnd ~count:(List.length jobs) ~size:192
+
   (* ---------------------------------------------------------------- verify
      e(A, B) = ab + e(sum_k w_k [L_k(tau)/gamma]_1, gamma) + e(C, delta), GT written additively as Curve.G has it.  The sum
      runs over the public coefficients; domains must agree (G.dot). *)

@@ -343,6 +343,32 @@ let zk_pinocchio_verify_folded_compressed =
   fn "zk_pinocchio_verify_folded_compressed"
     (uint64_t @-> ocaml_bytes @-> ocaml_bytes @-> ocaml_bytes @-> uint32_t @-> ptr int @-> ptr int32_t @-> returning int)
 
+(* A batch of witnesses proved in one call, every proof out as its compressed wire bytes (include/zkmi355x.h): 192 bytes per Groth16 proof, 480 per
+   Pinocchio proof -- the strings of the reference's proof record (groth16.ml:110-114, pinocchio.ml:195-208) back to back, what the *_compressed
+   verifiers above take.  sols: the witnesses back to back, or null: the resident witness for every proof.  status: one code per proof. *)
+let zk_groth16_prove_many_compressed =
+  fn "zk_groth16_prove_many_compressed"
+    (uint64_t @-> ptr char @-> ocaml_bytes @-> uint32_t @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
+
+let zk_pinocchio_prove_many_compressed =
+  fn "zk_pinocchio_prove_many_compressed"
+    (uint64_t @-> ptr char @-> ocaml_bytes @-> uint32_t @-> uint32_t @-> ocaml_bytes @-> ptr int32_t @-> returning int)
+
+(* the conversion launch of the two calls above on points the caller chooses (the test suite's hook) *)
+let zk_selftest_proof_wire = fn "zk_selftest_proof_wire" (int @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> returning int)
+
+(* The body both protocols' prove_many_compressed share: `count` proofs of the resident witness, randomness back to back in `rnd`, `size` wire bytes per
+   proof.  The first proof that failed raises what the single call raises (check); otherwise the proofs' wire bytes, one string each. *)
+let prove_many_compressed stub (h : Unsigned.UInt64.t) ~(rnd : bytes) ~(count : int) ~(size : int) : bytes list =
+  if count = 0 then []
+  else begin
+    let out = Bytes.create (size * count) in
+    let status = CArray.make int32_t ~initial:0l count in
+    check (stub h null_bytes (bytes_start rnd) (u32 count) (u32 0) (bytes_start out) (CArray.start status));
+    CArray.iter (fun st -> check (Int32.to_int st)) status;
+    List.init count (fun i -> Bytes.sub out (size * i) size)
+  end
+
 let vk_free (h : Unsigned.UInt64.t) = ignore (zk_vk_free h)
 
 let groth16_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =

@@ -275,6 +275,16 @@ module Make (C : Curve.S) = struct
     let g1 off = G1.of_bytes_exn (Bytes.sub out off 96) and g2 off = G2.of_bytes_exn (Bytes.sub out off 192) in
     { vv = g1 0; ww = g2 96; yy = g1 288; h = g1 384; vavv = g1 480; waww = g2 576; yayy = g1 768; bvwy = g1 864 }
 
+  (* A batch of proofs of one witness in ONE library call, each as its 480 wire bytes (zk_pinocchio_prove_many_compressed): the eight strings of the
+     proof record (pinocchio.ml:195-208) back to back, what Resident.verify_many_compressed takes.  jobs: the (dv, dw, dy) of each proof in the order
+     the reference draws them (:428-430); all zero is NonZK.  Nothing is decoded or compressed on the host. *)
+  let prove_many_with (qap : qap) (k : pkey) (sol : Fr.t Var.Map.t) (jobs : (Fr.t * Fr.t * Fr.t) list) : bytes list =
+    let handle = handle_of qap k in
+    if not (Var.Set.equal (Var.Map.domain sol) (Var.Map.domain qap.QAP.v)) then assert false;
+    Mi355x.(check (zk_pinocchio_set_witness handle (bytes_start (fr_bytes (values sol)))));
+    let rnd = fr_bytes (List.concat_map (fun (dv, dw, dy) -> [ dv; dw; dy ]) jobs) in
+    Mi355x.prove_many_compressed Mi355x.zk_pinocchio_prove_many_compressed handle ~rnd ~count:(List.length jobs) ~size:480
+
   let verify_with (ios : Fr.t Var.Map.t) (vk : vkey) (p : proof) : bool =
     (* the reference asserts equal domains before each of its three sums (pinocchio.ml:372,381,390) *)
     assert (Var.Set.equal (Var.Map.domain ios) (Var.Map.domain vk.vv_io));
@@ -429,6 +439,7 @@ module Make (C : Curve.S) = struct
 
     let keygen = keygen
     let prove _rng qap pkey sol = prove_with qap pkey sol Fr.zero Fr.zero Fr.zero
+    let prove_many _rng qap pkey sol count = prove_many_with qap pkey sol (List.init count (fun _ -> (Fr.zero, Fr.zero, Fr.zero)))
     let verify input_output vkey proof = verify_with input_output vkey proof
     let verify_many jobs vkey = verify_many_with jobs vkey
   end
@@ -448,6 +459,17 @@ module Make (C : Curve.S) = struct
       let dw = Fr.gen rng in
       let dy = Fr.gen rng in
       prove_with qap pkey sol dv dw dy
+
+    (* `count` proofs of one witness, dv, dw, dy drawn per proof in proof order; the proofs' wire bytes *)
+    let prove_many rng qap pkey sol count =
+      let draw _ =
+        let dv = Fr.gen rng in
+        let dw = Fr.gen rng in
+        let dy = Fr.gen rng in
+        (dv, dw, dy)
+      in
+      let rec jobs i acc = if i = count then List.rev acc else jobs (i + 1) (draw i :: acc) in
+      prove_many_with qap pkey sol (jobs 0 [])
 
     let verify = NonZK.verify
     let verify_many = NonZK.verify_many

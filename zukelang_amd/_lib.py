@@ -33,6 +33,7 @@ EXPORTS = [
     "zk_bench_field_mul", "zk_selftest_fp", "zk_selftest_fp_paired", "zk_selftest_fp2_lanewise", "zk_selftest_sqrt", "zk_selftest_fp12", "zk_selftest_subgroup", "zk_selftest_groth16_fold", "zk_selftest_pinocchio_fold", "zk_selftest_group", "zk_selftest_point_decompress",
     "zk_selftest_fr", "zk_selftest_fr29",
     "zk_groth16_pk_upload_compressed", "zk_pinocchio_pk_upload_compressed", "zk_bases_upload_compressed", "zk_groth16_pool_points_compressed", "zk_pinocchio_pool_points_compressed",
+    "zk_groth16_prove_many_compressed", "zk_pinocchio_prove_many_compressed", "zk_selftest_proof_wire",
 ]
 
 
@@ -119,6 +120,12 @@ KEY_WIRE_PROTOTYPES = {
     "zk_groth16_pool_points_compressed": [C.c_uint64, C.c_int, _P8, C.c_size_t, _PSZ],
     "zk_pinocchio_pool_points_compressed": [C.c_uint64, C.c_int, _P8, C.c_size_t, _PSZ],
 }
+# a batch of proofs in one call, out as wire bytes, and the conversion's hook (tests/test_prove_many_surface.py holds them to the header)
+PROVE_MANY_PROTOTYPES = {
+    "zk_groth16_prove_many_compressed": [C.c_uint64, _P8, _P8, C.c_uint32, C.c_uint32, _P8, _PI32],
+    "zk_pinocchio_prove_many_compressed": [C.c_uint64, _P8, _P8, C.c_uint32, C.c_uint32, _P8, _PI32],
+    "zk_selftest_proof_wire": [C.c_int, _P8, _P8, C.c_size_t, _P8],
+}
 KEY_FORMS = {"tau_powers": 0, "lagrange": 1}         # ZK_KEY_FORM_TAU_POWERS, ZK_KEY_FORM_LAGRANGE
 
 _lib = None
@@ -134,7 +141,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

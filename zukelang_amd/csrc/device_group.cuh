@@ -197,6 +197,8 @@ template <class P> struct DeviceGroup {
         }
         return rc;
     }
+    // the sums of the proof that last finished on `slot`, P::G1 then P::G2 raw XYZZ points on the list's first device: what proof_points_to_bytes_dev read
+    const void* sums(uint32_t slot) const { return slots[slot]->sum.p; }
     int prove_wait(uint32_t slot, uint8_t* proof) {
         if (slot >= P::MAX_SLOTS || !slots[slot]) ZK_FAIL(ZK_ERR_ARG, P::WAIT_NEVER_USED);
         GroupSlot& gs = *slots[slot];

@@ -15,6 +15,7 @@
 #include "ec.cuh"
 #include "groth16_key.cuh"
 #include "handle_table.h"
+#include "prove_many.cuh"
 
 #include <memory>
 #include <stdlib.h>
@@ -396,6 +397,28 @@ int groth16_prove_finish(Slot& sl) {
     sl.busy = false;
     return status_of_flags(sl.host + 384, "an Fr input (witness value, or a scalar of a caller-owned vector) is >= r");
 }
+// zk_groth16_prove_many_compressed on a key held whole on one device (prove_many.cuh): proof i in its raw form on its slot -- witness, r and s through the
+// slot's pinned staging memory, under ZK_GRAPH the slot's raw graph -- then the slot's sums A | C | B into the proof's row, on the slot's stream and
+// outside the graph, with the slot's event recorded again behind the copy.
+struct Groth16Many {
+    static constexpr uint32_t ROW_BYTES = ZK_GROTH16_PARTIAL_BYTES, WIRE_BYTES = 192;
+    Groth16Key& k;
+    const uint8_t *sols, *rs;
+    static ProofWire wire1() { return groth16_wire_g1(); }
+    static ProofWire wire2() { return groth16_wire_g2(); }
+    int enqueue(uint32_t i, uint32_t slot, void* d_row) {
+        Slot* sl;
+        ZKCHK(groth16_slot_get(k, slot, &sl));
+        ZKCHK(prove_enqueue(k, *sl, sols ? sols + 32 * (size_t)k.m * i : nullptr, rs + 64 * (size_t)i, rs + 64 * (size_t)i + 32, true));
+        const hipError_t e1 = hipMemcpyAsync(d_row, sl->results.p, ROW_BYTES, hipMemcpyDeviceToDevice, sl->s0);
+        const hipError_t e2 = hipEventRecord(sl->done, sl->s0);
+        if (e1 != hipSuccess || e2 != hipSuccess) (void)groth16_prove_finish(*sl);          // the proof is in flight: it does not stay so behind the caller's back
+        HIPCHK(e1);
+        HIPCHK(e2);
+        return ZK_OK;
+    }
+    int finish(uint32_t slot) { return groth16_prove_finish(*k.slots[slot]); }
+};
 
 }  // namespace zk
 
@@ -638,6 +661,28 @@ int zk_groth16_prove_wait(uint64_t handle, uint32_t slot, uint8_t proof[384]) {
 int zk_groth16_prove(uint64_t handle, const uint8_t* sol, const uint8_t r[32], const uint8_t s[32], uint8_t proof[384]) {
     ZKCHK(zk_groth16_prove_async(handle, sol, r, s, 0));
     return zk_groth16_prove_wait(handle, 0, proof);
+}
+// A batch of proofs in one call, out as wire bytes (include/zkmi355x.h; prove_many.cuh holds the loop)
+int zk_groth16_prove_many_compressed(uint64_t handle, const uint8_t* sols, const uint8_t* rs, uint32_t count, uint32_t in_flight, uint8_t* proofs, int32_t* status) {
+    ZKCHK(prove_many_check_args(rs, proofs, status, count, in_flight, "zk_groth16_prove_many_compressed: null rs, proofs or status"));
+    if (!count) return ZK_OK;
+    GroupKey* g = group_lookup(handle);
+    if (!g && !g_keys.find(handle)) ZKCHK(ensure_init());          // without a device no handle exists: say that, not that this one is unknown
+    if (g) return group_prove_many(*g, sols, rs, count, proofs, status);
+    Groth16Key* kp;
+    ZKCHK(key_lookup(handle, &kp));
+    Groth16Key& k = *kp;
+    if (k.world != 1) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_prove_many_compressed: the key is a shard (partial sums only); use prove_partial + combine");
+    if (!sols && !k.have_witness) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_prove_many_compressed: no witness: pass sols or call zk_groth16_set_witness first");
+    for (uint32_t i = 0; i < MAX_SLOTS; i++)
+        if (k.slots[i] && k.slots[i]->busy) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_prove_many_compressed: a proof is in flight on this key: call the matching _wait first");
+    in_flight = prove_many_in_flight(in_flight, count);
+    for (uint32_t i = 0; i < in_flight; i++) {
+        Slot* sl;
+        ZKCHK(groth16_slot_get(k, i, &sl));
+    }
+    Groth16Many many{k, sols, rs};
+    return prove_many_run(many, count, in_flight, proofs, status, ctx().stream);
 }
 int zk_groth16_set_witness(uint64_t handle, const uint8_t* sol) {
     if (GroupKey* g = group_lookup(handle)) return group_set_witness(*g, sol);

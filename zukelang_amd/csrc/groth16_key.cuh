@@ -91,6 +91,11 @@ int group_pool_points(GroupKey& g, int group, uint8_t* out, size_t capacity_poin
 int group_pool_layout(GroupKey& g, uint64_t* p1, uint64_t* p2);
 int group_qap_eval(GroupKey& g, const uint8_t* sol, uint8_t* v_out, uint8_t* w_out, uint8_t* h_out);
 int group_lagrange_pool_sizes(GroupKey& g, uint64_t* g1_points, uint64_t* g2_points);
+// zk_groth16_prove_many_compressed on a multi-device key: proof by proof through the group's slot 0, the sums the first device added up as the proof's row
+int group_prove_many(GroupKey& g, const uint8_t* sols, const uint8_t* rs, uint32_t count, uint8_t* proofs, int32_t* status);
+// where the sums of a proof (A | C | B, the slot's results) go in its wire record A 48 | B 96 | C 48 (groth16.ml:110-114)
+static inline ProofWire groth16_wire_g1() { return {2, ZK_GROTH16_PARTIAL_BYTES, 0, 192, {0, 144, 0, 0, 0, 0}}; }
+static inline ProofWire groth16_wire_g2() { return {1, ZK_GROTH16_PARTIAL_BYTES, 384, 192, {48, 0, 0, 0, 0, 0}}; }
 int single_qap_eval(Groth16Key& k, const uint8_t* sol, uint8_t* v_out, uint8_t* w_out, uint8_t* h_out);
 int single_pool_points(Groth16Key& k, int group, uint8_t* out, size_t capacity_points, size_t* count, bool wire = false);
 

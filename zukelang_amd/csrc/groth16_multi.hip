@@ -11,6 +11,7 @@
 #include "device_group.cuh"
 #include "groth16_key.cuh"
 #include "handle_table.h"
+#include "prove_many.cuh"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -163,6 +164,35 @@ int group_prove_async(GroupKey& g, const uint8_t* sol, const uint8_t* r, const u
         });
 }
 int group_prove_wait(GroupKey& g, uint32_t slot, uint8_t proof[384]) { return g.prove_wait(slot, proof); }
+// zk_groth16_prove_many_compressed on a multi-device key (prove_many.cuh with one proof in flight): each proof runs the per-proof path above on slot 0
+// to its end; the sums the first device added up for it are the proof's row, and the batch's conversion and copy are those of the one-device key.
+struct GroupMany {
+    static constexpr uint32_t ROW_BYTES = ZK_GROTH16_PARTIAL_BYTES, WIRE_BYTES = 192;
+    GroupKey& g;
+    const uint8_t *sols, *rs;
+    int last = ZK_OK;
+    static ProofWire wire1() { return groth16_wire_g1(); }
+    static ProofWire wire2() { return groth16_wire_g2(); }
+    int enqueue(uint32_t i, uint32_t, void* d_row) {
+        uint8_t proof[384];
+        ZKCHK(group_prove_async(g, sols ? sols + 32 * (size_t)g.m * i : nullptr, rs + 64 * (size_t)i, rs + 64 * (size_t)i + 32, 0));
+        last = g.prove_wait(0, proof);
+        if (!prove_status_is_per_proof(last)) return last;
+        DeviceScope ds(0);
+        hipStream_t cs = ctx().stream2;          // the stream the sums were written on
+        HIPCHK(hipMemcpyAsync(d_row, g.sums(0), ROW_BYTES, hipMemcpyDeviceToDevice, cs));
+        HIPCHK(hipStreamSynchronize(cs));
+        return ZK_OK;
+    }
+    int finish(uint32_t) { return last; }
+};
+int group_prove_many(GroupKey& g, const uint8_t* sols, const uint8_t* rs, uint32_t count, uint8_t* proofs, int32_t* status) {
+    if (!sols && !g.sub[0]->have_witness) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_prove_many_compressed: no witness: pass sols or call zk_groth16_set_witness first");
+    ZKCHK(g.check_idle("zk_groth16_prove_many_compressed: a proof is in flight on this key: call the matching _wait first"));
+    GroupMany many{g, sols, rs};
+    DeviceScope ds(0);
+    return prove_many_run(many, count, 1, proofs, status, ctx().stream2);
+}
 
 int group_lagrange_pool_sizes(GroupKey& g, uint64_t* g1_points, uint64_t* g2_points) {
     if (g1_points) *g1_points = 3 + (uint64_t)g.n + (g.n - 1) + g.n_mid;

@@ -183,6 +183,16 @@ int points_selftest_subgroup(Curve curve, SubgroupTest test, const uint8_t* poin
 int points_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, hipStream_t s);
 int points_selftest_sqrt(int field, const uint8_t* a, uint64_t n, uint8_t* root, uint8_t* is_square, hipStream_t s);          // zk_selftest_sqrt
 int points_selftest_decompress(Curve curve, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* verdict, hipStream_t s);         // zk_selftest_point_decompress
+// ---- proofs out as wire bytes (zk_*_prove_many_compressed; to_compressed_bytes, curve.ml:213-219, over a whole batch): `count` proofs lie as rows of XYZZ
+// sums on the device, row j at d_rows + row_stride j, the `per` points of one group back to back from row_first on (the layout the raw form of a proof
+// leaves in its slot).  One lane per point of the batch: one inversion, x out of Montgomery form, the sign bit, C0 00 .. 00 for the identity, written to
+// d_wire + wire_stride j + off[q].  Strides and offsets are multiples of 16.  Enqueues only; timer family prove_to_wire.
+struct ProofWire {
+    uint32_t per, row_stride, row_first, wire_stride;
+    uint32_t off[6];
+};
+int proofs_to_wire_dev(Curve curve, const void* d_rows, uint64_t count, const ProofWire& w, void* d_wire, hipStream_t s);
+int points_selftest_proof_wire(Curve curve, const uint8_t* affine, const uint8_t* z, uint64_t n, uint8_t* out, hipStream_t s);          // zk_selftest_proof_wire
 // ---- zk_selftest_group: every form of the group law on bare operands, one kernel per translation unit that builds the form (group_selftest.cuh says
 // why and what the buffers hold).  The numbers are the `form` argument of the C-ABI.
 enum GroupForm {

@@ -456,6 +456,14 @@ int zk_selftest_point_decompress(int group, const uint8_t* in, size_t n, uint8_t
     DeviceScope ds(0);
     return points_selftest_decompress(group ? CURVE_G2 : CURVE_G1, in, n, out, verdict, ctx().stream);
 }
+// the conversion launch of zk_*_prove_many_compressed (k_proofs_to_wire of msm_points.hip) on XYZZ points the caller chooses
+int zk_selftest_proof_wire(int group, const uint8_t* affine, const uint8_t* z, size_t n, uint8_t* out) {
+    if (!affine || !z || !out || !n || n >= ((size_t)1 << 24) || (group != 0 && group != 1))
+        ZK_FAIL(ZK_ERR_ARG, "zk_selftest_proof_wire: null argument, no points, or a group other than 0 (G1) / 1 (G2)");
+    ZKCHK(ensure_init());
+    DeviceScope ds(0);
+    return points_selftest_proof_wire(group ? CURVE_G2 : CURVE_G1, affine, z, n, out, ctx().stream);
+}
 int zk_g1_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G1, scalars, n, out); }
 int zk_g2_of_fr(const uint8_t* scalars, size_t n, uint8_t* out) { return of_fr_api(CURVE_G2, scalars, n, out); }
 int zk_g1_powers(uint32_t d, const uint8_t s[32], uint8_t* out) { return powers_api(CURVE_G1, d, s, out); }

@@ -309,6 +309,68 @@ template <class F> __global__ __launch_bounds__(128) void k_decompress_verdict(u
     verdict[i] = point_decompress(out, xb);
     aff_store<F>(dense + (size_t)B * i, out);
 }
+// The provers' form (zk_*_prove_many_compressed; ProofWire, msm.cuh): the XYZZ sums of a whole batch of proofs -> the proofs' wire records, one lane per
+// point.  xyzz_to_aff without its early exit: the inversion is the lockstep one (fp_inv.cuh), 0 for 0, so a lane that holds the identity runs the same
+// instructions as its neighbours and ends with x = y = 0; what it writes is chosen at the end.  The point's slot in the record comes out of the
+// argument struct by a chain of selects over constant indices, the lane's bytes are written at constant indices: nothing is indexed at run time.
+template <class F> FF_INLINE Aff<F> xyzz_to_aff_lockstep(const Xyzz<F>& p) {
+    const auto i = fe_inv(fe_mul(p.zz, p.zzz));
+    const auto izz = fe_mul(i, p.zzz);
+    const auto izzz = fe_mul(i, p.zz);
+    return {fe_mul(p.x, izz), fe_mul(p.y, izzz)};
+}
+template <class F> __global__ __launch_bounds__(128) void k_proofs_to_wire(uint8_t* __restrict__ out, const uint8_t* __restrict__ rows, uint64_t n, ProofWire w) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int CB = FieldOps<F>::WORDS * 4, XB = FieldOps<F>::WORDS * 16;
+    const uint64_t item = i / w.per;
+    const uint32_t q = (uint32_t)(i - item * w.per);
+    uint32_t off = w.off[0];
+#pragma unroll
+    for (int k = 1; k < 6; k++) off = q == (uint32_t)k ? w.off[k] : off;
+    const Xyzz<F> p = xyzz_load<F>(rows + (size_t)w.row_stride * item + w.row_first + (size_t)XB * q);
+    const bool inf = xyzz_is_inf(p);
+    const Aff<F> a = xyzz_to_aff_lockstep(p);
+    alignas(16) uint8_t xb[CB];
+    wire_encode(xb, a);
+    xb[0] |= wire_sign(a) ? 0xA0 : 0x80;
+    uint4* dst = reinterpret_cast<uint4*>(out + (size_t)w.wire_stride * item + off);
+#pragma unroll
+    for (int k = 0; k < CB / 16; k++) {
+        const uint4 v = reinterpret_cast<const uint4*>(xb)[k];
+        dst[k] = inf ? make_uint4(k == 0 ? 0xC0u : 0u, 0u, 0u, 0u) : v;
+    }
+}
+// zk_selftest_proof_wire: (x, y) in the ABI's uncompressed bytes and a scalar z -> the XYZZ point (x z^2, y z^3, z^2, z^3) as a one-point row of
+// k_proofs_to_wire; the all-zero pair -> the identity (zz = 0).  bit 0 of *flag: a coordinate >= p, z = 0 or z >= r.
+FF_INLINE bool lift_xy(Aff<Fp>& a, const uint8_t* p) {
+    const FpWords x = fpw_from_be(p), y = fpw_from_be(p + 48);
+    a = {fp_to_mont(x), fp_to_mont(y)};
+    return fpw_canonical(x) && fpw_canonical(y);
+}
+FF_INLINE bool lift_xy(Aff<Fp2>& a, const uint8_t* p) {
+    const FpWords x1 = fpw_from_be(p), x0 = fpw_from_be(p + 48), y1 = fpw_from_be(p + 96), y0 = fpw_from_be(p + 144);
+    a = {{fp_to_mont(x0), fp_to_mont(x1)}, {fp_to_mont(y0), fp_to_mont(y1)}};
+    return fpw_canonical(x0) && fpw_canonical(x1) && fpw_canonical(y0) && fpw_canonical(y1);
+}
+FF_INLINE Xyzz<Fp> lift_scale(const Aff<Fp>& a, const FpB<2>& zz, const FpB<2>& zzz) { return {fe_mul(a.x, zz), fe_mul(a.y, zzz), zz, zzz}; }
+FF_INLINE Xyzz<Fp2> lift_scale(const Aff<Fp2>& a, const FpB<2>& zz, const FpB<2>& zzz) {
+    return {{fe_mul(a.x.c0, zz), fe_mul(a.x.c1, zz)}, {fe_mul(a.y.c0, zzz), fe_mul(a.y.c1, zzz)}, {zz, fp_zero()}, {zzz, fp_zero()}};
+}
+template <class F> __global__ __launch_bounds__(128) void k_selftest_lift(uint8_t* __restrict__ xyzz, const uint8_t* __restrict__ aff, const uint32_t* __restrict__ z, uint64_t n, int* flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int B = FieldOps<F>::WORDS * 8;
+    const Fr zr = fe_load<FrParams>(z + 8 * i);
+    FpWords zw;
+#pragma unroll
+    for (int k = 0; k < 12; k++) zw.w[k] = k < 8 ? z[8 * i + k] : 0u;
+    Aff<F> a;
+    const bool ok = lift_xy(a, aff + (size_t)B * i);
+    if (!ok || !fe_is_canonical(zr) || fe_is_zero(zr)) atomicOr(flag, 1);
+    const FpB<2> zf = fp_to_mont(zw), zz = fe_mul(zf, zf), zzz = fe_mul(zz, zf);
+    xyzz_store<F>(xyzz + (size_t)2 * B * i, aff_is_inf(a) ? xyzz_inf<F>() : lift_scale(a, zz, zzz));
+}
 
 // zk_selftest_sqrt: the square roots and the sign rule above on bare field elements, one lane per element, as k_decompress_* call them.
 // field 0: 48 B big-endian each; field 1: 96 B each, imaginary part | real part (the order of a G2 coordinate on the wire).  root = the root that
@@ -790,6 +852,41 @@ int points_affine_to_wire(Curve curve, const void* d_aff, uint64_t n, uint8_t* h
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(host_out, dw.p, cb * n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return ZK_OK;
+}
+// the rows of XYZZ sums of `count` proofs (device) -> one group's points in the proofs' wire records (device): msm.cuh, ProofWire
+int proofs_to_wire_dev(Curve curve, const void* d_rows, uint64_t count, const ProofWire& w, void* d_wire, hipStream_t s) {
+    if (!count || !w.per) return ZK_OK;
+    if (w.per > 6) ZK_FAIL(ZK_ERR_ARG, "proofs_to_wire_dev: at most 6 points of a group per proof");
+    const uint64_t n = count * w.per;
+    ScopedTimer t("prove_to_wire", s);
+    for_curve(curve, [&](auto f) { hipLaunchKernelGGL(k_proofs_to_wire<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, (uint8_t*)d_wire, (const uint8_t*)d_rows, n, w); });
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// zk_selftest_proof_wire: n pairs (affine point, z) (host) -> n XYZZ points on the device -> k_proofs_to_wire as a batch of n one-point proofs -> wire bytes (host)
+int points_selftest_proof_wire(Curve curve, const uint8_t* affine, const uint8_t* z, uint64_t n, uint8_t* out, hipStream_t s) {
+    const size_t ub = aff_bytes(curve), cb = ub / 2, xb = xyzz_bytes(curve);
+    DevBuf din, dz, rows, dw, flag;
+    ZKCHK(din.alloc(ub * n));
+    ZKCHK(dz.alloc(32 * n));
+    ZKCHK(rows.alloc(xb * n));
+    ZKCHK(dw.alloc(cb * n));
+    ZKCHK(flag.alloc(4));
+    HIPCHK(hipMemsetAsync(flag.p, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(din.p, affine, ub * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dz.p, z, 32 * n, hipMemcpyHostToDevice, s));
+    for_curve(curve, [&](auto f) {
+        hipLaunchKernelGGL(k_selftest_lift<FIELD_OF(f)>, grid_for(n, 128), dim3(128), 0, s, rows.as<uint8_t>(), (const uint8_t*)din.as<uint8_t>(), (const uint32_t*)dz.as<uint32_t>(), n, flag.as<int>());
+    });
+    HIPCHK(hipGetLastError());
+    const ProofWire w{1, (uint32_t)xb, 0, (uint32_t)cb, {0, 0, 0, 0, 0, 0}};
+    ZKCHK(proofs_to_wire_dev(curve, rows.p, n, w, dw.p, s));
+    int h = 0;
+    HIPCHK(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, dw.p, cb * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h) ZK_FAIL(ZK_ERR_ARG, "zk_selftest_proof_wire: a coordinate is >= p, or a z is 0 or >= r");
     return ZK_OK;
 }
 

@@ -29,6 +29,7 @@
 #include "device_group.cuh"
 #include "ec.cuh"
 #include "handle_table.h"
+#include "prove_many.cuh"
 
 #include <memory>
 #include <random>
@@ -788,6 +789,62 @@ static int pin_group_derive(PinGroup& g) {
     return ZK_OK;
 }
 
+// ================================================================== zk_pinocchio_prove_many_compressed (prove_many.cuh holds the loop both protocols share)
+// A proof's row is its slot's results: the six G1 sums in pool order (vv, yy, vavv, yayy, bvwy, h), then ww, waww.  The record is the eight points in
+// declaration order (pinocchio.ml:195-208): vv 0 | ww 48 | yy 144 | h 192 | vavv 240 | waww 288 | yayy 384 | bvwy 432.
+static constexpr uint32_t PIN_ROW_BYTES = PIN_G1 * 192 + PIN_G2 * 384, PIN_WIRE_BYTES = 480;
+static inline ProofWire pin_wire_g1() { return {PIN_G1, PIN_ROW_BYTES, 0, PIN_WIRE_BYTES, {0, 144, 240, 384, 432, 192}}; }
+static inline ProofWire pin_wire_g2() { return {PIN_G2, PIN_ROW_BYTES, PIN_G1 * 192, PIN_WIRE_BYTES, {48, 288, 0, 0, 0, 0}}; }
+// a key held whole on one device: proof i in its raw form on its slot (one stream: a raw proof never forks), the sums into the row behind it
+struct PinMany {
+    static constexpr uint32_t ROW_BYTES = PIN_ROW_BYTES, WIRE_BYTES = PIN_WIRE_BYTES;
+    PinKey& k;
+    const uint8_t *sols, *blind;
+    static ProofWire wire1() { return pin_wire_g1(); }
+    static ProofWire wire2() { return pin_wire_g2(); }
+    int enqueue(uint32_t i, uint32_t slot, void* d_row) {
+        PinSlot* slp;
+        ZKCHK(pin_slot_get(k, slot, &slp));
+        PinSlot& sl = *slp;
+        if (sl.busy) ZK_FAIL(ZK_ERR_ARG, "slot still has a proof in flight: call zk_pinocchio_prove_wait first");
+        const uint8_t* d = blind + 96 * (size_t)i;
+        ZKCHK(pin_scalars_enqueue(k, sl, sols ? sols + 32 * (size_t)k.m * i : nullptr, d, d + 32, d + 64, false));
+        ZKCHK(pin_msms_enqueue(k, sl, true));
+        HIPCHK(hipMemcpyAsync(d_row, sl.results.p, ROW_BYTES, hipMemcpyDeviceToDevice, sl.st));
+        HIPCHK(hipEventRecord(sl.done, sl.st));
+        sl.busy = true;
+        return ZK_OK;
+    }
+    int finish(uint32_t slot) {
+        PinSlot& sl = *k.slots[slot];
+        HIPCHK(hipEventSynchronize(sl.done));
+        sl.busy = false;
+        return status_of_flags(sl.host + 960);
+    }
+};
+// a multi-device key: proof by proof through the group's slot 0, the sums the first device added up as the proof's row (groth16_multi.hip: GroupMany)
+struct PinGroupMany {
+    static constexpr uint32_t ROW_BYTES = PIN_ROW_BYTES, WIRE_BYTES = PIN_WIRE_BYTES;
+    PinGroup& g;
+    const uint8_t *sols, *blind;
+    int last = ZK_OK;
+    static ProofWire wire1() { return pin_wire_g1(); }
+    static ProofWire wire2() { return pin_wire_g2(); }
+    int enqueue(uint32_t i, uint32_t, void* d_row) {
+        uint8_t proof[960];
+        const uint8_t* d = blind + 96 * (size_t)i;
+        ZKCHK(pin_group_prove_async(g, sols ? sols + 32 * (size_t)g.m * i : nullptr, d, d + 32, d + 64, 0));
+        last = g.prove_wait(0, proof);
+        if (!prove_status_is_per_proof(last)) return last;
+        DeviceScope ds(0);
+        hipStream_t cs = ctx().stream2;          // the stream the sums were written on
+        HIPCHK(hipMemcpyAsync(d_row, g.sums(0), ROW_BYTES, hipMemcpyDeviceToDevice, cs));
+        HIPCHK(hipStreamSynchronize(cs));
+        return ZK_OK;
+    }
+    int finish(uint32_t) { return last; }
+};
+
 }  // namespace zk
 
 using namespace zk;
@@ -982,6 +1039,32 @@ int zk_pinocchio_prove_wait(uint64_t handle, uint32_t slot, uint8_t proof[960]) 
     ZKCHK(status_of_flags(sl.host + 960));
     memcpy(proof, sl.host, 960);
     return ZK_OK;
+}
+// A batch of proofs in one call, out as wire bytes (include/zkmi355x.h)
+int zk_pinocchio_prove_many_compressed(uint64_t handle, const uint8_t* sols, const uint8_t* blind, uint32_t count, uint32_t in_flight, uint8_t* proofs, int32_t* status) {
+    ZKCHK(prove_many_check_args(blind, proofs, status, count, in_flight, "zk_pinocchio_prove_many_compressed: null blind, proofs or status"));
+    if (!count) return ZK_OK;
+    PinGroup* g = g_pin_groups.find(handle);
+    if (!g && !g_pin.find(handle)) ZKCHK(ensure_init());          // without a device no handle exists: say that, not that this one is unknown
+    if (g) {
+        if (!sols && !g->sub[0]->have_witness) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_prove_many_compressed: no witness: pass sols or call zk_pinocchio_set_witness first");
+        ZKCHK(g->check_idle("zk_pinocchio_prove_many_compressed: a proof is in flight on this key: call zk_pinocchio_prove_wait first"));
+        PinGroupMany many{*g, sols, blind};
+        DeviceScope ds(0);
+        return prove_many_run(many, count, 1, proofs, status, ctx().stream2);
+    }
+    PinKey* kp;
+    ZKCHK(pin_lookup(handle, &kp));
+    PinKey& k = *kp;
+    if (!sols && !k.have_witness) ZK_FAIL(ZK_ERR_ARG, "zk_pinocchio_prove_many_compressed: no witness: pass sols or call zk_pinocchio_set_witness first");
+    ZKCHK(pin_check_idle(k, "zk_pinocchio_prove_many_compressed: a proof is in flight on this key: call zk_pinocchio_prove_wait first"));
+    in_flight = prove_many_in_flight(in_flight, count);
+    for (uint32_t i = 0; i < in_flight; i++) {
+        PinSlot* sl;
+        ZKCHK(pin_slot_get(k, i, &sl));
+    }
+    PinMany many{k, sols, blind};
+    return prove_many_run(many, count, in_flight, proofs, status, ctx().stream);
 }
 int zk_pinocchio_prove(uint64_t handle, const uint8_t* sol, const uint8_t dv[32], const uint8_t dw[32], const uint8_t dy[32],
                        uint8_t proof[960]) {

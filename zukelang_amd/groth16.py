@@ -319,6 +319,38 @@ def shard_bounds(size, rank, world, heavy=0):
     return cut(rank), cut(rank + 1)
 
 
+def _many_witnesses(to_bytes, sols, m):
+    """prove_many's witnesses -> (their bytes back to back, count), or (None, count) for `count` proofs of the resident witness."""
+    if isinstance(sols, int):
+        return None, sols
+    if isinstance(sols, np.ndarray) and sols.ndim == 2 and sols.dtype == np.uint8:          # one row of 32 m bytes per witness: handed over as it lies
+        if sols.shape[1] != 32 * m:
+            raise AssertionError("Variable not found")          # var.ml:75-77
+        return np.ascontiguousarray(sols).reshape(-1), sols.shape[0]
+    ws = [to_bytes(sol) for sol in sols]
+    if any(len(w) != 32 * m for w in ws):
+        raise AssertionError("Variable not found")          # var.ml:75-77
+    return (np.concatenate(ws) if ws else np.zeros(0, dtype=np.uint8)), len(ws)
+
+
+def _prove_many(fn, handle, ws, rnd, count, in_flight, size, return_status):
+    """The call both protocols' prove_many make: `count` proofs of `size` wire bytes each and the code the single call would return for each."""
+    out = np.zeros(max(1, size * count), dtype=np.uint8)
+    status = np.zeros(max(1, count), dtype=np.int32)
+    rnd = np.ascontiguousarray(rnd, dtype=np.uint8).reshape(-1)
+    _lib.check(fn(handle, _p(ws) if ws is not None and count else None, _p(rnd) if count else _p(out), C.c_uint32(count), C.c_uint32(in_flight), _p(out),
+                  status.ctypes.data_as(C.POINTER(C.c_int32))))
+    proofs = [bytes(out[size * i:size * i + size]) for i in range(count)]
+    codes = [int(x) for x in status[:count]]
+    if return_status:
+        return proofs, codes
+    for rc in codes:
+        if rc == ZK_ERR_REMAINDER:
+            raise AssertionError("Polynomial.is_zero rem")      # QAP.ml:134
+        _lib.check(rc)
+    return proofs
+
+
 class Groth16:
     @staticmethod
     def keygen(rng, circuit: R1CS, lagrange=False):
@@ -551,6 +583,21 @@ class Groth16:
         _lib.check(rc)
         b = bytes(out)
         return Proof(b[:96], b[96:288], b[288:])
+
+    def prove_many(self, rng_or_rs, sols, in_flight=0, return_status=False):
+        """A batch of proofs in ONE call, each as its 192 wire bytes a | b | c (zk_groth16_prove_many_compressed): what wire.groth16_proof_json_of_bytes
+        writes as the proof record and ResidentVKey.verify_many(..., compressed=True) takes.  sols: the witnesses, or an int: that many proofs of the
+        witness set_witness made resident.  rng_or_rs: a callable, drawn r then s per proof in proof order (groth16.ml:124-125), or the (r, s) pairs.
+        in_flight: proofs kept in flight, 1..15 (0: the library's default).  The first failed proof raises what `prove` raises; with return_status
+        nothing raises for a proof, and (proofs, statuses) comes back -- a failed proof's bytes are zeros."""
+        if self.world != 1:
+            raise ValueError("prove_many: the key is a shard; shards produce partial sums only")
+        ws, count = _many_witnesses(self._sol_bytes, sols, self.circuit.m)
+        rs = [(rng_or_rs() % FR_MODULUS, rng_or_rs() % FR_MODULUS) for _ in range(count)] if callable(rng_or_rs) else [tuple(x) for x in rng_or_rs]
+        if len(rs) != count or any(len(x) != 2 for x in rs):
+            raise ValueError("prove_many: need one (r, s) pair per proof")
+        rnd = fr_bytes([x for pair in rs for x in pair])
+        return _prove_many(_lib.lib().zk_groth16_prove_many_compressed, self.handle, ws, rnd, count, in_flight, 192, return_status)
 
     def reserve_slots(self, count):
         """Allocate the scratch and streams of `count` proof slots now (otherwise at first use)."""

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from .curve import G1, G2
-from .groth16 import _csr, _lagrange_at, _p, columns_at, ResidentVKey, ZK_ERR_REMAINDER
+from .groth16 import _csr, _lagrange_at, _many_witnesses, _p, _prove_many, columns_at, ResidentVKey, ZK_ERR_REMAINDER
 from .r1cs import FR_MODULUS, R1CS, fr_bytes
 
 
@@ -287,6 +287,25 @@ class _Prover:
     def reserve_slots(self, count):
         _lib.check(_lib.lib().zk_pinocchio_reserve_slots(self.handle, C.c_uint32(count)))
 
+    def _draw(self, rng):
+        """the blinding scalars of one proof: ZK draws dv, dw, dy in this order (pinocchio.ml:428-430), NonZK takes zeros and draws nothing"""
+        return (0, 0, 0)
+
+    def prove_many(self, rng_or_rs, sols, in_flight=0, return_status=False):
+        """A batch of proofs in ONE call, each as its 480 wire bytes, the eight points in declaration order (zk_pinocchio_prove_many_compressed): what
+        wire.pinocchio_proof_json_of_bytes writes as the proof record and verify_many(..., compressed=True) of a resident key takes.  sols: the
+        witnesses, or an int: that many proofs of the witness set_witness made resident.  rng_or_rs: a callable, drawn per proof in proof order as
+        `prove` draws, or the (dv, dw, dy) triples.  in_flight: proofs kept in flight, 1..15 (0: the library's default).  The first failed proof
+        raises what `prove` raises; with return_status (proofs, statuses) comes back and a failed proof's bytes are zeros."""
+        to_bytes = lambda sol: np.ascontiguousarray(sol, dtype=np.uint8).reshape(-1) if isinstance(sol, np.ndarray) else (
+            np.frombuffer(bytes(sol), dtype=np.uint8) if isinstance(sol, (bytes, bytearray)) else fr_bytes(sol))
+        ws, count = _many_witnesses(to_bytes, sols, self.circuit.m)
+        ds = [self._draw(rng_or_rs) for _ in range(count)] if callable(rng_or_rs) or rng_or_rs is None else [tuple(x) for x in rng_or_rs]
+        if len(ds) != count or any(len(x) != 3 for x in ds):
+            raise ValueError("prove_many: need one (dv, dw, dy) triple per proof")
+        rnd = fr_bytes([x for t in ds for x in t])
+        return _prove_many(_lib.lib().zk_pinocchio_prove_many_compressed, self.handle, ws, rnd, count, in_flight, 480, return_status)
+
     def prove_async(self, dv, dw, dy, slot):
         d = [fr_bytes([x]) for x in (dv, dw, dy)]
         _lib.check(_lib.lib().zk_pinocchio_prove_async(self.handle, None, _p(d[0]), _p(d[1]), _p(d[2]), C.c_uint32(slot)))
@@ -352,11 +371,14 @@ class ZK(_Prover):
     verify = staticmethod(verify)
     verify_many = staticmethod(verify_many)
 
-    def prove(self, rng, sol):
+    def _draw(self, rng):
         dv = rng() % FR_MODULUS     # pinocchio.ml:428-430: dv, dw, dy in this order
         dw = rng() % FR_MODULUS
         dy = rng() % FR_MODULUS
-        return self.prove_with(sol, dv, dw, dy)
+        return dv, dw, dy
+
+    def prove(self, rng, sol):
+        return self.prove_with(sol, *self._draw(rng))
 
 
 class NonZK(_Prover):

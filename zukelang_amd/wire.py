@@ -245,6 +245,23 @@ def groth16_proof_bytes_of_json(data):
     return _proof_bytes_of_json(data, (("a", 1), ("b", 2), ("c", 1)))
 
 
+def _proof_json_of_bytes(b, fields):
+    """The inverse of _proof_bytes_of_json: a proof's wire bytes, as the library's prove_many writes them, cut into the record's point strings.  Only the
+    length is checked; no point is decoded."""
+    b = bytes(b)
+    _need(len(b) == 48 * sum(g for _, g in fields), "a proof of %d points is %d wire bytes" % (len(fields), 48 * sum(g for _, g in fields)))
+    d, o = {}, 0
+    for f, g in fields:
+        d[f] = b[o:o + 48 * g]
+        o += 48 * g
+    return dumps(d)
+
+
+def groth16_proof_json_of_bytes(b):
+    """The 192 wire bytes a | b | c of a proof (Groth16.prove_many) -> the JSON proof record: no point arithmetic and no library call."""
+    return _proof_json_of_bytes(b, (("a", 1), ("b", 2), ("c", 1)))
+
+
 def groth16_vkey_to_json(vk, io_vars):
     """io_vars: the (name, id) of the public variables in key order (Var.Map order = the order of vk.ltgm_io)."""
     lt = bytes(vk.ltgm_io)
@@ -329,6 +346,11 @@ def pinocchio_proof_of_json(data):
 def pinocchio_proof_bytes_of_json(data):
     """A JSON proof -> its 480 wire bytes, the eight points in declaration order, for verify_many(..., compressed=True): no library call here."""
     return _proof_bytes_of_json(data, _PIN_FIELDS)
+
+
+def pinocchio_proof_json_of_bytes(b):
+    """The 480 wire bytes of a proof (prove_many of pinocchio.ZK / NonZK) -> the JSON proof record: no point arithmetic and no library call."""
+    return _proof_json_of_bytes(b, _PIN_FIELDS)
 
 
 def fr_to_json(x):
