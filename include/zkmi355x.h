@@ -286,6 +286,52 @@ int zk_groth16_pk_upload_compressed(uint32_t n, uint32_t m, const zk_csr* L, con
                                     uint32_t form /* ZK_KEY_FORM_TAU_POWERS | ZK_KEY_FORM_LAGRANGE */, uint64_t* handle);
 int zk_bases_upload_compressed(int group, const uint8_t* points, size_t n, uint64_t* handle);
 int zk_groth16_pool_points_compressed(uint64_t handle, int group, uint8_t* out, size_t capacity_points, size_t* count);
+/* ---- the key as a whole: is this proving key a Groth16 key of THIS circuit, and the partner of this verification key? ---------------------
+ * The uploads check a key point by point (encoding, curve, subgroup).  They do not check that ti1 / ti2 hold consecutive powers of one tau, that
+ * tiztd and ltd_mid belong to the circuit and to the delta of d1 / d2, or that the proofs will verify under the verification key at hand.  A key
+ * that fails one of these produces proofs that fail downstream; a CRAFTED ltd_mid or tiztd can make the proof element C leak witness values (Groth16
+ * hides the witness only under a well-formed CRS).  zk_groth16_key_check tests every relation of groth16.ml:45-108 on the key that lies in the
+ * handle, each as ONE random linear combination over all its indices.  With g1 = ti1[0], g2 = ti2[0] and pseudo-random rho, sigma, mu:
+ *   ZK_KEYCHK_GENERATORS  ti1[0], ti2[0] (and the verification key's one1, one2) are the generators                         byte comparison
+ *   ZK_KEYCHK_TAU_G1      ti1[i+1] = tau ti1[i], i <= n, tau that of ti2[1]      e(sum rho_i ti1[i+1], g2) = e(sum rho_i ti1[i], ti2[1])
+ *   ZK_KEYCHK_TAU_G2      ti2[i] has the exponent of ti1[i], i <= n+1            e(sum rho_i ti1[i], g2) = e(g1, sum rho_i ti2[i])
+ *   ZK_KEYCHK_BETA        b1, b2 hold one beta                                   e(b1, g2) = e(g1, b2)
+ *   ZK_KEYCHK_DELTA       d1, d2 hold one delta, delta != 0, vk.d = d2           e(d1, g2) = e(g1, d2); identity test; byte comparison
+ *   ZK_KEYCHK_H_BASES     tiztd[i] delta = tau^i Z(tau), i < n-1                 e(sum sigma_i tiztd[i], d2) = e(sum sigma_i ti1[i], <ti2, coefficients of Z>)
+ *   ZK_KEYCHK_L           ltd_mid[k] delta = L_k(tau) for k in mids, and with a verification key ltgm_io[k] gamma = L_k(tau) for the others (:59-99)
+ *                         e(sum mu_k ltd_mid[k], d2) e(sum mu_k ltgm_io[k], gm) = e(V, b2) e(a, W) e(Y, g2),  V = <ti1, coefficients of sum mu_k v_k>,
+ *                         W = <ti2, .. w_k>, Y = <ti1, .. y_k>; without a verification key mu is 0 outside mids and the gm pair drops out
+ *   ZK_KEYCHK_GAMMA       gamma != 0 (verification key only)                     identity test
+ * A relation reads other points of the key: a wrong ti2[1] also trips ZK_KEYCHK_H_BASES.  The sums are products over the handle's own window tables
+ * (eight in G1, three in G2: the work of about four proofs), the coefficient vectors come from the prover's Fr stage with mu in the witness's place,
+ * the pairings run on the device (the kernels of zk_pairing_product_many, without its point checks: every point is checked already).  vk.ab is not an argument: its bytes are the caller's pairing of pk_g1[0] and pk_g2[0].
+ *   handle: a tau-power key held whole on one device (zk_groth16_pk_upload, zk_groth16_pk_upload_compressed or zk_groth16_keygen with
+ *     ZK_KEY_FORM_TAU_POWERS).  The call leaves it as it found it: a proof made after the check has the bytes of one made before.
+ *   vk_g1 = one1 | ltgm_io (1 + n_io points), vk_g2 = one2 | gm | d: the layouts zk_groth16_keygen writes; both or neither.  n_io = m - |mids|.
+ *   THE CONTRACT FOR seed is that of rho in zk_groth16_verify_folded: 32 bytes from a cryptographic generator, drawn AFTER the key's bytes are fixed
+ *     and unpredictable to whoever made the key.  A malformed key then passes a relation with probability below 2^-253; with the seed known in advance
+ *     a key CAN be built whose defects cancel under the coefficients it expands to.  NULL: the library draws the bytes (std::random_device).  All 256
+ *     bits reach the coefficients: each 64-bit limb of every coefficient is a stream of its own, keyed by 8 bytes of the seed.  The verdict on a
+ *     well-formed key does not depend on the seed.
+ *   Returns ZK_OK whenever the check ran; *failed is the mask of the relations that do not hold, 0 for a well-formed key.  A malformed key is a
+ *     verdict, not an error.  Refused before the device is touched, with ZK_ERR_ARG: failed null; exactly one of vk_g1 / vk_g2; an n_io that is not
+ *     m - |mids|; a handle in Lagrange form (check the key before zk_groth16_pk_derive_lagrange); a shard or a multi-device handle; a handle with a
+ *     proof in flight; a handle uploaded under ZK_KEY_SUBGROUP_CHECK=0 (pairing relations mean nothing outside the subgroup, and the check does not
+ *     repeat the upload's work).  An unknown handle -> ZK_ERR_HANDLE (without a GPU: ZK_ERR_HIP, no handle can exist).  The verification key's points
+ *     are decoded and checked like those of zk_groth16_vk_upload, with its codes.
+ *   Out of scope: Pinocchio keys; sharded and multi-device handles; Lagrange-form handles (zk_groth16_pk_upload_lagrange still rests on its caller's
+ *     promise); no upload checks anything more by default.  Timer family of the check's own launches: key_check. */
+#define ZK_KEYCHK_GENERATORS 1u
+#define ZK_KEYCHK_TAU_G1     2u
+#define ZK_KEYCHK_TAU_G2     4u
+#define ZK_KEYCHK_BETA       8u
+#define ZK_KEYCHK_DELTA      16u
+#define ZK_KEYCHK_H_BASES    32u
+#define ZK_KEYCHK_L          64u
+#define ZK_KEYCHK_GAMMA      128u
+int zk_groth16_key_check(uint64_t handle, const uint8_t* vk_g1 /* one1 | ltgm_io, may be NULL */, size_t n_io,
+                         const uint8_t* vk_g2 /* one2 | gm | d, may be NULL */,
+                         const uint8_t seed[32] /* may be NULL */, uint32_t* failed /* bit mask, 0 = well formed */);
 int zk_groth16_pk_free(uint64_t handle);
 
 /* Groth16.prove rng qap pkey sol with r, s supplied by the caller in the order the reference

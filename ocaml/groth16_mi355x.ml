@@ -274,6 +274,20 @@ module Make (C : Curve.S) = struct
     let rnd = Mi355x.cat (List.concat_map (fun (r, s) -> [ Fr.to_bytes r; Fr.to_bytes s ]) jobs) in
     Mi355x.prove_many_compressed Mi355x.zk_groth16_prove_many_compressed handle ~rnd ~count:(List.length jobs) ~size:192
 
+  (* ---------------------------------------------------------------- check_key
+     Is pkey a well-formed key of qap's circuit -- and, with ~vkey, the partner of that verification key?  Every relation of setup (groth16.ml:45-108)
+     as one random combination on the device (zk_groth16_key_check); the names of the relations that do not hold, [] for a well-formed key.  vkey.ab is
+     compared here, with the pairing of the key's own alpha and beta (groth16.ml:103), and reported as "ab": the library never sees it.  seed: 32 bytes
+     drawn by the caller AFTER the key's bytes are fixed, from a cryptographic generator; without it the library draws them. *)
+  let check_key ?(vkey : vkey option) ?(seed : bytes option) (qap : qap) (pkey : pkey) : string list =
+    let handle = handle_of qap pkey in
+    let vk = Option.map (fun (v : vkey) -> (g1_bytes (v.one1 :: values v.ltgm_io), g2_bytes [ v.one2; v.gm; v.d ])) vkey in
+    let mask = Mi355x.groth16_key_check ?vk ?seed handle in
+    let names = List.filter_map (fun (bit, name) -> if mask land bit <> 0 then Some name else None) Mi355x.keychk_names in
+    match vkey with
+    | Some v when not GT.(Pairing.pairing pkey.a pkey.b2 = v.ab) -> names @ [ "ab" ]
+    | _ -> names
+
   (* ---------------------------------------------------------------- verify
      e(A, B) = ab + e(sum_k w_k [L_k(tau)/gamma]_1, gamma) + e(C, delta), GT written additively as Curve.G has it.  The sum
      runs over the public coefficients; domains must agree (G.dot). *)

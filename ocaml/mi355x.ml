@@ -473,6 +473,25 @@ let pool_points_compressed stub (h : Unsigned.UInt64.t) ~(pool : int) ~(point_by
   check (stub h pool (CArray.start out) !@cnt cnt);
   Bytes.init len (fun i -> CArray.get out i)
 
+(* The key as a whole against its circuit and, when given, its verification key (include/zkmi355x.h, "the key as a whole"): vk_g1, vk_g2 and seed may be
+   null.  failed: the mask of the relations that do not hold (the header's ZK_KEYCHK bits), 0 for a well-formed key. *)
+let zk_groth16_key_check =
+  fn "zk_groth16_key_check" (uint64_t @-> ptr char @-> size_t @-> ptr char @-> ptr char @-> ptr uint32_t @-> returning int)
+
+(* the bits of the mask, in bit order, under their names *)
+let keychk_names = [ (1, "generators"); (2, "tau_g1"); (4, "tau_g2"); (8, "beta"); (16, "delta"); (32, "h_bases"); (64, "l"); (128, "gamma") ]
+
+(* vk: (one1 | ltgm_io, one2 | gm | d) as uncompressed bytes, or None: the key against its circuit alone.  seed: 32 bytes the CALLER drew from a
+   cryptographic generator after the key's bytes were fixed (the header's contract); None: the library draws them.  Returns the mask. *)
+let groth16_key_check ?vk ?seed (h : Unsigned.UInt64.t) : int =
+  let failed = allocate uint32_t Unsigned.UInt32.zero in
+  let arr = Option.map carray_of_bytes in
+  let v1 = arr (Option.map fst vk) and v2 = arr (Option.map snd vk) and sd = arr seed in
+  let start = function Some a -> CArray.start a | None -> null_bytes in
+  let n_io = match vk with Some (g1, _) -> (Bytes.length g1 / 96) - 1 | None -> 0 in
+  check (zk_groth16_key_check h (start v1) (sz n_io) (start v2) (start sd) failed);
+  Unsigned.UInt32.to_int !@failed
+
 let pinocchio_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in
   check

@@ -45,6 +45,10 @@ int frstage_scratch_alloc(const FrStage& f, FrScratch& sc);
 // Montgomery form; *sc.flag |= 1 when some gate is violated (QAP.ml:134), |= 2 when a witness
 // value is not canonical.  Everything is enqueued on `s`; nothing synchronizes.
 int frstage_eval(const FrStage& f, FrScratch& sc, const void* d_witness_canonical, hipStream_t s);
+// The stage's basis conversion alone: the VALUES on 0..n-1 in sc.abc[0..n) and sc.abc[n..2n) (Montgomery) -> the monomial coefficients of their
+// interpolants in sc.d[0..n) and sc.d[n2..n2+n).  What frstage_eval does to L w and R w; callers with values of their own (the key check's O mu) write
+// them into sc.abc first.  sc.abc is not changed; sc.bufA and sc.tmp are scratch.  Enqueues only.
+int frstage_interpolate(const FrStage& f, FrScratch& sc, hipStream_t s);
 // the flag word, copied to the host, as the status of the proof it belongs to
 static inline int status_of_flags(const void* flag_word, const char* range_text = "witness value >= r") {
     int hf;

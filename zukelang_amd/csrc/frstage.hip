@@ -518,24 +518,8 @@ int frstage_eval(const FrStage& f, FrScratch& sc, const void* d_wit_canon, hipSt
         hipLaunchKernelGGL(k_check_r1cs, g1d(n), dim3(256), 0, s, (const uint32_t*)a, (const uint32_t*)b, (const uint32_t*)cc, n, sc.flag.as<int>());
         HIPCHK(hipGetLastError());
     }
-    if (n == 1) {      // one gate: the values are the (constant) polynomials; h is empty
-        HIPCHK(hipMemcpyAsync(sc.d.p, a, 32, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(FRP(sc.d) + 8 * (uint64_t)n2, b, 32, hipMemcpyDeviceToDevice, s));
-        return ZK_OK;
-    }
-    // ---- values -> Newton coefficients (both vectors), into d[0..n2) and d[n2..2 n2)
-    {
-        ScopedTimer t("fr_newton", s);
-        // both vectors as two nodes of one batched convolution
-        hipLaunchKernelGGL(k_scale_pad2, g1d(2 * (uint64_t)S), dim3(256), 0, s, FRP(sc.bufA), (const uint32_t*)a, (const uint32_t*)FRP(f.invfact), (uint64_t)n, (uint64_t)n,
-                           (uint64_t)S, 2 * (uint64_t)S);
-        if (rns) ZKCHK(rns_conv_table(sc.rns_a, sc.bufA.p, 2 * (uint64_t)S, f.log_S, RNS_IN_PLAIN, f.e_rns, (uint64_t)S - 1, sc.bufA.p, RNS_OUT_RANGE, 0, n, (uint64_t)S, s));
-        else ZKCHK(ntt_mul_table(sc.bufA.p, 2 * (uint64_t)S, f.log_S, f.e_ntt.p, (uint64_t)S - 1, true, nullptr, nullptr, s));
-        hipLaunchKernelGGL(k_scale_pad2, g1d(2 * (uint64_t)n2), dim3(256), 0, s, FRP(sc.d), (const uint32_t*)FRP(sc.bufA), (const uint32_t*)nullptr, (uint64_t)n, (uint64_t)S,
-                           (uint64_t)n2, 2 * (uint64_t)n2);
-    }
-    // ---- Newton -> monomial
-    ZKCHK(tree_convert(f, sc.d.p, 2, f.log_n2, sc.tmp.p, s, rns ? &sc.rns_a : nullptr));
+    ZKCHK(frstage_interpolate(f, sc, s));
+    if (n == 1) return ZK_OK;      // one gate: h is empty
     // ---- h
     {
         ScopedTimer t("fr_quotient", s);
@@ -555,6 +539,35 @@ int frstage_eval(const FrStage& f, FrScratch& sc, const void* d_wit_canon, hipSt
         // h[j] = hh[n-2-j], j < n-1
         hipLaunchKernelGGL(k_reverse_pad, g1d(n - 1), dim3(256), 0, s, FRP(sc.h), (const uint32_t*)(FRP(sc.bufA) + 8 * (uint64_t)S), (uint64_t)n - 2, (uint64_t)n - 1, (uint64_t)n - 1);
     }
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// Steps 2-3 of the stage on their own: the VALUES on the points 0..n-1 of two vectors, sc.abc[0..n) and sc.abc[n..2n), become the monomial
+// coefficients of their interpolants in sc.d[0..n) and sc.d[n2..n2+n) (Montgomery in and out).  frstage_eval runs it on L w and R w; the key check
+// (key_check.hip) also on O mu, which a proof never converts.  Works in sc.bufA and sc.tmp; sc.abc is left as it was.  Enqueues only.
+int frstage_interpolate(const FrStage& f, FrScratch& sc, hipStream_t s) {
+    const uint32_t n = f.n, n2 = f.n2, S = f.S;
+    const bool rns = f.rns_ok && n > 1 && rns_enabled();
+    const uint32_t* a = FRP(sc.abc);
+    const uint32_t* b = a + 8 * (uint64_t)n;
+    if (n == 1) {      // one gate: the values are the (constant) polynomials
+        HIPCHK(hipMemcpyAsync(sc.d.p, a, 32, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(FRP(sc.d) + 8 * (uint64_t)n2, b, 32, hipMemcpyDeviceToDevice, s));
+        return ZK_OK;
+    }
+    // ---- values -> Newton coefficients (both vectors), into d[0..n2) and d[n2..2 n2)
+    {
+        ScopedTimer t("fr_newton", s);
+        // both vectors as two nodes of one batched convolution
+        hipLaunchKernelGGL(k_scale_pad2, g1d(2 * (uint64_t)S), dim3(256), 0, s, FRP(sc.bufA), (const uint32_t*)a, (const uint32_t*)FRP(f.invfact), (uint64_t)n, (uint64_t)n,
+                           (uint64_t)S, 2 * (uint64_t)S);
+        if (rns) ZKCHK(rns_conv_table(sc.rns_a, sc.bufA.p, 2 * (uint64_t)S, f.log_S, RNS_IN_PLAIN, f.e_rns, (uint64_t)S - 1, sc.bufA.p, RNS_OUT_RANGE, 0, n, (uint64_t)S, s));
+        else ZKCHK(ntt_mul_table(sc.bufA.p, 2 * (uint64_t)S, f.log_S, f.e_ntt.p, (uint64_t)S - 1, true, nullptr, nullptr, s));
+        hipLaunchKernelGGL(k_scale_pad2, g1d(2 * (uint64_t)n2), dim3(256), 0, s, FRP(sc.d), (const uint32_t*)FRP(sc.bufA), (const uint32_t*)nullptr, (uint64_t)n, (uint64_t)S,
+                           (uint64_t)n2, 2 * (uint64_t)n2);
+    }
+    // ---- Newton -> monomial
+    ZKCHK(tree_convert(f, sc.d.p, 2, f.log_n2, sc.tmp.p, s, rns ? &sc.rns_a : nullptr));
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }

@@ -543,6 +543,27 @@ int zk_groth16_pk_derive_lagrange(uint64_t handle) {
     ZKCHK(zk_groth16_pk_derive_lagrange_sets(handle, 7, n1.p, n2.p));
     return zk_groth16_pk_install_lagrange(handle, n1.p, n2.p, 0, 1);
 }
+// The key as a whole against its circuit and its verification key (include/zkmi355x.h; key_check.hip holds the check).  Everything that can be refused
+// is refused here, before the device is touched.
+int zk_groth16_key_check(uint64_t handle, const uint8_t* vk_g1, size_t n_io, const uint8_t* vk_g2, const uint8_t seed[32], uint32_t* failed) {
+    if (!failed) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: null failed");
+    if (!vk_g1 != !vk_g2) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: vk_g1 and vk_g2 come together or not at all");
+    if (group_lookup(handle)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: multi-device keys are not checked; check the key on one device");
+    Groth16Key* kp = g_keys.find(handle);
+    if (!kp) {
+        ZKCHK(ensure_init());          // without a device no handle exists: say that, not that this one is unknown
+        ZK_FAIL(ZK_ERR_HANDLE, g_keys.unknown());
+    }
+    Groth16Key& k = *kp;
+    if (k.lagrange) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: the handle holds Lagrange-form pools; the check reads the tau powers (check the key before zk_groth16_pk_derive_lagrange)");
+    if (k.world != 1) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: the key is a shard; the check needs the whole pools");
+    if ((vk_g1 || n_io) && n_io != (size_t)k.m - k.n_mid) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: n_io is not the number of variables outside mids");
+    for (uint32_t i = 0; i < MAX_SLOTS; i++)
+        if (k.slots[i] && k.slots[i]->busy) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: a proof is in flight on this key: call the matching _wait first");
+    if (!k.g1.in_subgroup || !k.g2.in_subgroup)
+        ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: the key was uploaded under ZK_KEY_SUBGROUP_CHECK=0; pairing relations mean nothing outside the subgroup");
+    return groth16_key_check(k, vk_g1, n_io, vk_g2, seed, failed);
+}
 int zk_groth16_pk_shard(uint64_t handle, uint32_t rank, uint32_t world) {
     Groth16Key* kp;
     ZKCHK(key_lookup(handle, &kp));

@@ -188,6 +188,22 @@ class Proof:
         return G1.to_compressed_bytes(self.a) + G2.to_compressed_bytes(self.b) + G1.to_compressed_bytes(self.c)
 
 
+class KeyCheck:
+    """The verdict of Groth16.check_key: .failed is zk_groth16_key_check's mask (plus this wrapper's "ab" bit), .names the relations that do not
+    hold, in bit order, .ok whether there is none."""
+
+    def __init__(self, failed):
+        self.failed = int(failed)
+        self.names = [name for name, bit in _lib.KEYCHK_BITS.items() if self.failed & bit] + (["ab"] if self.failed & _lib.KEYCHK_AB else [])
+        self.ok = self.failed == 0
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "KeyCheck(ok)" if self.ok else "KeyCheck(failed=%s)" % "|".join(self.names)
+
+
 def _lagrange_at(n, tau):
     """l_i(tau) for the integer domain 0..n-1 and Z(tau) (QAP.ml:84,92), O(n) with one inversion."""
     P = FR_MODULUS
@@ -414,6 +430,7 @@ class Groth16:
                                                 _p(g1), len(g1) // 96, _p(g2), len(g2) // 192, _p(v1), _p(v2), C.byref(h)))
         self = cls.__new__(cls)
         self.circuit, self.rank, self.world, self._keep, self.handle = circuit, 0, 1, (circuit,), h
+        self._ab_src = (bytes(g1[:96]), bytes(g2[:192]))
         vk = VKey(bytes(v1[:96]), v1[96:], bytes(v2[:192]), bytes(v2[192:384]), bytes(v2[384:]),
                   Pairing.pairing(bytes(g1[:96]), bytes(g2[:192])))        # ab = e(alpha, beta), groth16.ml:103
         return self, PKey(g1, g2), vk
@@ -462,6 +479,7 @@ class Groth16:
                                                                      _p(g2), len(g2) // 96, _lib.KEY_FORMS["lagrange" if lagrange else "tau_powers"], C.byref(h)))
         self = cls.__new__(cls)
         self.circuit, self.rank, self.world, self._keep, self.handle = circuit, 0, 1, (circuit,), h
+        self._ab_src = (bytes(g1[:48]), bytes(g2[:96]))
         return self
 
     def derive_lagrange(self):
@@ -520,6 +538,47 @@ class Groth16:
         (zk_groth16_pk_shard): afterwards prove_rs / prove_async / prove_wait run the all-gather + combine of the sharded path."""
         _lib.check(_lib.lib().zk_groth16_pk_shard(self.handle, C.c_uint32(rank), C.c_uint32(world)))
         self.rank, self.world = rank, world
+
+    def _alpha_beta(self):
+        """a and b2 of the key this prover was made from (uncompressed bytes): what vkey.ab must be the pairing of"""
+        if len(self._keep) > 1:
+            pk = self._keep[1]
+            return bytes(pk.g1[:96]), bytes(pk.g2[:192])
+        src = getattr(self, "_ab_src", None)
+        if src is None:
+            raise ValueError("check_key: this prover does not know its key's a and b2")
+        a, b2 = src
+        if len(a) == 48:          # from_compressed: wire bytes
+            a, b2 = G1.of_compressed_bytes_many(a), G2.of_compressed_bytes_many(b2)
+        return bytes(a), bytes(b2)
+
+    def check_key(self, vkey=None, seed=None):
+        """Is the key in this handle a well-formed Groth16 key of this circuit -- and, with `vkey`, the partner of that verification key?
+        (zk_groth16_key_check: every relation of the setup as one random combination on the device, the cost of a few proofs.)  Returns a KeyCheck:
+        .ok, .failed (the mask) and .names.  A malformed key is a verdict, not an exception.  seed: 32 bytes; leave it None and they are drawn from
+        os.urandom here, after the key's bytes are fixed.  A caller that passes its own takes over the contract of include/zkmi355x.h: unpredictable to
+        whoever made the key.  With a vkey, vkey.ab is compared with e(a, b2) on the host and reported as "ab" (bit 31, a name of this wrapper: the
+        library never sees ab).  Tau-power handles held whole on one device only."""
+        import os
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("check_key: the seed is 32 bytes")
+        sd = np.frombuffer(seed, dtype=np.uint8)
+        failed = C.c_uint32(0)
+        if vkey is None:
+            _lib.check(_lib.lib().zk_groth16_key_check(self.handle, None, 0, None, _p(sd), C.byref(failed)))
+            return KeyCheck(failed.value)
+        lt = np.ascontiguousarray(vkey.ltgm_io, dtype=np.uint8).reshape(-1)
+        v1 = np.frombuffer(bytes(vkey.one1) + bytes(lt), dtype=np.uint8)
+        v2 = np.frombuffer(bytes(vkey.one2) + bytes(vkey.gm) + bytes(vkey.d), dtype=np.uint8)
+        if len(v1) % 96 or len(v1) < 96 or len(v2) != 576:
+            raise ValueError("check_key: the verification key is not (1 + n_io) * 96 and 3 * 192 bytes")
+        _lib.check_points(_lib.lib().zk_groth16_key_check(self.handle, _p(v1), len(v1) // 96 - 1, _p(v2), _p(sd), C.byref(failed)))
+        mask = failed.value
+        a, b2 = self._alpha_beta()
+        if bytes(vkey.ab) != bytes(Pairing.pairing(a, b2)):
+            mask |= _lib.KEYCHK_AB
+        return KeyCheck(mask)
 
     def pool_points(self, group, compressed=False):
         """The resident base pool (1 = G1, 2 = G2) as uncompressed bytes, in pool order; compressed=True: in wire form (48 / 96 B per point, encoded
