@@ -15,6 +15,7 @@ from collections import Counter
 import pytest
 
 import oracle_lib as O
+from msm_digit_model import bucket_keys, digit_plan, msm_windows as windows
 from oracle import pyref as P
 from test_gpu_options import options
 from zukelang_amd.curve import G1, G2
@@ -40,32 +41,8 @@ SETTINGS = [
 ]
 
 
-# ---- the plan, restated (csrc/msm_tail.cuh: digit_plan; csrc/msm_digits.cuh: the recoding; csrc/msm.hip: the chunks)
-def digit_plan(c):
-    nbw = 1 << (c - 1)
-    lb = (c + 1) // 2
-    return dict(nbw=nbw, lb=lb, nd0=1 << lb, nd1=(nbw >> lb) + 1)
-
-
-def windows(c):
-    return 255 // c + 1
-
-
-def bucket_keys(scalars, c, precomp, identity):
-    """the global bucket of every non-zero digit of every scalar whose base is not the identity, as the sort files them"""
-    nw, bias, nbw = windows(c), (1 << (c - 1)) - 1, 1 << (c - 1)
-    K = sum(bias << (c * j) for j in range(nw))
-    keys = []
-    for s, ident in zip(scalars, identity):
-        if s == 0 or ident:
-            continue
-        for j in range(nw):
-            e = ((s + K) >> (c * j)) & ((1 << c) - 1)
-            if e != bias:
-                keys.append((0 if precomp else j * nbw) + abs(e - bias) - 1)
-    return keys
-
-
+# ---- the plan, restated (csrc/msm_tail.cuh: digit_plan; csrc/msm_digits.cuh: the recoding, shared with tests/test_gpu_msm_digit_ends.py in
+# tests/msm_digit_model.py and held to the sources there and below; csrc/msm.hip: the chunks)
 def runs(scalars, c, precomp, identity):
     """{bucket: (first sorted position, entries)} of a product"""
     counts = Counter(bucket_keys(scalars, c, precomp, identity))
