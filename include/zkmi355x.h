@@ -264,7 +264,7 @@ int zk_groth16_pool_points(uint64_t handle, int group, uint8_t* out, size_t capa
  *   answer as [r] P = O on every point of the curve.  ZK_KEY_SUBGROUP_CHECK=0 means what it means at upload: no subgroup test, no folded windows.
  *   Null L / R / O / mid / pools / handle or an unknown form -> ZK_ERR_ARG before the device is touched; without a GPU -> ZK_ERR_HIP.
  * zk_groth16_pk_upload_compressed: form = ZK_KEY_FORM_TAU_POWERS is zk_groth16_pk_upload, ZK_KEY_FORM_LAGRANGE is zk_groth16_pk_upload_lagrange (its
- *   lengths, and its caller's promise that the points are the key's Lagrange form).
+ *   lengths, and its caller's promise that the points are the key's Lagrange form -- which zk_groth16_key_check_lagrange puts to the test).
  * zk_pinocchio_pk_upload_compressed (below): h_lagrange = NULL is zk_pinocchio_pk_upload, else zk_pinocchio_pk_upload_lagrange (n points of 48 B;
  *   ZK_ERR_ARG under a device list of several entries, as there).  si[0] must be the generator's wire bytes.  The n + 1 G2 points between waw and the
  *   two appended points are not read, as in the uncompressed call.
@@ -315,12 +315,12 @@ int zk_groth16_pool_points_compressed(uint64_t handle, int group, uint8_t* out, 
  *     well-formed key does not depend on the seed.
  *   Returns ZK_OK whenever the check ran; *failed is the mask of the relations that do not hold, 0 for a well-formed key.  A malformed key is a
  *     verdict, not an error.  Refused before the device is touched, with ZK_ERR_ARG: failed null; exactly one of vk_g1 / vk_g2; an n_io that is not
- *     m - |mids|; a handle in Lagrange form (check the key before zk_groth16_pk_derive_lagrange); a shard or a multi-device handle; a handle with a
+ *     m - |mids|; a handle in Lagrange form (zk_groth16_key_check_lagrange checks that form); a shard or a multi-device handle; a handle with a
  *     proof in flight; a handle uploaded under ZK_KEY_SUBGROUP_CHECK=0 (pairing relations mean nothing outside the subgroup, and the check does not
  *     repeat the upload's work).  An unknown handle -> ZK_ERR_HANDLE (without a GPU: ZK_ERR_HIP, no handle can exist).  The verification key's points
  *     are decoded and checked like those of zk_groth16_vk_upload, with its codes.
- *   Out of scope: Pinocchio keys; sharded and multi-device handles; Lagrange-form handles (zk_groth16_pk_upload_lagrange still rests on its caller's
- *     promise); no upload checks anything more by default.  Timer family of the check's own launches: key_check. */
+ *   Out of scope: Pinocchio keys; sharded and multi-device handles (those three still rest on their caller's promise); Lagrange-form handles have
+ *     the call below; no upload checks anything more by default.  Timer family of the check's own launches: key_check. */
 #define ZK_KEYCHK_GENERATORS 1u
 #define ZK_KEYCHK_TAU_G1     2u
 #define ZK_KEYCHK_TAU_G2     4u
@@ -332,6 +332,40 @@ int zk_groth16_pool_points_compressed(uint64_t handle, int group, uint8_t* out, 
 int zk_groth16_key_check(uint64_t handle, const uint8_t* vk_g1 /* one1 | ltgm_io, may be NULL */, size_t n_io,
                          const uint8_t* vk_g2 /* one2 | gm | d, may be NULL */,
                          const uint8_t seed[32] /* may be NULL */, uint32_t* failed /* bit mask, 0 = well formed */);
+/* ---- a Lagrange-form key as a whole -----------------------------------------------------------------------------------------------------------
+ * The same question for a handle in Lagrange form, however it came by it: zk_groth16_pk_upload_lagrange, zk_groth16_pk_upload_compressed or
+ * zk_groth16_keygen with ZK_KEY_FORM_LAGRANGE, zk_groth16_pk_derive_lagrange.  Pools read back from a key cache are bytes from somewhere else: this is
+ * the check between loading them and proving, without the derivation the cache exists to save.  Such a handle holds no tau power, not even [tau]_2, so
+ * the relations are stated on VALUES.  Pools g1 = a | d1 | b1 | l1[n] | hl[n-1] | ltd_mid, g2 = b2 | d2 | l2[n]; l_i the Lagrange basis of the points
+ * 0..n-1, lambda_t of n..2n-2, w_i = (-1)^(n-1-i) / (i! (n-1-i)!) the barycentric weights of 0..n-1; g1 := sum l1[i], g2 := sum l2[i] (honestly the
+ * generators: sum l_i = 1), T2 := sum i l2[i] (honestly [tau]_2: sum i l_i(X) = X for n >= 2).  The bits are those of zk_groth16_key_check:
+ *   ZK_KEYCHK_GENERATORS  sum l1 = [1]_1, sum l2 = [1]_2 (and the verification key's one1, one2 are the generators)          byte comparison
+ *   ZK_KEYCHK_TAU_G2      l1[i] g2 = g1 l2[i]                                     e(sum rho_i l1[i], g2) = e(g1, sum rho_i l2[i])
+ *   ZK_KEYCHK_TAU_G1      l1 is the Lagrange basis at ONE point: l1[i] (i g2 - T2) is proportional to w_i (n >= 2)
+ *                         e(sum i pi_i l1[i], g2) = e(sum pi_i l1[i], T2) for pi in the hyperplane sum w_i pi_i = 0 -- the values on 0..n-1 of a polynomial
+ *                         q of degree <= n-2; a linear form vanishes on all of it exactly when its coefficients are proportional to w
+ *   ZK_KEYCHK_BETA        b1 g2 = g1 b2                                           e(b1, g2) = e(g1, b2)
+ *   ZK_KEYCHK_DELTA       d1 g2 = g1 d2, delta != 0, vk.d = d2                    e(d1, g2) = e(g1, d2); identity test; byte comparison
+ *   ZK_KEYCHK_H_BASES     w_0 hl[t] d2 = l2[0] sum_i i lambda_t(i) l1[i], t < n-1, i.e. hl[t] delta = lambda_t(tau) Z(tau) (tau l_0(tau) / w_0 = Z(tau))
+ *                         e(sum_t w_0 sigma_t hl[t], d2) = e(S, l2[0]), sigma_t = q(n + t), S = sum i pi_i l1[i] (the sum TAU_G1 has made); pi -> sigma is a
+ *                         bijection onto Fr^(n-1), so every t has a coefficient of its own
+ *   ZK_KEYCHK_L           ltd_mid[k] d2 (mids; with a verification key ltgm_io[k] gm for the others) = (sum_i L[i,k] l1[i]) b2 + a (sum_i R[i,k] l2[i])
+ *                         + (sum_i O[i,k] l1[i]) g2:   e(sum mu_k ltd_mid[k], d2) e(sum mu_k ltgm_io[k], gm) = e(V, b2) e(a, W) e(Y, g2),
+ *                         V = sum_i (L mu)_i l1[i], W = sum_i (R mu)_i l2[i], Y = sum_i (O mu)_i l1[i]
+ *   ZK_KEYCHK_GAMMA       gamma != 0 (verification key only)                      identity test
+ * For n = 1 TAU_G1 and H_BASES are vacuous and never set.  A well-formed basis of ANOTHER point (the tau of hl and ltd_mid shifted, or the domain 1..n,
+ * which is the domain 0..n-1 at tau - 1) passes TAU_G1 and fails H_BASES and L.  No basis conversion runs: pi comes from a raw vector without a
+ * division, sigma by the prover's own extrapolation, L mu | R mu | O mu from its Fr stage with mu in the witness's place; twelve products over the
+ * handle's window tables (eight in G1, four in G2), twelve pairing products on the device.
+ *   handle: a Lagrange-form key held whole on one device.  Nothing of the handle is written: a proof made after the check has the bytes of one made
+ *     before.  vk_g1, n_io, vk_g2, seed (THE SAME CONTRACT), the return value ("a malformed key is a verdict, not an error"), the decoding of the
+ *     verification key with its codes and the timer family key_check are those of zk_groth16_key_check.
+ *   Refused before the device is touched, with ZK_ERR_ARG: failed null; exactly one of vk_g1 / vk_g2; an n_io that is not m - |mids|; a tau-power
+ *     handle (zk_groth16_key_check is its call); a shard or a multi-device handle; a handle with a proof in flight; a handle made under
+ *     ZK_KEY_SUBGROUP_CHECK=0.  An unknown handle -> ZK_ERR_HANDLE (without a GPU: ZK_ERR_HIP). */
+int zk_groth16_key_check_lagrange(uint64_t handle, const uint8_t* vk_g1 /* one1 | ltgm_io, may be NULL */, size_t n_io,
+                                  const uint8_t* vk_g2 /* one2 | gm | d, may be NULL */,
+                                  const uint8_t seed[32] /* may be NULL */, uint32_t* failed /* bit mask, 0 = well formed */);
 int zk_groth16_pk_free(uint64_t handle);
 
 /* Groth16.prove rng qap pkey sol with r, s supplied by the caller in the order the reference

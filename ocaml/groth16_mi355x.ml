@@ -279,14 +279,25 @@ module Make (C : Curve.S) = struct
      as one random combination on the device (zk_groth16_key_check); the names of the relations that do not hold, [] for a well-formed key.  vkey.ab is
      compared here, with the pairing of the key's own alpha and beta (groth16.ml:103), and reported as "ab": the library never sees it.  seed: 32 bytes
      drawn by the caller AFTER the key's bytes are fixed, from a cryptographic generator; without it the library draws them. *)
-  let check_key ?(vkey : vkey option) ?(seed : bytes option) (qap : qap) (pkey : pkey) : string list =
-    let handle = handle_of qap pkey in
-    let vk = Option.map (fun (v : vkey) -> (g1_bytes (v.one1 :: values v.ltgm_io), g2_bytes [ v.one2; v.gm; v.d ])) vkey in
-    let mask = Mi355x.groth16_key_check ?vk ?seed handle in
+  let key_check_names ?(vkey : vkey option) (pkey : pkey) (mask : int) : string list =
     let names = List.filter_map (fun (bit, name) -> if mask land bit <> 0 then Some name else None) Mi355x.keychk_names in
     match vkey with
     | Some v when not GT.(Pairing.pairing pkey.a pkey.b2 = v.ab) -> names @ [ "ab" ]
     | _ -> names
+
+  let vk_bytes (vkey : vkey option) = Option.map (fun (v : vkey) -> (g1_bytes (v.one1 :: values v.ltgm_io), g2_bytes [ v.one2; v.gm; v.d ])) vkey
+
+  let check_key ?(vkey : vkey option) ?(seed : bytes option) (qap : qap) (pkey : pkey) : string list =
+    let vk = vk_bytes vkey in
+    key_check_names ?vkey pkey (Mi355x.groth16_key_check ?vk ?seed (handle_of qap pkey))
+
+  (* The same for the key as the handle holds it in LAGRANGE form (zk_groth16_key_check_lagrange): after derive_lagrange_on_upload, or for `handle`
+     from upload_compressed ~lagrange:true -- pools read back from a key cache, bytes from somewhere else until this has looked at them.  No derivation
+     runs.  pkey gives alpha and beta for "ab"; the names are check_key's. *)
+  let check_key_lagrange ?(vkey : vkey option) ?(seed : bytes option) ?(handle : Unsigned.UInt64.t option) (qap : qap) (pkey : pkey) : string list =
+    let h = match handle with Some h -> h | None -> handle_of qap pkey in
+    let vk = vk_bytes vkey in
+    key_check_names ?vkey pkey (Mi355x.groth16_key_check_lagrange ?vk ?seed h)
 
   (* ---------------------------------------------------------------- verify
      e(A, B) = ab + e(sum_k w_k [L_k(tau)/gamma]_1, gamma) + e(C, delta), GT written additively as Curve.G has it.  The sum

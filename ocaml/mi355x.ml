@@ -483,14 +483,23 @@ let keychk_names = [ (1, "generators"); (2, "tau_g1"); (4, "tau_g2"); (8, "beta"
 
 (* vk: (one1 | ltgm_io, one2 | gm | d) as uncompressed bytes, or None: the key against its circuit alone.  seed: 32 bytes the CALLER drew from a
    cryptographic generator after the key's bytes were fixed (the header's contract); None: the library draws them.  Returns the mask. *)
-let groth16_key_check ?vk ?seed (h : Unsigned.UInt64.t) : int =
+let key_check_call stub ?vk ?seed (h : Unsigned.UInt64.t) : int =
   let failed = allocate uint32_t Unsigned.UInt32.zero in
   let arr = Option.map carray_of_bytes in
   let v1 = arr (Option.map fst vk) and v2 = arr (Option.map snd vk) and sd = arr seed in
   let start = function Some a -> CArray.start a | None -> null_bytes in
   let n_io = match vk with Some (g1, _) -> (Bytes.length g1 / 96) - 1 | None -> 0 in
-  check (zk_groth16_key_check h (start v1) (sz n_io) (start v2) (start sd) failed);
+  check (stub h (start v1) (sz n_io) (start v2) (start sd) failed);
   Unsigned.UInt32.to_int !@failed
+
+let groth16_key_check ?vk ?seed (h : Unsigned.UInt64.t) : int = key_check_call zk_groth16_key_check ?vk ?seed h
+
+(* The same question for a handle in Lagrange form (include/zkmi355x.h, "a Lagrange-form key as a whole"): pools loaded with form = key_form_lagrange,
+   generated in that form or derived on the device.  The same arguments, the same bits; a tau-power handle is refused. *)
+let zk_groth16_key_check_lagrange =
+  fn "zk_groth16_key_check_lagrange" (uint64_t @-> ptr char @-> size_t @-> ptr char @-> ptr char @-> ptr uint32_t @-> returning int)
+
+let groth16_key_check_lagrange ?vk ?seed (h : Unsigned.UInt64.t) : int = key_check_call zk_groth16_key_check_lagrange ?vk ?seed h
 
 let pinocchio_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in

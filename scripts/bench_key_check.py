@@ -5,7 +5,7 @@
 under zk_profile_enable(2), the device time of ONE check by timer family (zk_profile_get; the check's own launches are the family key_check).
 
 The claim under test is "a check costs a small multiple of one proof": the JSON holds both figures and their ratio, whatever it is.
-(zk_groth16_key_check_lagrange of the issue that asked for this script is not built: there is no second figure.)
+(zk_groth16_key_check_lagrange has a script of its own, scripts/bench_key_check_lagrange.py, which times both calls side by side.)
 
     python scripts/bench_key_check.py --out profiles/key_check.json
 """
@@ -98,7 +98,7 @@ def main():
     a = ap.parse_args()
     _lib.check(_lib.lib().zk_init(0))
     doc = {"how": "python scripts/bench_key_check.py (host wall time, best of %d; one MI355X)" % a.repeats,
-           "not_measured": "check_lagrange_against: zk_groth16_key_check_lagrange is not built", "sizes": {}}
+           "see_also": "zk_groth16_key_check_lagrange: scripts/bench_key_check_lagrange.py -> profiles/key_check_lagrange.json", "sizes": {}}
     for log_n in a.log_n:
         doc["sizes"]["2^%d" % log_n] = measure(log_n, a.repeats)
         print("2^%d:" % log_n, json.dumps({k: (v["best_ms"] if isinstance(v, dict) and "best_ms" in v else v) for k, v in doc["sizes"]["2^%d" % log_n].items()

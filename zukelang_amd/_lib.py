@@ -34,7 +34,7 @@ EXPORTS = [
     "zk_selftest_fr", "zk_selftest_fr29",
     "zk_groth16_pk_upload_compressed", "zk_pinocchio_pk_upload_compressed", "zk_bases_upload_compressed", "zk_groth16_pool_points_compressed", "zk_pinocchio_pool_points_compressed",
     "zk_groth16_prove_many_compressed", "zk_pinocchio_prove_many_compressed", "zk_selftest_proof_wire",
-    "zk_groth16_key_check",
+    "zk_groth16_key_check", "zk_groth16_key_check_lagrange",
 ]
 
 
@@ -131,6 +131,11 @@ PROVE_MANY_PROTOTYPES = {
 KEY_CHECK_PROTOTYPES = {
     "zk_groth16_key_check": [C.c_uint64, _P8, C.c_size_t, _P8, _P8, C.POINTER(C.c_uint32)],
 }
+# the same check of a Lagrange-form handle (tests/test_key_check_lagrange_surface.py holds it to the header).  A table of its own:
+# tests/test_key_check_surface.py holds KEY_CHECK_PROTOTYPES to exactly the one entry.
+KEY_CHECK_LAGRANGE_PROTOTYPES = {
+    "zk_groth16_key_check_lagrange": [C.c_uint64, _P8, C.c_size_t, _P8, _P8, C.POINTER(C.c_uint32)],
+}
 # the bits of zk_groth16_key_check's mask (ZK_KEYCHK_*), in bit order, under the names Groth16.check_key reports
 KEYCHK_BITS = {
     "generators": 1, "tau_g1": 2, "tau_g2": 4, "beta": 8, "delta": 16, "h_bases": 32, "l": 64, "gamma": 128,
@@ -151,7 +156,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()) + list(KEY_CHECK_LAGRANGE_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

@@ -62,6 +62,10 @@ static inline int status_of_flags(const void* flag_word, const char* range_text 
 // sc.abc[0..n), sc.abc[n..2n) and h(n + t), t < n - 1, in sc.h (Montgomery); flags as above.
 int frstage_init_lagrange(FrStage& f, hipStream_t s);     // after frstage_init
 int frstage_eval_lagrange(const FrStage& f, FrScratch& sc, const void* d_witness_canonical, hipStream_t s);
+// The variant's extrapolation alone (n >= 2): n VALUES on 0..n-1 (Montgomery) -> S_j = sum_i x_i c_i / (j - i) at d_buf[j], j = n .. 2n-2; the
+// interpolant's value at n + t is f.zt[t] S_(n+t).  d_buf holds f.S elements (the rest is scratch) and may be any device buffer; sc lends its residue
+// arrays.  What frstage_eval_lagrange does to L w, R w, O w; the Lagrange-form key check runs it on coefficients of its own.  Enqueues only.
+int frstage_extrapolate(const FrStage& f, FrScratch& sc, const void* d_values, void* d_buf, hipStream_t s);
 
 // kappa[0], kappa[1] (Montgomery, 2 x 32 B on device) = the X^(n-1) coefficients of the interpolants of the VALUES a = sc.abc[0..n), b = sc.abc[n..2n):
 // sum_i x_i c_i with the barycentric weights c_i = (-1)^(n-1-i) / (i! (n-1-i)!) -- after either frstage_eval form.  d_partials: 2 * LEAD_BLOCKS Fr of

@@ -592,6 +592,19 @@ int frstage_init_lagrange(FrStage& f, hipStream_t s) {
     f.lagrange = true;
     return ZK_OK;
 }
+// The extrapolation of the Lagrange-form stage on its own: the VALUES x_i on the points 0..n-1 (Montgomery, n >= 2) -> the barycentric sums
+// S_j = sum_i x_i c_i / (j - i) at d_buf[j] for j = n .. 2n-2 (d_buf: S elements, the rest of it scratch); the interpolant's value at j is Z(j) S_j,
+// Z(n + t) = f.zt[t].  frstage_eval_lagrange runs it on L w, R w and O w; the Lagrange-form key check (key_check.hip) on its coefficients pi.  Works in
+// sc.rns_a where the residue number system is on.  Enqueues only.
+int frstage_extrapolate(const FrStage& f, FrScratch& sc, const void* d_values, void* d_buf, hipStream_t s) {
+    const uint32_t n = f.n, S = f.S;
+    if (!f.lagrange || n < 2) ZK_FAIL(ZK_ERR_ARG, "frstage_extrapolate: tables not initialised");
+    hipLaunchKernelGGL(k_lag_scale, g1d(S), dim3(256), 0, s, (uint32_t*)d_buf, (const uint32_t*)d_values, (const uint32_t*)FRP(f.invfact), n, (uint64_t)S);
+    if (f.rns_ok && f.g_rns.p && rns_enabled())          // only the values at n .. 2n-2 are read
+        ZKCHK(rns_conv_table(sc.rns_a, d_buf, S, f.log_S, RNS_IN_PLAIN, f.g_rns, (uint64_t)S - 1, (void*)((uint32_t*)d_buf + 8 * (uint64_t)n), RNS_OUT_RANGE, (uint64_t)n, (uint64_t)n - 1, 0, s));
+    else ZKCHK(ntt_mul_table(d_buf, S, f.log_S, f.g_ntt.p, (uint64_t)S - 1, true, nullptr, nullptr, s));
+    return ZK_OK;
+}
 int frstage_eval_lagrange(const FrStage& f, FrScratch& sc, const void* d_wit_canon, hipStream_t s) {
     HIPCHK(hipGetLastError());
     if (!f.lagrange) ZK_FAIL(ZK_ERR_ARG, "frstage_eval_lagrange: tables not initialised");
@@ -614,12 +627,7 @@ int frstage_eval_lagrange(const FrStage& f, FrScratch& sc, const void* d_wit_can
         ScopedTimer t("fr_extrapolate", s);
         const uint32_t* src[3] = {a, b, cc};
         void* dst[3] = {sc.bufA.p, (void*)(FRP(sc.bufA) + 8 * (uint64_t)S), sc.tmp.p};
-        for (int k = 0; k < 3; k++) {
-            hipLaunchKernelGGL(k_lag_scale, g1d(S), dim3(256), 0, s, (uint32_t*)dst[k], src[k], (const uint32_t*)FRP(f.invfact), n, (uint64_t)S);
-            if (f.rns_ok && f.g_rns.p && rns_enabled())          // only the values at n .. 2n-2 are read (k_lag_h)
-                ZKCHK(rns_conv_table(sc.rns_a, dst[k], S, f.log_S, RNS_IN_PLAIN, f.g_rns, (uint64_t)S - 1, (void*)((uint32_t*)dst[k] + 8 * (uint64_t)n), RNS_OUT_RANGE, (uint64_t)n, (uint64_t)n - 1, 0, s));
-            else ZKCHK(ntt_mul_table(dst[k], S, f.log_S, f.g_ntt.p, (uint64_t)S - 1, true, nullptr, nullptr, s));
-        }
+        for (int k = 0; k < 3; k++) ZKCHK(frstage_extrapolate(f, sc, src[k], dst[k], s));
         hipLaunchKernelGGL(k_lag_h, g1d(n), dim3(256), 0, s, FRP(sc.h), (const uint32_t*)FRP(sc.bufA), (const uint32_t*)(FRP(sc.bufA) + 8 * (uint64_t)S),
                            (const uint32_t*)FRP(sc.tmp), (const uint32_t*)FRP(f.zt), n);
     }

@@ -564,6 +564,26 @@ int zk_groth16_key_check(uint64_t handle, const uint8_t* vk_g1, size_t n_io, con
         ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check: the key was uploaded under ZK_KEY_SUBGROUP_CHECK=0; pairing relations mean nothing outside the subgroup");
     return groth16_key_check(k, vk_g1, n_io, vk_g2, seed, failed);
 }
+// The same for a handle in Lagrange form, whichever way it came by it (upload, compressed upload, keygen, derivation): other relations, the same refusals.
+int zk_groth16_key_check_lagrange(uint64_t handle, const uint8_t* vk_g1, size_t n_io, const uint8_t* vk_g2, const uint8_t seed[32], uint32_t* failed) {
+    if (!failed) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: null failed");
+    if (!vk_g1 != !vk_g2) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: vk_g1 and vk_g2 come together or not at all");
+    if (group_lookup(handle)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: multi-device keys are not checked; check the key on one device");
+    Groth16Key* kp = g_keys.find(handle);
+    if (!kp) {
+        ZKCHK(ensure_init());          // without a device no handle exists: say that, not that this one is unknown
+        ZK_FAIL(ZK_ERR_HANDLE, g_keys.unknown());
+    }
+    Groth16Key& k = *kp;
+    if (!k.lagrange) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: the handle holds the tau powers; that form is checked by zk_groth16_key_check");
+    if (k.world != 1) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: the key is a shard; the check needs the whole pools");
+    if ((vk_g1 || n_io) && n_io != (size_t)k.m - k.n_mid) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: n_io is not the number of variables outside mids");
+    for (uint32_t i = 0; i < MAX_SLOTS; i++)
+        if (k.slots[i] && k.slots[i]->busy) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: a proof is in flight on this key: call the matching _wait first");
+    if (!k.g1.in_subgroup || !k.g2.in_subgroup)
+        ZK_FAIL(ZK_ERR_ARG, "zk_groth16_key_check_lagrange: the key was uploaded under ZK_KEY_SUBGROUP_CHECK=0; pairing relations mean nothing outside the subgroup");
+    return groth16_key_check_lagrange(k, vk_g1, n_io, vk_g2, seed, failed);
+}
 int zk_groth16_pk_shard(uint64_t handle, uint32_t rank, uint32_t world) {
     Groth16Key* kp;
     ZKCHK(key_lookup(handle, &kp));

@@ -76,6 +76,8 @@ int groth16_derive_lagrange_pools(const FrStage& f, const uint8_t* d_g1, uint64_
 // key_check.hip: the whole of zk_groth16_key_check behind its argument checks (a tau-power key held whole on one device, no proof in flight); vk_g1 and
 // vk_g2 both given or both null; seed: 32 bytes or null (drawn here)
 int groth16_key_check(Groth16Key& k, const uint8_t* vk_g1, size_t n_io, const uint8_t* vk_g2, const uint8_t* seed, uint32_t* failed);
+// the same for zk_groth16_key_check_lagrange: a Lagrange-form key held whole on one device
+int groth16_key_check_lagrange(Groth16Key& k, const uint8_t* vk_g1, size_t n_io, const uint8_t* vk_g2, const uint8_t* seed, uint32_t* failed);
 void groth16_shard_range(uint64_t points, uint64_t heavy, uint32_t rank, uint32_t world, uint64_t* lo, uint64_t* hi);
 
 // ---- multi-device keys (groth16_multi.hip): one shard per entry of the device list behind ONE handle

@@ -559,21 +559,31 @@ class Groth16:
         os.urandom here, after the key's bytes are fixed.  A caller that passes its own takes over the contract of include/zkmi355x.h: unpredictable to
         whoever made the key.  With a vkey, vkey.ab is compared with e(a, b2) on the host and reported as "ab" (bit 31, a name of this wrapper: the
         library never sees ab).  Tau-power handles held whole on one device only."""
+        return self._key_check(_lib.lib().zk_groth16_key_check, "check_key", vkey, seed)
+
+    def check_lagrange_key(self, vkey=None, seed=None):
+        """check_key for a handle in Lagrange form -- Groth16(cs, pk, lagrange=True), generate(form="lagrange"), derive_lagrange(), or
+        from_compressed(..., lagrange=True) of pools read back from a key cache: bytes from somewhere else until they are checked
+        (zk_groth16_key_check_lagrange: the relations on values, no derivation, no basis conversion).  The same KeyCheck with the same names, the same
+        seed contract and the same "ab" bit; a tau-power handle is refused (check_key is its call)."""
+        return self._key_check(_lib.lib().zk_groth16_key_check_lagrange, "check_lagrange_key", vkey, seed)
+
+    def _key_check(self, fn, what, vkey, seed):
         import os
         seed = os.urandom(32) if seed is None else bytes(seed)
         if len(seed) != 32:
-            raise ValueError("check_key: the seed is 32 bytes")
+            raise ValueError("%s: the seed is 32 bytes" % what)
         sd = np.frombuffer(seed, dtype=np.uint8)
         failed = C.c_uint32(0)
         if vkey is None:
-            _lib.check(_lib.lib().zk_groth16_key_check(self.handle, None, 0, None, _p(sd), C.byref(failed)))
+            _lib.check(fn(self.handle, None, 0, None, _p(sd), C.byref(failed)))
             return KeyCheck(failed.value)
         lt = np.ascontiguousarray(vkey.ltgm_io, dtype=np.uint8).reshape(-1)
         v1 = np.frombuffer(bytes(vkey.one1) + bytes(lt), dtype=np.uint8)
         v2 = np.frombuffer(bytes(vkey.one2) + bytes(vkey.gm) + bytes(vkey.d), dtype=np.uint8)
         if len(v1) % 96 or len(v1) < 96 or len(v2) != 576:
-            raise ValueError("check_key: the verification key is not (1 + n_io) * 96 and 3 * 192 bytes")
-        _lib.check_points(_lib.lib().zk_groth16_key_check(self.handle, _p(v1), len(v1) // 96 - 1, _p(v2), _p(sd), C.byref(failed)))
+            raise ValueError("%s: the verification key is not (1 + n_io) * 96 and 3 * 192 bytes" % what)
+        _lib.check_points(fn(self.handle, _p(v1), len(v1) // 96 - 1, _p(v2), _p(sd), C.byref(failed)))
         mask = failed.value
         a, b2 = self._alpha_beta()
         if bytes(vkey.ab) != bytes(Pairing.pairing(a, b2)):
