@@ -9,6 +9,8 @@ index violates its relation.  A pairing equation e(P, Q) = e(R, S) between subgr
 What the relation L needs of a polynomial u_k is <e, u_k> = sum_j (u_k)_j e[j] for an exponent list e (ti1 or ti2, whatever they hold).  With the
 Lagrange basis l_g of 0..n-1, u_k = sum_g M[g][k] l_g, so <e, u_k> = sum_g M[g][k] <e, l_g>: `basis_dots` interpolates in big integers -- every l_g by
 synthetic division of Z, O(n^2) -- and the columns are sparse sums."""
+import functools
+
 from zukelang_amd.r1cs import FR_MODULUS as P
 
 GENERATORS, TAU_G1, TAU_G2, BETA, DELTA, H_BASES, L, GAMMA = 1, 2, 4, 8, 16, 32, 64, 128
@@ -17,6 +19,11 @@ NAMES = {GENERATORS: "generators", TAU_G1: "tau_g1", TAU_G2: "tau_g2", BETA: "be
 
 def z_coeffs(n):
     """Z = prod_{i<n} (X - i), n + 1 coefficients, lowest first"""
+    return list(_z_coeffs(n))
+
+
+@functools.lru_cache(maxsize=8)
+def _z_coeffs(n):
     z = [1]
     for i in range(n):
         nz = [0] * (len(z) + 1)
@@ -24,12 +31,17 @@ def z_coeffs(n):
             nz[j + 1] = (nz[j + 1] + c) % P
             nz[j] = (nz[j] - i * c) % P
         z = nz
-    return z
+    return tuple(z)
 
 
 def basis_dots(n, e):
-    """[<e[0..n), l_g> for g < n]: l_g = c_g Z / (X - g), c_g = 1 / prod_{i != g} (g - i)"""
-    z = z_coeffs(n)
+    """[<e[0..n), l_g> for g < n]: l_g = c_g Z / (X - g), c_g = 1 / prod_{i != g} (g - i).  Crafted keys that leave a tau basis alone share its pass."""
+    return list(_basis_dots(n, tuple(e[:n])))
+
+
+@functools.lru_cache(maxsize=16)
+def _basis_dots(n, e):
+    z = _z_coeffs(n)
     fact = [1] * n
     for i in range(1, n):
         fact[i] = fact[i - 1] * i % P
@@ -44,7 +56,7 @@ def basis_dots(n, e):
         if (n - 1 - g) & 1:
             den = P - den
         out.append(acc * pow(den, P - 2, P) % P)
-    return out
+    return tuple(out)
 
 
 def _entries(M):

@@ -2,7 +2,8 @@
 
 include/zkmi355x.h (zk_set_option) promises that no public knob changes a result.  CASES has one row per public name: the values to exercise (every
 branch its parse site tells apart), where the library reads it, and the companion settings a value needs to reach its branch.  tests/test_option_cases.py
-(CPU) keeps the table equal to PUBLIC_OPTIONS and the `read` column equal to the read sites; tests/test_gpu_options.py (GPU) runs it.
+(CPU) keeps the table equal to PUBLIC_OPTIONS and the `read` column equal to the read sites; tests/test_gpu_options.py (GPU) runs it.  ROUTES, further
+down, has one row per way to make a handle: tests/test_gpu_options_routes.py (GPU) runs CASES through every one of them.
 
 read:
   "cached" -- a function-local static (ZK_ENV, or `static const ... = ::zk::opt(...)`): fixed at first use, so only a fresh process reaches another value
@@ -74,6 +75,67 @@ CACHED_GROUPS = [
     {"ZK_SLOT_STREAMS": "1", "ZK_MSM_TARGET_THREADS": "4096", "ZK_MSM_CHUNK_MIN": "64", "ZK_SORT_MIN_WGS": "64"},
     {"ZK_SERIAL_STREAMS": "1", "ZK_SORT_SCALAR_MAJOR": "0"},
 ]
+
+
+# ---- the routes to a handle.  CASES above says WHICH settings to run; ROUTES says THROUGH WHAT.  tests/test_gpu_options.py is the first route
+# (PROVE_ROUTE: uncompressed upload, derivation, prove / prove_async); tests/test_gpu_options_routes.py runs every live setting, every cached group
+# and the named interactions through each row below.  What is expected never comes from the library at its default options: proofs from the trapdoor
+# oracles, sums from the oracle's naive fold, masks from the integer models, key bytes from the host keygen (itself held to the oracle's setup).
+#
+# entry:   the C entry points of include/zkmi355x.h the row ANSWERS FOR: each name stands in one row only, so a deleted row leaves its names
+#          uncovered (tests/test_option_cases.py: every key, proving, pool and resident-MSM call of the header is in a row, in PROVE_ROUTE or in
+#          EXEMPT).  Every proving route also runs zk_*_prove and zk_*_prove_many_compressed on its handle
+# with_ba: companions added to the rows of size "ba" -- the route's key has a size of its own, and the automatic batch-affine rounds need a mean of
+#          8 entries per bucket (msm.hip: ba_rounds_for); test_option_cases.py does the arithmetic
+# multi:   what a row with multi=True asks of the route on the device list [0, 0]: "proofs" -- the single-device bytes; "bytes" -- zk_*_keygen
+#          gives no handle on a device list (ZK_ERR_ARG), the key bytes are still keygen's; None -- not run (key checks refuse such handles, resident
+#          bases live on the list's first device: both tested where those calls are)
+Route = namedtuple("Route", "entry protocol with_ba multi")
+
+PROVE_ROUTE = ("zk_groth16_pk_upload", "zk_groth16_prove", "zk_groth16_prove_async", "zk_groth16_prove_wait",
+               "zk_pinocchio_pk_upload", "zk_pinocchio_prove", "zk_pinocchio_prove_async", "zk_pinocchio_prove_wait")
+
+ROUTES = {
+    "g16_wire": Route(("zk_groth16_pk_upload_compressed", "zk_groth16_prove_many_compressed"), "groth16", {}, "proofs"),
+    "g16_generated": Route(("zk_groth16_keygen", "zk_groth16_pool_points"), "groth16", {}, "bytes"),
+    # the pools of a derived handle out in wire form, in again as a Lagrange-form key (what a key cache does)
+    "g16_cached_lagrange": Route(("zk_groth16_pool_points_compressed",), "groth16", {}, None),
+    # the n1025 circuit of tests/test_gpu_key_check.py (KEY_CHECK_POOLS); the Lagrange-form keys go up through zk_groth16_pk_upload_lagrange
+    "g16_key_check": Route(("zk_groth16_key_check", "zk_groth16_key_check_lagrange", "zk_groth16_pk_upload_lagrange"), "groth16", {"ZK_MSM_WINDOW": "8"}, None),
+    "pin_wire": Route(("zk_pinocchio_pk_upload_compressed", "zk_pinocchio_pool_points_compressed", "zk_pinocchio_prove_many_compressed"), "pinocchio", {}, "proofs"),
+    "pin_generated": Route(("zk_pinocchio_keygen",), "pinocchio", {}, "bytes"),
+    "pin_lagrange": Route(("zk_pinocchio_pk_upload_lagrange", "zk_pinocchio_pool_points"), "pinocchio", {}, None),
+    "resident": Route(("zk_bases_upload", "zk_bases_upload_compressed", "zk_msm_resident", "zk_msm_resident_many"), "msm", {}, None),
+}
+
+# which entry points of the header the table must account for, and the ones it leaves out on purpose
+ROUTED_WORDS = ("prove", "pk_upload", "keygen", "key_check", "msm_resident", "bases_upload", "pool_points")
+EXEMPT = {
+    "zk_groth16_pk_upload_sharded": "a device list builds its shards through the same code: the multi rows of both option modules",
+    "zk_groth16_prove_partial": "a shard's half of a proof: what a multi-device handle runs per device (multi rows)",
+    "zk_groth16_prove_partial_async": "as zk_groth16_prove_partial (multi rows)",
+    "zk_groth16_prove_partial_wait": "as zk_groth16_prove_partial (multi rows)",
+    "zk_groth16_prove_partial_wait_device": "as zk_groth16_prove_partial, the sums left on the device (tests/test_gpu_groth16.py)",
+}
+# the verifiers have no row because they read no option: test_option_cases.py holds that to their sources
+VERIFIER_SOURCES = ("pairing_dev.hip", "verify_resident.hip", "pairing_host.hip")
+
+# the pools of the key-check route's key, per form: what ba_rounds_for sees
+KEY_CHECK_POOLS = {"tau_powers": (3089, 1029), "lagrange": (3087, 1027)}
+
+# the named interactions of tests/test_gpu_options_routes.py: a handle meets setting A, then setting B, in both directions
+FLIPS = {
+    "ba_rounds": {"ZK_MSM_BA_ROUNDS": "2"},
+    "window5": {"ZK_MSM_WINDOW": "5"},
+    "window17": {"ZK_MSM_WINDOW": "17"},
+    "two_level16": {"ZK_MSM_WINDOW": "16", "ZK_SORT_TWO_LEVEL_MIN": "10"},
+}
+
+
+def route_settings(route, c, settings):
+    """the settings of a live run as the route runs them: its companions for the row's size, never over what the row itself sets"""
+    extra = ROUTES[route].with_ba if c.size == "ba" else {}
+    return dict(extra, **settings)
 
 
 def live_runs():
