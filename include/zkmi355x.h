@@ -79,7 +79,15 @@ int zk_set_devices(uint64_t mask);
  * ("msm_window", "ZK_MSM_WINDOW"); value = the string the variable would hold; value == NULL hands the knob back to the environment.  An option set
  * here wins over the environment.  Knobs are read when a key is uploaded or at the first proof and cached: set options BEFORE the first key upload.
  * Unknown names -> ZK_ERR_ARG.  None changes a result (the one that changes a precondition, key_subgroup_check = 0, also switches off the folded
- * windows that rely on it). */
+ * windows that rely on it).
+ * ZK_GRAPH=1 captures each slot's proof once into a hipGraph and replays it, so the device pointers a proof reads are frozen at the first proof of the
+ * slot.  Some of them point at tables that belong to the device, not to the key, and that grow when a later call needs more of them (a larger key
+ * of either protocol, zk_fr_ntt or zk_fr_poly_mul at a larger size): the twiddle tables of the Fr stage.  The rule for those, with or without graphs:
+ *   a device pointer to a table of the device, once handed to an enqueue or a capture, stays valid and keeps its values until zk_shutdown.
+ * A table that grows is replaced for later calls and kept for earlier ones (each growth at least doubles it, so all old tables together cost less
+ * than the current one); nothing is released before zk_shutdown.  Hence any call may be made while ANOTHER handle has proofs in flight or graphs
+ * captured -- uploads, frees, zk_fr_*, zk_msm_*, key checks, verification; the restrictions stated with the single calls concern the slots of the
+ * handle they are called on. */
 int zk_set_option(const char* name, const char* value);
 int zk_set_device_list(const int32_t* devices, uint32_t count);
 int zk_get_device_list(int32_t* devices /* may be NULL */, uint32_t capacity, uint32_t* count);

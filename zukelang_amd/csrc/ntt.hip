@@ -190,33 +190,53 @@ __global__ void k_fr_to_factor(uint32_t* buf, uint64_t n) {
 
 // The twiddle tables live in the CONTEXT of the device they were generated on (zk_common.h: CtxBufs; contexts are heap-allocated and never destroyed
 // by static destructors, which must not call into a HIP runtime that is already gone).
+//
+// The heaps GROW when a call needs more levels than they hold (a larger key of either protocol, zk_fr_ntt or zk_fr_poly_mul at a larger size), while
+// kernels of other keys may be queued with the old pointers and captured graphs (ZK_GRAPH=1) hold them for good: the old heaps are retired, not freed
+// (ctx_tables.h has the rule; a heap's levels do not depend on its size, so old and new agree on every level the old one has).  Nothing is released
+// before zk_shutdown.  The new heaps are complete before this returns, so a caller may read them on any stream.
 int ntt_ensure_twiddles(uint32_t log_n) {
     Ctx& c = ctx();
     if (log_n > 30) ZK_FAIL(ZK_ERR_ARG, "NTT size above 2^30 is not supported");
     if (!c.bufs) ZK_FAIL(ZK_ERR_HIP, "ntt: no device context (zk_init)");
-    DevBuf &g_tw_fwd = c.bufs->tw_fwd, &g_tw_inv = c.bufs->tw_inv, &g_inv_pow2 = c.bufs->inv_pow2;
+    GrowingTable &g_tw_fwd = c.bufs->tw_fwd, &g_tw_inv = c.bufs->tw_inv;
+    DevBuf& g_inv_pow2 = c.bufs->inv_pow2;
+    if (g_inv_pow2.p && c.tw_fwd && c.tw_log >= log_n) return ZK_OK;          // every call under stream capture ends here: the key's upload grew the heaps
     if (!g_inv_pow2.p) {
         ZKCHK(g_inv_pow2.alloc(66 * 32));
         hipLaunchKernelGGL(k_gen_inv_pow2, dim3(1), dim3(64), 0, c.stream, g_inv_pow2.as<uint32_t>());
         HIPCHK(hipGetLastError());
     }
-    if (c.tw_log >= log_n && c.tw_fwd) return ZK_OK;
-    uint32_t k = log_n < 12 ? 12 : log_n;
+    if (!(c.tw_log >= log_n && c.tw_fwd)) {
+        const uint32_t k = ctx_table_log_cap(log_n, 12);
+        // Nothing is freed here, so nothing in flight has to end first; the wait keeps a growth (rare: set-up calls only) a point at which the device is
+        // idle, as it is in rns_ntt.hip, instead of relying on what hipMalloc happens to wait for.
+        HIPCHK(hipDeviceSynchronize());
+        // when the second allocation fails the context keeps its old pair (c.tw_* below is not reached); the next call grows what is behind and fills both
+        if (!g_tw_fwd.covers(k)) ZKCHK(g_tw_fwd.grow(k, ((size_t)32) << k, device_table_alloc));
+        if (!g_tw_inv.covers(k)) ZKCHK(g_tw_inv.grow(k, ((size_t)32) << k, device_table_alloc));
+        ctx_table_trace("Fr twiddle heaps", c.tw_log, k, g_tw_fwd.retired());
+        int inverse = 0;
+        for (GrowingTable* t : {&g_tw_fwd, &g_tw_inv}) {          // each heap whole, at its own size (they differ only after such a failure)
+            const uint64_t total = (uint64_t)1 << t->log_cap();
+            hipLaunchKernelGGL(k_gen_twiddles, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.stream, (uint32_t*)t->live(), t->log_cap(), inverse++);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    // generated on c.stream, read on whatever stream the caller passes (a slot's, a resident handle's): complete before anybody has the pointers
     HIPCHK(hipStreamSynchronize(c.stream));
-    ZKCHK(g_tw_fwd.alloc(((size_t)32) << k));
-    ZKCHK(g_tw_inv.alloc(((size_t)32) << k));
-    uint64_t total = (uint64_t)1 << k;
-    dim3 grid((unsigned)((total + 255) / 256));
-    hipLaunchKernelGGL(k_gen_twiddles, grid, dim3(256), 0, c.stream, g_tw_fwd.as<uint32_t>(), k, 0);
-    hipLaunchKernelGGL(k_gen_twiddles, grid, dim3(256), 0, c.stream, g_tw_inv.as<uint32_t>(), k, 1);
-    HIPCHK(hipGetLastError());
-    c.tw_fwd = g_tw_fwd.p;
-    c.tw_inv = g_tw_inv.p;
-    c.tw_log = k;
+    c.tw_fwd = g_tw_fwd.live();
+    c.tw_inv = g_tw_inv.live();
+    c.tw_log = g_tw_fwd.log_cap() < g_tw_inv.log_cap() ? g_tw_fwd.log_cap() : g_tw_inv.log_cap();
     return ZK_OK;
 }
-static void ntt_release() {          // zk_shutdown, once per context (current): the buffers themselves die with the context's CtxBufs
-    ctx().tw_fwd = ctx().tw_inv = nullptr; ctx().tw_log = 0;
+static void ntt_release() {          // zk_shutdown, once per context (current), the device idle: every heap the context ever had, live and retired
+    Ctx& c = ctx();
+    if (c.bufs) {
+        c.bufs->tw_fwd.release_all(device_table_free);
+        c.bufs->tw_inv.release_all(device_table_free);
+    }
+    c.tw_fwd = c.tw_inv = nullptr; c.tw_log = 0;
 }
 static CleanupRegistrar g_ntt_cleanup(ntt_release);
 

@@ -56,14 +56,18 @@ __global__ void k_rns_gen_tw(uint32_t* __restrict__ tw, uint32_t log_cap) {
     }
     tw[(uint64_t)i * cap + t] = acc;
 }
+// The heap grows like the Fr twiddle heaps of ntt.hip and under the same rule (ctx_tables.h): the old one is retired, not freed -- a proof of another
+// key in flight reads it, and a captured graph (ZK_GRAPH=1) holds its pointer TOGETHER WITH its log_cap (the stride between the primes' heaps), so an
+// old heap must also keep its layout.  `ready` is the capacity whose heap has been generated: callers are handed the live pointer only with it.
 struct RnsTw {
-    DevBuf buf;
-    uint32_t log_cap = 0;
+    GrowingTable buf;
+    uint32_t ready = 0;
 };
 static RnsTw* g_rns_tw[64];          // per virtual device (contexts are never destroyed by static destructors; released in zk_shutdown)
-static void rns_release() {
+static void rns_release() {          // zk_shutdown, once per context (current), the device idle: the live heap and every retired one
     const int v = ctx().vdev;
     if (v >= 0 && v < 64 && g_rns_tw[v]) {
+        g_rns_tw[v]->buf.release_all(device_table_free);
         delete g_rns_tw[v];
         g_rns_tw[v] = nullptr;
     }
@@ -75,20 +79,22 @@ int rns_ensure_twiddles(uint32_t log_len) {
     if (c.vdev < 0 || c.vdev >= 64) ZK_FAIL(ZK_ERR_ARG, "rns: no device context");
     if (!g_rns_tw[c.vdev]) g_rns_tw[c.vdev] = new RnsTw;
     RnsTw& t = *g_rns_tw[c.vdev];
-    if (t.log_cap >= log_len && t.buf.p) return ZK_OK;
-    const uint32_t k = log_len < 14 ? 14 : log_len;
-    HIPCHK(hipDeviceSynchronize());          // a proof in flight may still read the old heap
-    ZKCHK(t.buf.alloc(4 * (size_t)RNS_PRIMES << k));
-    hipLaunchKernelGGL(k_rns_gen_tw, dim3((unsigned)(((uint64_t)1 << k) / 256), RNS_PRIMES), dim3(256), 0, c.stream, t.buf.as<uint32_t>(), k);
+    if (t.ready >= log_len && t.buf.covers(log_len)) return ZK_OK;          // every call under stream capture ends here: the key's upload grew the heap
+    const uint32_t k = ctx_table_log_cap(log_len, 14);
+    HIPCHK(hipDeviceSynchronize());          // nothing is freed; a growth stays a point at which the device is idle (ntt.hip)
+    if (!t.buf.covers(k)) ZKCHK(t.buf.grow(k, 4 * (size_t)RNS_PRIMES << k, device_table_alloc));
+    const uint32_t cap = t.buf.log_cap();
+    ctx_table_trace("residue-system twiddle heap", t.ready, cap, t.buf.retired());
+    hipLaunchKernelGGL(k_rns_gen_tw, dim3((unsigned)(((uint64_t)1 << cap) / 256), RNS_PRIMES), dim3(256), 0, c.stream, (uint32_t*)t.buf.live(), cap);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c.stream));
-    t.log_cap = k;
+    HIPCHK(hipStreamSynchronize(c.stream));          // generated on c.stream, read on the caller's: complete before anybody has the pointer
+    t.ready = cap;
     return ZK_OK;
 }
 static const uint32_t* rns_tw(uint32_t* log_cap) {
     RnsTw& t = *g_rns_tw[ctx().vdev];
-    *log_cap = t.log_cap;
-    return t.buf.as<uint32_t>();
+    *log_cap = t.ready;
+    return (const uint32_t*)t.buf.live();
 }
 
 // ---- Fr -> residues

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/zkmi355x.h"
+#include "ctx_tables.h"
 #include "zk_err.h"
 
 namespace zk {
@@ -90,9 +91,20 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-// per-context device tables (released by the owning translation unit's cleanup hook)
+// what a GrowingTable of device memory is handed (ctx_tables.h takes its allocator and deallocator as arguments: it is host-only)
+static inline int device_table_alloc(size_t bytes, void** p) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) return set_error(ZK_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+    return ZK_OK;
+}
+static inline void device_table_free(void* p) { (void)hipFree(p); }
+
+// per-context device tables (released by the owning translation unit's cleanup hook, or with the context).  A table that can be REPLACED after its
+// first use is a GrowingTable (ctx_tables.h: the old buffer is retired, never freed before zk_shutdown -- a proof in flight or a captured graph may hold
+// its pointer); a DevBuf here is allocated once per context and keeps its pointer.  tests/test_ctx_tables.py holds the list of both.
 struct CtxBufs {
-    DevBuf tw_fwd, tw_inv, inv_pow2;      // ntt.hip
+    GrowingTable tw_fwd, tw_inv;          // ntt.hip: the Fr twiddle heaps (floor 2^12)
+    DevBuf inv_pow2;                      // ntt.hip: the scale factors, 66 elements, filled once
     DevBuf pow2[2];                       // msm.hip: 2^k * generator, both curves (fixed_base_mul)
 };
 
