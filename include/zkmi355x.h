@@ -374,6 +374,31 @@ int zk_groth16_key_check(uint64_t handle, const uint8_t* vk_g1 /* one1 | ltgm_io
 int zk_groth16_key_check_lagrange(uint64_t handle, const uint8_t* vk_g1 /* one1 | ltgm_io, may be NULL */, size_t n_io,
                                   const uint8_t* vk_g2 /* one2 | gm | d, may be NULL */,
                                   const uint8_t seed[32] /* may be NULL */, uint32_t* failed /* bit mask, 0 = well formed */);
+/* ---- a delta contribution to a resident key ----------------------------------------------------------------------------------------------------
+ * The checks above tell a host that a key is well formed; they cannot tell it that whoever made the key has forgotten delta.  The usual remedy is a
+ * phase-2 contribution: a party multiplies delta by a secret delta', and the key is sound if ONE party forgets its factor.  Of a key (groth16.ml:45-108)
+ * only d1, d2 (delta), tiztd[i] or hl[t], ltd_mid[k] (1 / delta) and vkey.d (= d2) depend on delta.  This call changes, in place on the device:
+ *   g1[1] = d1 and g2[1] = d2    <- delta' times the point
+ *   the tail of the G1 pool       <- 1 / delta' mod r times every point:  tiztd[n-1] | ltd_mid[|mids|], in Lagrange form hl[n-1] | ltd_mid
+ * and nothing else.  The window tables of both pools are built again from the points on the device, the way zk_groth16_keygen and
+ * zk_groth16_pk_install_lagrange build them: no host round trip, no decoding, no subgroup test -- a multiple of a subgroup point is in the subgroup; a
+ * ZK_KEY_SUBGROUP_CHECK=0 origin is inherited as it stands.  The identity stays the identity.  The handle is unchanged until the new pools and tables
+ * are complete; then they replace the old ones, and every slot of the handle (its workspaces, under ZK_GRAPH its captured proofs) is dropped and built
+ * again at its next use: a proof on a slot used before the call comes out under the NEW key.  Afterwards the handle cannot be told apart from one
+ * uploaded from the contributed key's bytes: pool bytes, proofs on every entry point, a later derivation, both key checks, zk_groth16_pk_shard.
+ *   dmul: delta', canonical Fr bytes.  link_g1: d1 before | d1 after.  dmul_g2: [delta']_2.  vk_d: d2 after, the d of the new verification key (ab and
+ *     ltgm_io do not depend on delta).  A link shows e(d1 after, g2) = e(d1 before, [delta']_2): the RATIO of two delta.  A ceremony's transcript hash
+ *     and its proof of knowledge of delta' are the caller's protocol.
+ *   Before the device is touched: null dmul -> ZK_ERR_ARG; delta' = 0 -> ZK_ERR_ARG (the reference divides by delta); delta' >= r ->
+ *     ZK_ERR_SCALAR_RANGE.  An unknown or freed handle, a Pinocchio handle -> ZK_ERR_HANDLE (without a GPU: ZK_ERR_HIP).  A shard, a multi-device
+ *     handle, a handle with a proof in flight -> ZK_ERR_ARG.  After any refusal the handle proves exactly as before.
+ * The multiplications run on the kernels of the Lagrange derivation (csrc/lagrange_derive.hip: k_aff_to_raw, k_g_tabmul, k_raw_to_aff) over a table of
+ * equal scalars (csrc/contribute.hip); a kernel of its own was built, measured against them and dropped (profiles/contribute_kernel_ab.json).
+ * Timer family contribute. */
+int zk_groth16_pk_contribute(uint64_t handle, const uint8_t dmul[32] /* delta', canonical Fr bytes */,
+                             uint8_t link_g1[2 * 96]   /* d1 before | d1 after, may be NULL */,
+                             uint8_t dmul_g2[192]      /* [delta']_2, may be NULL */,
+                             uint8_t vk_d[192]         /* d2 after = the new vkey.d, may be NULL */);
 int zk_groth16_pk_free(uint64_t handle);
 
 /* Groth16.prove rng qap pkey sol with r, s supplied by the caller in the order the reference
@@ -815,6 +840,11 @@ int zk_selftest_proof_wire(int group, const uint8_t* affine /* n * 96 | 192 */, 
  * A null pointer, n = 0, an unknown group / form / rep, a coordinate >= p, an identity b where the form excludes it -> ZK_ERR_ARG; a scalar >= r ->
  * ZK_ERR_SCALAR_RANGE; all before the device is touched. */
 int zk_selftest_group(int group, int form, int rep, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
+/* The tail of zk_groth16_pk_contribute on a caller's list (tests/test_gpu_contribute.py): out[i] = k pts[i] for n uncompressed G1 points (the identity as
+ * the library encodes it, or all zeros; it stays the identity) and ONE canonical scalar k of 32 B, little-endian (0 is served: every product is the
+ * identity).  slab: points per chain of launches, 0 = the call's default of 2^18, so that a list of a few hundred points can cross a slab boundary.  A
+ * null pointer, n = 0 or k >= r -> ZK_ERR_ARG before the device is touched; a coordinate >= p -> ZK_ERR_ARG, a point off the curve -> ZK_ERR_NOT_ON_CURVE. */
+int zk_selftest_g1_scale(const uint8_t* pts /* n * 96 */, size_t n, const uint8_t k[32], uint32_t slab /* 0 = default */, uint8_t* out /* n * 96 */);
 /* zk_groth16_verify_folded stopped before the comparison (tests/test_gpu_verify_folded.py): both sides of the folded equation as GT encodings --
  * lhs_gt the final exponentiation of the product of the count + 2 Miller values, rhs_gt = ab^S -- and the two sums that enter the key's pairs,
  * sum_c = sum_i [rho_i] C_i and sum_io = sum_k t_k ltgm_io_k, un-negated, uncompressed (the identity as the library encodes it).  Same arguments and

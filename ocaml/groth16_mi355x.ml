@@ -299,6 +299,14 @@ module Make (C : Curve.S) = struct
     let vk = vk_bytes vkey in
     key_check_names ?vkey pkey (Mi355x.groth16_key_check_lagrange ?vk ?seed h)
 
+  (* ---------------------------------------------------------------- contribute
+     A phase-2 contribution on the device (zk_groth16_pk_contribute): delta <- delta dmul for the key the handle of (qap, pkey) holds -- d1, d2 times
+     dmul, tiztd (or hl) and ltd_mid times 1 / dmul, new window tables, no host round trip.  Returns (d1 before | d1 after, [dmul]_2, d2 after), uncompressed:
+     the link between the two keys and the d of the new verification key (ab and ltgm_io stay).  From here on the handle holds the CONTRIBUTED key, not
+     pkey: proofs come out under it, and its bytes are read back through the pool calls (Mi355x.pool_points_compressed). *)
+  let contribute (qap : qap) (pkey : pkey) ~(dmul : Fr.t) : bytes * bytes * bytes =
+    Mi355x.groth16_pk_contribute (handle_of qap pkey) ~dmul:(Fr.to_bytes dmul)
+
   (* ---------------------------------------------------------------- verify
      e(A, B) = ab + e(sum_k w_k [L_k(tau)/gamma]_1, gamma) + e(C, delta), GT written additively as Curve.G has it.  The sum
      runs over the public coefficients; domains must agree (G.dot). *)

@@ -501,6 +501,19 @@ let zk_groth16_key_check_lagrange =
 
 let groth16_key_check_lagrange ?vk ?seed (h : Unsigned.UInt64.t) : int = key_check_call zk_groth16_key_check_lagrange ?vk ?seed h
 
+(* A delta contribution to the resident key (include/zkmi355x.h, "a delta contribution to a resident key"): d1, d2 times delta', the tail of the G1 pool
+   times 1 / delta', new window tables, all on the device.  dmul: delta', 32 canonical bytes.  Returns (d1 before | d1 after, [delta']_2, d2 after): the
+   link of the two keys and the d of the new verification key, uncompressed. *)
+let zk_groth16_pk_contribute =
+  fn "zk_groth16_pk_contribute" (uint64_t @-> ptr char @-> ptr char @-> ptr char @-> ptr char @-> returning int)
+
+let groth16_pk_contribute (h : Unsigned.UInt64.t) ~(dmul : bytes) : bytes * bytes * bytes =
+  let d = carray_of_bytes dmul in
+  let link = CArray.make char 192 and dg2 = CArray.make char 192 and vkd = CArray.make char 192 in
+  check (zk_groth16_pk_contribute h (CArray.start d) (CArray.start link) (CArray.start dg2) (CArray.start vkd));
+  let out a = Bytes.init 192 (fun i -> CArray.get a i) in
+  (out link, out dg2, out vkd)
+
 let pinocchio_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in
   check

@@ -35,6 +35,7 @@ EXPORTS = [
     "zk_groth16_pk_upload_compressed", "zk_pinocchio_pk_upload_compressed", "zk_bases_upload_compressed", "zk_groth16_pool_points_compressed", "zk_pinocchio_pool_points_compressed",
     "zk_groth16_prove_many_compressed", "zk_pinocchio_prove_many_compressed", "zk_selftest_proof_wire",
     "zk_groth16_key_check", "zk_groth16_key_check_lagrange",
+    "zk_groth16_pk_contribute", "zk_selftest_g1_scale",
 ]
 
 
@@ -136,6 +137,11 @@ KEY_CHECK_PROTOTYPES = {
 KEY_CHECK_LAGRANGE_PROTOTYPES = {
     "zk_groth16_key_check_lagrange": [C.c_uint64, _P8, C.c_size_t, _P8, _P8, C.POINTER(C.c_uint32)],
 }
+# the delta contribution and its kernel's hook (tests/test_contribute_surface.py holds them to the header)
+CONTRIBUTE_PROTOTYPES = {
+    "zk_groth16_pk_contribute": [C.c_uint64, _P8, _P8, _P8, _P8],
+    "zk_selftest_g1_scale": [_P8, C.c_size_t, _P8, C.c_uint32, _P8],
+}
 # the bits of zk_groth16_key_check's mask (ZK_KEYCHK_*), in bit order, under the names Groth16.check_key reports
 KEYCHK_BITS = {
     "generators": 1, "tau_g1": 2, "tau_g2": 4, "beta": 8, "delta": 16, "h_bases": 32, "l": 64, "gamma": 128,
@@ -156,7 +162,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()) + list(KEY_CHECK_LAGRANGE_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()) + list(KEY_CHECK_LAGRANGE_PROTOTYPES.items()) + list(CONTRIBUTE_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

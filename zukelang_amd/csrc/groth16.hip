@@ -619,6 +619,81 @@ int zk_groth16_pk_shard(uint64_t handle, uint32_t rank, uint32_t world) {
     ZKCHK(groth16_slot_get(k, 0, &sl));
     return ZK_OK;
 }
+// A phase-2 contribution to the resident key (include/zkmi355x.h): delta <- delta delta'.  d1 and d2 are multiplied by delta', the tail of the G1 pool
+// (tiztd | ltd_mid, or hl | ltd_mid) by 1 / delta' (contribute.hip), and both pools get new window tables the way zk_groth16_pk_install_lagrange builds
+// them, from the points on the device.  Everything is built into temporaries; the handle changes only after the last launch has succeeded.
+int zk_groth16_pk_contribute(uint64_t handle, const uint8_t dmul[32], uint8_t link_g1[2 * 96], uint8_t dmul_g2[192], uint8_t vk_d[192]) {
+    if (!dmul) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_contribute: null dmul");
+    uint64_t dw[4], dinv[4];
+    cs_load(dw, dmul);
+    if (cs_is_zero(dw)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_contribute: delta' = 0 (the reference divides by delta)");
+    if (!cs_canonical(dw)) ZK_FAIL(ZK_ERR_SCALAR_RANGE, "zk_groth16_pk_contribute: delta' >= r");
+    if (group_lookup(handle)) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_contribute: multi-device keys take no contribution; contribute on one device");
+    Groth16Key* kp = g_keys.find(handle);
+    if (!kp) {
+        ZKCHK(ensure_init());          // without a device no handle exists: say that, not that this one is unknown
+        ZK_FAIL(ZK_ERR_HANDLE, g_keys.unknown());
+    }
+    Groth16Key& k = *kp;
+    if (k.world != 1) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_contribute: the key is a shard; a contribution needs the whole pools");
+    for (uint32_t i = 0; i < MAX_SLOTS; i++)
+        if (k.slots[i] && k.slots[i]->busy) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_contribute: a proof is in flight on this key: call the matching _wait first");
+    DeviceScope ds(k.vdev);
+    HIPCHK(hipDeviceSynchronize());
+    Ctx& c = ctx();
+    hipStream_t s = c.stream;
+    cs_fr_inv(dinv, dw);
+    const uint64_t nt = k.lagrange ? (uint64_t)k.n : (uint64_t)k.n + 2, tail = 3 + nt, tail_pts = k.p1 - tail;          // (n - 1) + |mids|
+    DevBuf n1, n2, dk, side1, side2, enc1, enc2;
+    ZKCHK(n1.alloc(96 * k.p1));
+    ZKCHK(n2.alloc(192 * k.p2));
+    ZKCHK(dk.alloc(32));
+    ZKCHK(side1.alloc(96 * 2));           // d1 before | d1 after
+    ZKCHK(side2.alloc(192 * 2));          // [delta']_2 | d2 after
+    ZKCHK(enc1.alloc(96 * 2));
+    ZKCHK(enc2.alloc(192 * 2));
+    uint8_t host1[2 * 96], host2[2 * 192];
+    // window 0 of the resident tables IS the key in pool order: back into the dense affine format
+    ZKCHK(msm_bases_dense(k.g1, 0, k.p1, n1.p, s));
+    ZKCHK(msm_bases_dense(k.g2, 0, k.p2, n2.p, s));
+    HIPCHK(hipMemcpyAsync(dk.p, dw, 32, hipMemcpyHostToDevice, s));
+    {
+        ScopedTimer tm("contribute", s);
+        HIPCHK(hipMemcpyAsync(side1.p, n1.as<uint8_t>() + 96, 96, hipMemcpyDeviceToDevice, s));
+        ZKCHK(points_scale_tabmul(CURVE_G1, n1.as<uint8_t>() + 96, n1.as<uint8_t>() + 96, dk.p, 1, s));
+        ZKCHK(points_scale_tabmul(CURVE_G2, n2.as<uint8_t>() + 192, n2.as<uint8_t>() + 192, dk.p, 1, s));
+        ZKCHK(fixed_base_mul(CURVE_G2, side2.p, dk.p, 1, s));
+        HIPCHK(hipMemcpyAsync(side1.as<uint8_t>() + 96, n1.as<uint8_t>() + 96, 96, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(side2.as<uint8_t>() + 192, n2.as<uint8_t>() + 192, 192, hipMemcpyDeviceToDevice, s));
+        ZKCHK(g1_scale_points(n1.as<uint8_t>() + 96 * tail, tail_pts, dinv, 0, s));
+    }
+    ZKCHK(points_affine_to_bytes(CURVE_G1, enc1.p, side1.p, 2, s));
+    ZKCHK(points_affine_to_bytes(CURVE_G2, enc2.p, side2.p, 2, s));
+    HIPCHK(hipMemcpyAsync(host1, enc1.p, sizeof host1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(host2, enc2.p, sizeof host2, hipMemcpyDeviceToHost, s));
+    // delta' is the contributor's secret: neither it nor its inverse stays behind, on the device or in this frame (the caller's copy is the caller's)
+    HIPCHK(hipMemsetAsync(dk.p, 0, 32, s));
+    for (volatile uint64_t* w : {(volatile uint64_t*)dw, (volatile uint64_t*)dinv})
+        for (int i = 0; i < 4; i++) w[i] = 0;
+    // a multiple of a subgroup point is in the subgroup: the origin of the key's points (checked, or uploaded under ZK_KEY_SUBGROUP_CHECK=0) is inherited
+    MsmBases g1, g2;
+    const uint32_t cw = key_window(k.hi1 - k.lo1, k.g1.in_subgroup);
+    ZKCHK(msm_bases_from_device_affine(g1, CURVE_G1, n1.p, k.p1, cw, true, s, k.g1.in_subgroup));
+    ZKCHK(msm_bases_from_device_affine(g2, CURVE_G2, n2.p, k.p2, cw, true, s, k.g2.in_subgroup));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    // ---- commit (nothing below can fail before the key is consistent again).  The slots go with the old tables: their workspaces, and under ZK_GRAPH
+    // their captured graphs, hold pointers into them; a slot is built again at its next use
+    for (uint32_t i = 0; i < MAX_SLOTS; i++) k.slots[i].reset();
+    k.g1 = std::move(g1);
+    k.g2 = std::move(g2);
+    if (link_g1) memcpy(link_g1, host1, sizeof host1);
+    if (dmul_g2) memcpy(dmul_g2, host2, 192);
+    if (vk_d) memcpy(vk_d, host2 + 192, 192);
+    Slot* sl;
+    ZKCHK(groth16_slot_get(k, 0, &sl));          // on failure the key is valid under the new delta; the slot is created at the next use
+    return ZK_OK;
+}
 int zk_groth16_pool_points(uint64_t handle, int group, uint8_t* out, size_t capacity_points, size_t* count) {
     if (GroupKey* g = group_lookup(handle)) return group_pool_points(*g, group, out, capacity_points, count);
     Groth16Key* k;

@@ -1,6 +1,7 @@
 // Internal interface of the Groth16 prover (groth16.hip) that the multi-device form (groth16_multi.hip) builds on: the key and slot records and the
 // two halves of a proof -- Fr stage -> scalar vectors, multi-scalar products over a slice of the pools -- as enqueue-only functions.
 #pragma once
+#include "contribute_scalar.h"
 #include "frstage.cuh"
 #include "msm.cuh"
 
@@ -73,6 +74,12 @@ int groth16_prove_finish(Slot& sl);          // waits for sl.done, frees the slo
 // replaces the key's pools by rank's slice of the complete Lagrange-form pools at d_g1 / d_g2 (device memory of the key's device) and flips its Fr stage
 int groth16_install_lagrange(Groth16Key& k, const void* d_g1, const void* d_g2, uint32_t rank, uint32_t world);
 int groth16_derive_lagrange_pools(const FrStage& f, const uint8_t* d_g1, uint64_t n_mid, const uint8_t* d_g2, uint8_t* out_g1, uint8_t* out_g2, uint32_t sets, hipStream_t s);   // lagrange_derive.hip
+// lagrange_derive.hip: dst[i] <- k[i] * src[i], dense affine points and canonical scalars on the device (dst may be src), through the derivation's three
+// passes k_aff_to_raw, k_g_tabmul, k_raw_to_aff; waits for the stream
+int points_scale_tabmul(Curve curve, void* d_dst, const void* d_src, const void* d_k, uint64_t n, hipStream_t s);
+// contribute.hip: pts[i] <- k * pts[i] in place for n dense affine G1 points (device) and ONE canonical scalar (little-endian words), through
+// points_scale_tabmul over a table of equal scalars, `slab` points per chain of launches (0 = the default); waits for the stream
+int g1_scale_points(void* d_pts, uint64_t n, const uint64_t k[4], uint32_t slab, hipStream_t s);
 // key_check.hip: the whole of zk_groth16_key_check behind its argument checks (a tau-power key held whole on one device, no proof in flight); vk_g1 and
 // vk_g2 both given or both null; seed: 32 bytes or null (drawn here)
 int groth16_key_check(Groth16Key& k, const uint8_t* vk_g1, size_t n_io, const uint8_t* vk_g2, const uint8_t* seed, uint32_t* failed);

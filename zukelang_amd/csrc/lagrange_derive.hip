@@ -662,6 +662,28 @@ int derive_shifted_bases_g1(const FrStage& f, const uint8_t* d_si, uint8_t* d_ou
     return derive_set<Fp>(tn, d_si, f.n - 1, d_out, s);
 }
 
+// dst[i] <- k[i] * src[i] for dense affine points (device; dst may be src), k: canonical scalars on the device, through the three passes of a
+// derivation's scaling step: k_aff_to_raw, k_g_tabmul, k_raw_to_aff.  What zk_groth16_pk_contribute multiplies with: d1 and d2 by delta', the tail of
+// the G1 pool by 1 / delta' (contribute.hip).
+template <class T> static int scale_affine_tabmul(uint8_t* d_dst, const uint8_t* d_src, const uint32_t* d_k, uint64_t n, hipStream_t s) {
+    constexpr size_t XB = RawLayout<T>::XYZZ;
+    constexpr uint32_t LP = LaneCount<T>::N;
+    DevBuf A, scr;
+    ZKCHK(A.alloc(XB * n));
+    ZKCHK(scr.alloc((size_t)16 * XB * (n < DERIVE_SLAB ? n : DERIVE_SLAB)));
+    hipLaunchKernelGGL(k_aff_to_raw<T>, g1d(n * LP), dim3(256), 0, s, A.as<uint8_t>(), d_src, n, n);
+    ZKCHK(g_tabmul<T>(A.as<uint8_t>(), d_k, n, scr.as<uint8_t>(), s));
+    hipLaunchKernelGGL(k_raw_to_aff<T>, g1d(n * LP, 128), dim3(128), 0, s, d_dst, (const uint8_t*)A.as<uint8_t>(), n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));          // the working arrays go with this frame
+    return ZK_OK;
+}
+int points_scale_tabmul(Curve curve, void* d_dst, const void* d_src, const void* d_k, uint64_t n, hipStream_t s) {
+    if (!n) return ZK_OK;
+    if (curve == CURVE_G1) return scale_affine_tabmul<Fp>((uint8_t*)d_dst, (const uint8_t*)d_src, (const uint32_t*)d_k, n, s);
+    return scale_affine_tabmul<Fp2H>((uint8_t*)d_dst, (const uint8_t*)d_src, (const uint32_t*)d_k, n, s);
+}
+
 // ------------------------------------------------------------------ zk_selftest_group, forms 13-16 (group_selftest.cuh)
 // One lane (G1) or lane pair (G2) per pair of operands.  An XYZZ operand becomes the Jacobian point (X ZZ, Y ZZZ, ZZ), as window_table_affine takes its
 // multiplicand; a Jacobian result leaves through jac_to_xyzz.  The scalar multiplication gets the 16 raw XYZZ points of scratch per multiplication

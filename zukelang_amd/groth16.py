@@ -177,6 +177,78 @@ class VKey:
         return ResidentVKey(h.value, n_io, lambda p: bytes(p.a) + bytes(p.b) + bytes(p.c), 384, "zk_groth16_verify_resident")
 
 
+    def with_delta(self, vk_d):
+        """The partner verification key of a key after Groth16.contribute: only d changes (vk_d, the contribution's d2 after); ab = e(alpha, beta) and
+        ltgm_io = [L_k(tau)/gamma]_1 do not depend on delta."""
+        vk_d = bytes(vk_d)
+        if len(vk_d) != 192:
+            raise ValueError("with_delta: d is one uncompressed G2 point of 192 bytes")
+        return VKey(self.one1, self.ltgm_io, self.one2, self.gm, vk_d, self.ab)
+
+
+@dataclass
+class Contribution:
+    """What Groth16.contribute returns (uncompressed points): d1 of the key before and after, [delta']_2, and d2 after -- the d of the new
+    verification key (VKey.with_delta).  (d1_before, d1_after, dmul_g2) is a link of verify_contributions."""
+    d1_before: bytes
+    d1_after: bytes
+    dmul_g2: bytes
+    vk_d: bytes
+
+
+# the generator of G2 as the library encodes points (imaginary part | real part, big-endian): verify_contributions pairs against it on the host
+_G2_ONE = bytes.fromhex(
+    "13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e"
+    "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8"
+    "0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be"
+    "0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801")
+_FP_MODULUS = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
+
+
+def _g1_negate(pt):
+    pt = bytes(pt)
+    y = int.from_bytes(pt[48:], "big")
+    return pt[:48] + ((_FP_MODULUS - y) % _FP_MODULUS).to_bytes(48, "big")
+
+
+def _is_identity(pt):
+    """the identity as the library writes it (the infinity bit, then zeros) or as its key decoder also reads it (all zeros)"""
+    return bool(pt[0] & 0x40) or not any(pt)
+
+
+def verify_contributions(d1_first, links, d1_last):
+    """Do these links lead from the key whose d1 is d1_first to the key whose d1 is d1_last?  links: (d1_before, d1_after, dmul_g2) per contribution,
+    in order (a Contribution is taken apart the same way).  True when every link satisfies e(d1_after, g2) = e(d1_before, [delta']_2) (zk_pairing_check
+    on the host: two pairings per link; the call also refuses points off the curve or outside the subgroup), the first link starts at d1_first, each
+    link starts where the one before it ended, the last ends at d1_last, and no [delta']_2 nor any d1 is the identity.  An empty chain holds when
+    d1_first == d1_last.
+
+    What a link is: it shows the RATIO of two delta -- d1_after = delta' d1_before for the delta' whose [delta']_2 the contributor published.  What
+    it is not: it does not show that the contributor KNEW delta' (a proof of knowledge does that), nor that the chain is the one a ceremony agreed
+    on (its transcript hash does that), nor that the rest of either key is well formed (Groth16.check_key under VKey.with_delta does that).  Those
+    are the caller's protocol."""
+    cur = bytes(d1_first)
+    if len(cur) != 96 or len(bytes(d1_last)) != 96 or _is_identity(cur):
+        return False
+    for link in links:
+        if isinstance(link, Contribution):
+            link = (link.d1_before, link.d1_after, link.dmul_g2)
+        before, after, dg2 = (bytes(x) for x in link)
+        if len(before) != 96 or len(after) != 96 or len(dg2) != 192:
+            return False
+        if before != cur or _is_identity(after) or _is_identity(dg2):
+            return False
+        one = C.c_int(0)
+        try:
+            _lib.check(_lib.lib().zk_pairing_check(after + _g1_negate(before), _G2_ONE + dg2, C.c_size_t(2), C.byref(one)))
+        except _lib.ZkError:
+            return False
+        if not one.value:
+            return False
+        cur = after
+    return cur == bytes(d1_last)
+
+
 @dataclass
 class Proof:
     a: bytes   # G1 96 B
@@ -589,6 +661,25 @@ class Groth16:
         if bytes(vkey.ab) != bytes(Pairing.pairing(a, b2)):
             mask |= _lib.KEYCHK_AB
         return KeyCheck(mask)
+
+    def contribute(self, dmul=None):
+        """A phase-2 contribution to the key in this handle, on the device (zk_groth16_pk_contribute): delta <- delta * dmul.  d1 and d2 are multiplied
+        by dmul, tiztd (or hl) and ltd_mid by 1 / dmul, the window tables are built again from the points on the device; afterwards the handle is the
+        one an upload of the contributed key's bytes gives (pool_points(..., compressed=True) stores it).  dmul: 0 < dmul < r; None draws it from
+        os.urandom here and FORGETS it on return -- a key is sound when one contributor did.  Returns a Contribution; the partner verification
+        key is vkey.with_delta(contribution.vk_d).  Tau-power and Lagrange-form handles held whole on one device."""
+        import os
+        if dmul is None:
+            dmul = 0
+            while not dmul:
+                dmul = int.from_bytes(os.urandom(64), "little") % FR_MODULUS
+        dmul = int(dmul)
+        if dmul < 0 or dmul >= 1 << 256:
+            raise ValueError("contribute: dmul is an element of Fr")
+        d = np.frombuffer(dmul.to_bytes(32, "little"), dtype=np.uint8)
+        link, dg2, vkd = (np.zeros(k, dtype=np.uint8) for k in (192, 192, 192))
+        _lib.check(_lib.lib().zk_groth16_pk_contribute(self.handle, _p(d), _p(link), _p(dg2), _p(vkd)))
+        return Contribution(bytes(link[:96]), bytes(link[96:]), bytes(dg2), bytes(vkd))
 
     def pool_points(self, group, compressed=False):
         """The resident base pool (1 = G1, 2 = G2) as uncompressed bytes, in pool order; compressed=True: in wire form (48 / 96 B per point, encoded
