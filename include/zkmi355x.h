@@ -245,7 +245,11 @@ int zk_groth16_pk_shard(uint64_t handle, uint32_t rank, uint32_t world);
  * Status: ZK_ERR_ARG for a null L / R / O / mid / toxic, an unknown form, n outside [1, 2^24], m = 0, gamma = 0 or delta = 0 (the reference divides by
  * them, :70-90), a malformed matrix, and for handle != NULL while the device list has several entries (multi-device keygen is not offered; the
  * bytes can be had on any list, computed on its first device); ZK_ERR_DOMAIN for a wrong *_points; ZK_ERR_SCALAR_RANGE for a trapdoor scalar or a
- * matrix coefficient >= r; ZK_ERR_HIP without a GPU -- the argument checks (null, form, counts, trapdoor) come first. */
+ * matrix coefficient >= r; ZK_ERR_HIP without a GPU -- the argument checks (null, form, counts, trapdoor) come first.
+ * Zero and degenerate trapdoors: alpha = 0, beta = 0 and tau = 0 are served like any value (a, b1, b2 are then the identity; the tau powers are
+ * the generator followed by identities), and so is every other tau -- a point of the domain 0 .. n-1 (Z(tau) = 0: the l_i(tau) are a unit vector,
+ * tiztd / hl all the identity), a point of n .. 2n-2 (the lambda_t(tau) are a unit vector), 1, r-1: l_i(tau) divides by nothing that depends on
+ * tau.  Only gamma = 0 and delta = 0 are refused.  tests/test_gpu_degenerate_trapdoors.py holds each to the literal setup. */
 #define ZK_KEY_FORM_TAU_POWERS 0
 #define ZK_KEY_FORM_LAGRANGE   1
 int zk_groth16_keygen(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
@@ -517,7 +521,8 @@ int zk_pinocchio_pk_upload_lagrange(uint32_t n, uint32_t m, const zk_csr* L, con
                                     const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points,
                                     const uint8_t* h_lagrange /* n * 96 */, uint64_t* handle);
 /* KeyGen.generate, pinocchio.ml:77-189, in one call; arguments, forms, handle and status codes as zk_groth16_keygen (no trapdoor value is refused
- * but one >= r: the reference divides by none).
+ * but one >= r: the reference divides by none -- each of rv, rw, s, av, aw, ay, b, gm may be 0, and s may be a point of the domain 0 .. n-1
+ * (t = Z(s) = 0: vt .. ybt, wt, wawt and the verification key's yt are the identity) or of n .. 2n-2; the key is the reference's, sound or not).
  *   toxic = rv | rw | s | av | aw | ay | b | gm (:83-91);  pk_g1 / pk_g2: the layouts of zk_pinocchio_pk_upload, 5 |mids| + (n+1) + 2m + 7 and
  *   2 |mids| + (n+1) + 2 points;  vk_g1 = one | aw | bgm | vv_io | yy_io (3 + 2 n_io), vk_g2 = one2 | av | ay | gm2 | bgm2 | yt | ww_io (6 + n_io), :62-75.
  *   The handle's h pool is compact whenever ZK_PIN_COMPACT_H allows it: a generated key satisfies the relation behind it by construction, so the

@@ -473,12 +473,19 @@ static void lagrange_at(lagtab_t *T, uint32_t n, const fr_t *tau) {
     fact[0] = FR_ONE;
     for (uint32_t i = 1; i <= n; i++) { fr_t fi; fr_from_u64(&fi, i); fr_mul(&fact[i], &fact[i - 1], &fi); }
     fr_t zt = FR_ONE;
+    uint32_t hit = n;                                                          /* tau = hit is a point of the domain */
     for (uint32_t i = 0; i < n; i++) {
         fr_t fi, d; fr_from_u64(&fi, i); fr_sub(&d, tau, &fi); fr_mul(&zt, &zt, &d);
+        if (fr_is_zero(&d)) hit = i;
         fr_mul(&den[i], &d, &fact[i]); fr_mul(&den[i], &den[i], &fact[n - 1 - i]);
         if ((n - 1 - i) & 1) fr_neg(&den[i], &den[i]);
     }
     T->zt = zt;
+    if (hit < n) {                                                             /* the batch inversion below would invert 0: the basis is the unit vector, Z = 0 */
+        for (uint32_t i = 0; i < n; i++) T->lag[i] = i == hit ? FR_ONE : FR_ZERO;
+        free(den); free(pre); free(fact);
+        return;
+    }
     /* batch inversion */
     pre[0] = FR_ONE;
     for (uint32_t i = 0; i < n; i++) fr_mul(&pre[i + 1], &pre[i], &den[i]);
@@ -775,8 +782,10 @@ out:
  *   vv' = [rv (v_mid(s) + dv t)]_1, ww' = [rw (w_mid(s) + dw t)]_2, yy' = [ry (y_mid(s) + dy t)]_1,
  *   h'  = [h(s) + dw v(s) + dv w(s) + dv dw t - dy]_1,  h(s) = (v(s) w(s) - y(s)) / t,
  *   vavv' = av vv', waww' = aw ww', yayy' = ay yy',
- *   bvwy' = [b (rv v_mid + rw w_mid + ry y_mid) + b t (rv dv + rw dw + ry dy)]_1 */
-API void orc_pinocchio_prove_trapdoor(uint32_t n, uint32_t m,
+ *   bvwy' = [b (rv v_mid + rw w_mid + ry y_mid) + b t (rv dv + rw dw + ry dy)]_1
+ * Returns 0, or -4 with `proof` untouched when s is a point of the domain: t = Z(s) = 0 and h(s) is 0 / 0 in this form (the value of the quotient
+ * POLYNOMIAL at s is not a function of v(s), w(s), y(s)); there orc_pinocchio_prove on the dense QAP is the only oracle. */
+API int orc_pinocchio_prove_trapdoor(uint32_t n, uint32_t m,
                                       const uint32_t *l_ptr, const uint32_t *l_col, const uint8_t *l_val,
                                       const uint32_t *r_ptr, const uint32_t *r_col, const uint8_t *r_val,
                                       const uint32_t *o_ptr, const uint32_t *o_col, const uint8_t *o_val,
@@ -793,6 +802,7 @@ API void orc_pinocchio_prove_trapdoor(uint32_t n, uint32_t m,
     lagtab_t T; lagrange_at(&T, n, &s);
     csr_t L = {l_ptr, l_col, l_val}, Rm = {r_ptr, r_col, r_val}, O = {o_ptr, o_col, o_val};
     fr_t vs, vm, ws, wm, ys, ym, t = T.zt;
+    if (fr_is_zero(&t)) { free(c); free(T.lag); return -4; }
     csr_at_tau(&vs, &vm, &L, n, c, mid, T.lag);
     csr_at_tau(&ws, &wm, &Rm, n, c, mid, T.lag);
     csr_at_tau(&ys, &ym, &O, n, c, mid, T.lag);
@@ -821,4 +831,5 @@ API void orc_pinocchio_prove_trapdoor(uint32_t n, uint32_t m,
     fr_mul(&x, &e_yy, &ay); g1_mul(&P1, &g1, &x); g1_to_bytes(proof + 768, &P1);
     g1_mul(&P1, &g1, &e_b); g1_to_bytes(proof + 864, &P1);
     free(c); free(T.lag);
+    return 0;
 }

@@ -230,8 +230,13 @@ def pinocchio_prove(qap, pk_g1, pk_g2, mid, sol, dv, dw, dy):
 
 
 def pinocchio_prove_trapdoor(n, m, L, R, O, mid, sol, toxic, dv, dw, dy):
+    """The proof's bytes from the trapdoor.  s inside the domain 0 .. n-1 raises ValueError: Z(s) = 0 and this form has no h(s) (0 / 0); the
+    literal pinocchio_prove on the dense QAP is the oracle there."""
     out = _buf(960)
-    lib.orc_pinocchio_prove_trapdoor(n, m, *L.args(), *R.args(), *O.args(), _b(bytes(mid)), _b(sol), _b(toxic), _b(dv), _b(dw), _b(dy), out)
+    rc = lib.orc_pinocchio_prove_trapdoor(n, m, *L.args(), *R.args(), *O.args(), _b(bytes(mid)), _b(sol), _b(toxic), _b(dv), _b(dw), _b(dy), out)
+    if rc == -4:
+        raise ValueError("pinocchio_prove_trapdoor: s is a point of the domain, Z(s) = 0; use the literal pinocchio_prove")
+    assert rc == 0, rc
     return bytes(out)
 
 

@@ -303,7 +303,7 @@ def test_pinocchio_keygen_exponents_points_pools_and_proofs(log_n, compact):
 @pytest.mark.parametrize("name", ["readme", "n1", "unused", "mid0"])
 def test_small_circuits_handles_and_proofs(name):
     cs, w = all_public(CIRCUITS["cubic6"]) if name == "mid0" else CIRCUITS[name]()
-    # (a trapdoor inside the domain is held to the LITERAL setup in the byte tests above: the exponent and trapdoor oracles used here divide by tau - i)
+    # (a trapdoor inside the domain is held to the LITERAL setup in the byte tests above, and on every route to a handle in tests/test_gpu_degenerate_trapdoors.py)
     check_groth16(cs, w, trapdoors(0x51 + len(name), cs, 5, False), cross_check=True)
     for compact in (True, False):
         check_pinocchio(cs, w, trapdoors(0x52 + len(name), cs, 8, False), cross_check=True, compact=compact)

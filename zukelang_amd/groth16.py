@@ -277,8 +277,12 @@ class KeyCheck:
 
 
 def _lagrange_at(n, tau):
-    """l_i(tau) for the integer domain 0..n-1 and Z(tau) (QAP.ml:84,92), O(n) with one inversion."""
+    """l_i(tau) for the integer domain 0..n-1 and Z(tau) (QAP.ml:84,92), O(n) with one inversion.  At a point of the domain the batch inversion
+    below would invert 0 (every tau - i is a factor of its product): there the basis is the unit vector and Z = 0, no division at all."""
     P = FR_MODULUS
+    tau %= P
+    if tau < n:
+        return [int(i == tau) for i in range(n)], 0
     fact = [1] * (n + 1)
     for i in range(1, n + 1):
         fact[i] = fact[i - 1] * i % P
