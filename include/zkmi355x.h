@@ -798,6 +798,28 @@ int zk_selftest_fp_paired(const uint32_t* operands, size_t n, uint8_t* out);
  * product x y / 2^406 in Fp2:   0  a b      1  c d      2  a b - c d (the fused end of a mixed addition).
  * A null pointer, n = 0, a limb or a top limb out of range -> ZK_ERR_ARG before the device is touched. */
 int zk_selftest_fp2_lanewise(const uint32_t* operands, size_t n, uint8_t* out);
+/* The base field under its products, on bare limbs (tests/test_gpu_fp29.py): the additive forms of csrc/ff.cuh with their tables of spread multiples of p,
+ * the full reduction, the zero test, the dense memory format and the lockstep inversion of csrc/fp_inv.cuh.  operands: n x 3 values a, b, c as their 14 limbs
+ * of 29 bits in a 16-word slot each (48 words per lane); slots an op does not read are not looked at.  Unless stated otherwise an operand is weakly
+ * normalised -- limbs 0..12 at most 2^29 + 7 -- and its top limb is at most that of its value bound B, (B p) >> 377; keeping the VALUE below B p is the
+ * caller's part.  out: raw limbs (14 words) with no reduction beyond what the function under test does, unless stated otherwise.
+ *   op 0   fp_canon_call(a), a < 8192 p: the exact limbs of a mod p
+ *   op 1   fp_carry(a): a is ANY 14 words (no limb rule; the top limb is taken modulo 2^32)
+ *   op 2   fe_add(a, b), a, b < 64 p          op 3   fe_dbl(a), a < 64 p
+ *   op 4   the first 12 words of a are a dense 384-bit value below p (anything else -> ZK_ERR_ARG): fp_unpack of it (14 words) | fp_pack of that (12 words)
+ *   op 5   a in EXACT limbs (at most 2^29 - 1) and below p (anything else -> ZK_ERR_ARG), taken as the plain integer X: fp_inv29_call(X) as it returns it,
+ *          weakly normalised limbs of X^-1 mod p with a value in (4 p, 60 p), 0 for 0 (14 words) | fe_inv_fast of the same limbs, fully reduced: X^-1 2^812 mod p (14 words)
+ *   op 8, 9, 10   fe_is_zero<B>(a), a < B p, B = 2, 64 (the at-rest bound), 192 (the largest any call site instantiates).  One flag word: bit 0 as a unit
+ *          without ZK_FP_INLINE_MUL compiles it (slow path fp_canon), bit 1 as a unit with it does (slow path fp_is_zero_mod_p_inline), bit 2
+ *          fp_is_zero_mod_p_inline(a) called directly (a = k p for k = limb0 / p mod 2^29)
+ *   op 16 + k, k = 0..11    fe_sub<64, B>(a, b): a - b + 2^(k+1) p through row k of FP29_KP; a < 64 p, b < B p, B = 1 for k = 0 and 2^k otherwise
+ *   op 32 + k, k = 0..12    fe_neg<B>(a): 2^(k+1) p - a through row k of FP29_KP; a < B p, B as above
+ *   op 48 + k, k = 0..12    fe_neg_lazy<B>(a): the same through row k of FP29_KPN with NO carry pass: limbs in [1, 2^30]
+ *   op 64 + k, k = 1..11    fe_sub_sub_dbl<64, B, B>(a, b, c): a - b - 2 c + 2^(k+1) p through row k of FP29_KPW; a < 64 p, b, c < B p, B = 1 for k = 1 and 2^(k-1) otherwise
+ * These are all the rows a function can be instantiated with under FP_MAX_BOUND = 8192.
+ * A null pointer, n = 0, n >= 2^24, another op, a limb or a top limb out of range, an operand that is not canonical where the op needs one -> ZK_ERR_ARG
+ * before the device is touched. */
+int zk_selftest_fp29(int op, const uint32_t* operands, size_t n, uint32_t* out);
 /* Square roots as the decompression kernels take them (tests/test_gpu_field.py): n elements of Fp (field 0: 48 B big-endian each) or Fp2 (field 1:
  * 96 B each, imaginary part | real part, the order of a G2 coordinate on the wire), one lane per element.  is_square[i] = 1 / 0; root[i] = of the two
  * roots the one the ZCash sign rule calls the larger (Fp2: by the imaginary part, by the real part when that is zero) -- decided by the same device

@@ -79,6 +79,45 @@ def test_field_battery_matches_big_integers():
         assert get(i, 22) == ((b0 * b0 - b1 * b1) % p, 2 * b0 * b1 % p)[c], (i, "fp2 lane-pair square with the lazy difference")
 
 
+def test_inversions_whose_montgomery_residue_is_the_edge():
+    """Added rows for outputs 5, 16 and 17.  The hook takes canonical x and inverts the integer x * 2^406 mod p, so 0, 1, 2^380 above arrive as what are in
+    effect random integers.  Here x = X * 2^-406 mod p for the X that matter to fp_inv29_call (tests/fp29_cases.py): those that keep it busy for all 27
+    iterations, those of them a 26-iteration build gets wrong, the values on either side of its `exact` switch, the limb boundaries.  For output 17 the
+    pair (x0, x1) is steered so that the norm x0^2 + x1^2 is such an x, where x - x1^2 has a square root."""
+    import fp29_cases as Cs
+    classes = Cs.full_length_montgomery_residues()
+    assert all(classes.values()) and len(classes["needs_all_27"]) >= 32 and len(classes["wrong_after_26"]) >= 16
+    rinv = pow(2, -406, p)
+    rnd = random.Random(0xED6E)
+    xs = [X * rinv % p for cl in classes.values() for X in cl]
+    a, b, steered = [], [], 0
+    for x in xs:                                    # lanes (2k, 2k+1): x itself beside a random partner
+        a += [x, rnd.randrange(p)]
+        b += [rnd.randrange(p), x]
+    for x in xs:                                    # lanes (2k, 2k+1) = (x0, x1) with x0^2 + x1^2 = x
+        for _ in range(64):
+            x1 = rnd.randrange(p)
+            x0 = pow((x - x1 * x1) % p, (p + 1) // 4, p)
+            if (x0 * x0 + x1 * x1) % p == x:
+                a += [x0, x1]
+                b += [rnd.randrange(p), rnd.randrange(p)]
+                steered += 1
+                break
+    assert steered >= len(xs) * 3 // 4
+    n = len(a)
+    out = np.zeros(NOUT * 48 * n, dtype=np.uint8)
+    _lib.check(_lib.lib().zk_selftest_fp(b"".join(le48(x) for x in a), b"".join(le48(x) for x in b), C.c_size_t(n), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    raw = out.tobytes()
+    get = lambda i, k: int.from_bytes(raw[48 * (NOUT * i + k):48 * (NOUT * i + k + 1)], "little")
+    inv = lambda x: pow(x, p - 2, p)
+    for i in range(n):
+        assert get(i, 5) == inv(a[i]), (i, "fe_inv", hex(a[i]))
+        assert get(i, 16) == inv(a[i]), (i, "fe_inv_fast", hex(a[i]))
+        e = i & ~1
+        nrm = inv((a[e] * a[e] + a[e + 1] * a[e + 1]) % p)
+        assert get(i, 17) == ((a[e] * nrm) % p, (-a[e + 1] * nrm) % p)[i & 1], (i, "fp2 fe_inv_fast", hex(a[e]), hex(a[e + 1]))
+
+
 def be48(x):
     return int(x).to_bytes(48, "big")
 

@@ -77,6 +77,29 @@ def test_word_field_battery_matches_big_integers():
     assert all(seen.values()), seen
 
 
+def test_inverses_whose_montgomery_residue_is_the_edge():
+    """Added rows for output 7.  fe_inv runs words_inv on the Montgomery residue a * 2^256 mod r, so the edge operands above arrive as what are in effect
+    random integers.  Here a = A * 2^-256 mod r for A in 1, 2, r - 1, 2^k, r - 2^k and the A that drive the outer loop of words_inv longest in its
+    integer restatement (fp29_model.words_inv; tests/fp29_cases.py searches with a fixed seed).  The largest count found is 203, against the guard
+    4 * 32 * 8 = 1024."""
+    import fp29_cases as Cs
+    import fp29_model as FP
+    table = Cs.fr_words_inv_operands()
+    assert {1, 2, r - 1, 1 << 252, r - (1 << 7)} <= set(table) and len(table) >= 64
+    assert 200 <= max(table.values()) < Cs.FR_GUARD // 4, max(table.values())
+    rinv = pow(2, -256, r)
+    a = [A * rinv % r for A in table]
+    b = [1] * len(a)
+    out = np.zeros(NOUT * 32 * len(a), dtype=np.uint8)
+    ab, bb = blob(a), blob(b)
+    _lib.check(_lib.lib().zk_selftest_fr(0, ab.ctypes.data_as(_lib._P8), bb.ctypes.data_as(_lib._P8), len(a), out.ctypes.data_as(_lib._P8)))
+    raw = out.tobytes()
+    for i, (A, x) in enumerate(zip(table, a)):
+        assert x * (1 << 256) % r == A and FP.words_inv(A, r)[0] == pow(A, -1, r)
+        got = int.from_bytes(raw[32 * (NOUT * i + 7):32 * (NOUT * i + 8)], "little")
+        assert got == pow(x, r - 2, r), (hex(A), table[A])
+
+
 def test_is_canonical_decides_the_borrow_chain_at_every_word():
     word = lambda k: 1 << (32 * k)
     vals = [r - 1, r, r + 1, (1 << 256) - 1, 0]
