@@ -403,6 +403,40 @@ int zk_groth16_pk_contribute(uint64_t handle, const uint8_t dmul[32] /* delta', 
                              uint8_t link_g1[2 * 96]   /* d1 before | d1 after, may be NULL */,
                              uint8_t dmul_g2[192]      /* [delta']_2, may be NULL */,
                              uint8_t vk_d[192]         /* d2 after = the new vkey.d, may be NULL */);
+/* ---- a phase-1 string specialised to a circuit ---------------------------------------------------------------------------------------------------
+ * The deterministic station between a powers-of-tau string and phase 2: from [tau^i]_1, [alpha tau^i]_1, [beta tau^i]_1, [beta]_2, [tau^i]_2 and the
+ * circuit, the key of groth16.ml:45-108 for the trapdoor (alpha, beta, gamma = 1, delta = 1, tau), byte for byte -- with no secret anywhere: every
+ * point of the key is a linear combination of the string's points.  After it zk_groth16_pk_contribute moves delta and zk_groth16_key_check judges the
+ * result; the trapdoor never exists on any host.
+ *   srs_g1 = tau1[max(n+2, 2n-1)] | alpha_tau1[n] | beta_tau1[n]  (96 B each),  srs_g2 = beta2 | tau2[n+2]  (192 B each): uncompressed points, exactly
+ *     the counts zk_groth16_srs_sizes gives (ZK_ERR_DOMAIN otherwise).
+ *   Key bytes (pk_g1 / pk_g2 / vk_g1 / vk_g2 / handle / form: layouts, optionality and meaning as in zk_groth16_keygen):
+ *     a = alpha_tau1[0]   d1 = the G1 generator   b1 = beta_tau1[0]   ti1 = tau1[0 .. n+1]   b2 = beta2   d2 = the G2 generator   ti2 = tau2
+ *     tiztd[i] = sum_j z_j tau1[i+j], i < n-1, z the coefficients of Z = prod_{i<n} (X - i)        (one correlation in the exponent)
+ *     ltd_mid[k] = sum_i (L[i,k] [beta l_i] + R[i,k] [alpha l_i] + O[i,k] [l_i]) for the mids, Var order (groth16.ml:59-68: beta with L, alpha with R);
+ *       [l_i], [alpha l_i], [beta l_i] are derived from the three G1 lists as zk_groth16_pk_derive_lagrange derives [l_i] from ti1
+ *     vk_g1 = one1 | ltgm_io (the same sum for the other variables, gamma = 1),  vk_g2 = one2 | gm | d: three times the G2 generator;
+ *       ab = e(a, b2) stays the caller's pairing
+ *   handle: what an upload of those bytes would build (ZK_KEY_FORM_TAU_POWERS), or that plus zk_groth16_pk_derive_lagrange (ZK_KEY_FORM_LAGRANGE;
+ *     the [l_i]_1 of the specialisation are reused).  Every later call works on it: pool points, every prove entry point, contribute, both key checks.
+ * The string's points come from outside and are checked like the points of zk_groth16_pk_upload, list by list in the order above, the first bad list
+ * deciding: an encoding -> ZK_ERR_ARG, a point off the curve or outside the subgroup -> ZK_ERR_NOT_ON_CURVE.  ZK_KEY_SUBGROUP_CHECK=0 skips the
+ * subgroup part, and the handle remembers it: zk_groth16_key_check refuses it as it refuses such uploads.
+ * TRUST: the call cannot know whether the string is well formed and does not try.  Whatever points it is given, the output is the linear map above
+ * applied to them.  The contract is: run zk_groth16_key_check (or zk_groth16_key_check_lagrange) with the returned verification key on the result.
+ * A string whose lists disagree gives a key that fails it (alpha_tau1 not alpha tau^i: bit L; a wrong high power of tau1: bit H_BASES).  A check of
+ * the string itself -- the powers beyond n+1, the alpha and beta lists against tau2 -- is not part of this library.
+ * Status, in this order, everything before ZK_ERR_HIP without touching the device: ZK_ERR_ARG for a null L / R / O / mid / srs_g1 / srs_g2, an unknown
+ * form, n outside [1, 2^24] (the transforms in the exponent run at 2 * 2^ceil(log2 n) <= 2^25 points, the bound of zk_groth16_keygen and of the
+ * derivation) or m = 0; ZK_ERR_DOMAIN for any *_points that is not exactly the expected count; ZK_ERR_ARG for a malformed matrix or more than
+ * 2^30 - 1 variables plus nonzero entries; ZK_ERR_SCALAR_RANGE for a matrix coefficient >= r; ZK_ERR_HIP without a GPU; ZK_ERR_ARG for handle != NULL
+ * while the device list has several entries; then the verdict on the string.  A refused call writes nothing and leaves no handle.
+ * Timer families specialize_derive, specialize_correlate, specialize_mul, specialize_sum (and lagrange_derive for the Lagrange-form handle). */
+int zk_groth16_srs_sizes(uint32_t n, uint64_t* tau_g1, uint64_t* ab_g1, uint64_t* tau_g2);          /* max(n+2, 2n-1), n, n+2; each may be NULL */
+int zk_groth16_pk_specialize(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
+                             const uint8_t* srs_g1, size_t srs_g1_points, const uint8_t* srs_g2, size_t srs_g2_points, uint32_t form,
+                             uint8_t* pk_g1, size_t pk_g1_points, uint8_t* pk_g2, size_t pk_g2_points,
+                             uint8_t* vk_g1 /* (1 + n_io) * 96 */, uint8_t* vk_g2 /* 3 * 192 */, uint64_t* handle);
 int zk_groth16_pk_free(uint64_t handle);
 
 /* Groth16.prove rng qap pkey sol with r, s supplied by the caller in the order the reference
@@ -872,6 +906,13 @@ int zk_selftest_group(int group, int form, int rep, const uint8_t* a, const uint
  * identity).  slab: points per chain of launches, 0 = the call's default of 2^18, so that a list of a few hundred points can cross a slab boundary.  A
  * null pointer, n = 0 or k >= r -> ZK_ERR_ARG before the device is touched; a coordinate >= p -> ZK_ERR_ARG, a point off the curve -> ZK_ERR_NOT_ON_CURVE. */
 int zk_selftest_g1_scale(const uint8_t* pts /* n * 96 */, size_t n, const uint8_t k[32], uint32_t slab /* 0 = default */, uint8_t* out /* n * 96 */);
+/* The column sums of zk_groth16_pk_specialize on a caller's list (tests/test_gpu_colsum.py): out[k] = sum over e in [col_ptr[k], col_ptr[k+1]) of
+ * coef[e] * pts[row[e]] for n_pts uncompressed G1 points (the identity as the library encodes it, or all zeros) and m columns, through the call's own
+ * stages: the split of the entries by coefficient class, the compacted multiplications, the chunked sums and their levels.  An empty column gives the
+ * identity; a row may repeat within a column.  A null pointer, n_pts = 0, m = 0, a col_ptr that is not monotone, a row >= n_pts -> ZK_ERR_ARG, a
+ * coefficient >= r -> ZK_ERR_SCALAR_RANGE, all before the device is touched; a coordinate >= p -> ZK_ERR_ARG, a point off the curve -> ZK_ERR_NOT_ON_CURVE. */
+int zk_selftest_g1_colsum(const uint8_t* pts /* n_pts * 96 */, size_t n_pts, const uint32_t* col_ptr /* m + 1 */, const uint32_t* row /* nnz */,
+                          const uint8_t* coef /* nnz * 32 */, uint32_t m, uint8_t* out /* m * 96 */);
 /* zk_groth16_verify_folded stopped before the comparison (tests/test_gpu_verify_folded.py): both sides of the folded equation as GT encodings --
  * lhs_gt the final exponentiation of the product of the count + 2 Miller values, rhs_gt = ab^S -- and the two sums that enter the key's pairs,
  * sum_c = sum_i [rho_i] C_i and sum_io = sum_k t_k ltgm_io_k, un-negated, uncompressed (the identity as the library encodes it).  Same arguments and

@@ -216,6 +216,59 @@ module Make (C : Curve.S) = struct
         ignore (register vars (l, r, o) n pkey));
     (pkey, vkey)
 
+  (* ---------------------------------------------------------------- specialize
+     A phase-1 string specialised to the circuit on the device (zk_groth16_pk_specialize): the keys `keygen` would give for the trapdoor
+     (alpha, beta, 1, 1, tau) from [tau^i]_1 (max (n+2) (2n-1) of them), [alpha tau^i]_1, [beta tau^i]_1 (n each), [beta]_2 and [tau^i]_2 (n+2) --
+     nobody knows the trapdoor.  The lists must have exactly those lengths (Mi355x.groth16_srs_sizes).  The call trusts the string: run check_key
+     with the returned vkey on the result, then contribute. *)
+  let specialize (circuit : circuit) (qap : qap) ~(tau1 : G1.t list) ~(alpha_tau1 : G1.t list) ~(beta_tau1 : G1.t list) ~(beta2 : G2.t)
+      ~(tau2 : G2.t list) : pkey * vkey =
+    let n = Poly.degree qap.target in
+    let vars = List.map fst (Var.Map.bindings qap.v) in
+    let m = List.length vars in
+    let is_mid v = Var.Set.mem v circuit.Circuit.mids in
+    let mids = List.filter is_mid vars and ios = List.filter (fun v -> not (is_mid v)) vars in
+    let mid = Mi355x.cat (List.map (fun v -> Bytes.make 1 (if is_mid v then '\001' else '\000')) vars) in
+    let n_ti = n + 2 and n_tiz = max (n - 1) 0 and n_mid = List.length mids and n_io = List.length ios in
+    let l, r, o = matrices_of_gates (index_of_vars vars) circuit.Circuit.gates in
+    let p1, p2, v1, v2, h =
+      Mi355x.specialize_call ~n ~m l r o ~mid
+        ~srs_g1:(Mi355x.cat [ g1_bytes tau1; g1_bytes alpha_tau1; g1_bytes beta_tau1 ])
+        ~srs_g2:(Mi355x.cat [ G2.to_bytes beta2; g2_bytes tau2 ])
+        ~form:Mi355x.key_form_lagrange
+        ~g1_points:(3 + n_ti + n_tiz + n_mid)
+        ~g2_points:(2 + n_ti) ~vk1_points:(1 + n_io) ~vk2_points:3
+    in
+    let take b at off count = List.init count (fun i -> at b (off + i)) in
+    let rekey ks points = Var.Map.of_list (List.combine ks points) in
+    let pkey : pkey =
+      { a = g1_at p1 0;
+        d1 = g1_at p1 1;
+        b1 = g1_at p1 2;
+        ti1 = take p1 g1_at 3 n_ti;
+        tiztd = take p1 g1_at (3 + n_ti) n_tiz;
+        ltd_mid = rekey mids (take p1 g1_at (3 + n_ti + n_tiz) n_mid);
+        b2 = g2_at p2 0;
+        d2 = g2_at p2 1;
+        ti2 = take p2 g2_at 2 n_ti
+      }
+    in
+    let vkey : vkey =
+      { one1 = g1_at v1 0;
+        ltgm_io = rekey ios (take v1 g1_at 1 n_io);
+        one2 = g2_at v2 0;
+        gm = g2_at v2 1;
+        d = g2_at v2 2;
+        ab = Pairing.pairing pkey.a pkey.b2
+      }
+    in
+    (match h with
+    | Some h ->
+        Gc.finalise (fun _ -> ignore (Mi355x.zk_groth16_pk_free h)) pkey;
+        Handles.replace handles pkey h
+    | None -> ignore (register vars (l, r, o) n pkey));
+    (pkey, vkey)
+
   (* ---------------------------------------------------------------- prove *)
 
   let prove rng (qap : qap) (pkey : pkey) (sol : f Var.Map.t) : proof =

@@ -235,6 +235,43 @@ let keygen_call f ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(
        (if want_handle then h else from_voidp uint64_t null));
   (g1, g2, vk1, vk2, if want_handle then Some !@h else None)
 
+(* ------------------------------------------------------------------ a phase-1 string specialised to a circuit (header: zk_groth16_pk_specialize)
+   srs_g1 = tau1[max(n+2, 2n-1)] | alpha_tau1[n] | beta_tau1[n], srs_g2 = beta2 | tau2[n+2], uncompressed: the key of the trapdoor
+   (alpha, beta, 1, 1, tau) comes out, bytes and handle as from keygen_call, and no secret went in.  The string is trusted: check the key. *)
+
+let zk_groth16_srs_sizes = fn "zk_groth16_srs_sizes" (uint32_t @-> ptr uint64_t @-> ptr uint64_t @-> ptr uint64_t @-> returning int)
+
+let zk_groth16_pk_specialize =
+  fn "zk_groth16_pk_specialize"
+    (uint32_t @-> uint32_t @-> ptr csr @-> ptr csr @-> ptr csr @-> ocaml_bytes @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> size_t @-> uint32_t
+   @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> size_t @-> ocaml_bytes @-> ocaml_bytes @-> ptr uint64_t @-> returning int)
+
+(* the call's column sums on a caller's list (the library's own tests): pts, n_pts, col_ptr, row, coef, m, out *)
+let zk_selftest_g1_colsum =
+  fn "zk_selftest_g1_colsum" (ocaml_bytes @-> size_t @-> ptr uint32_t @-> ptr uint32_t @-> ocaml_bytes @-> uint32_t @-> ocaml_bytes @-> returning int)
+
+(* (points of tau1, of alpha_tau1 and beta_tau1 each, of tau2) for n constraints *)
+let groth16_srs_sizes ~n : int * int * int =
+  let a = allocate uint64_t Unsigned.UInt64.zero and b = allocate uint64_t Unsigned.UInt64.zero and c = allocate uint64_t Unsigned.UInt64.zero in
+  check (zk_groth16_srs_sizes (u32 n) a b c);
+  (Unsigned.UInt64.to_int !@a, Unsigned.UInt64.to_int !@b, Unsigned.UInt64.to_int !@c)
+
+(* one specialisation: (pk_g1, pk_g2, vk_g1, vk_g2, handle option), the handle under the rule of keygen_call *)
+let specialize_call ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(srs_g1 : bytes) ~(srs_g2 : bytes) ~form ~g1_points ~g2_points ~vk1_points
+    ~vk2_points =
+  let g1 = Bytes.create (96 * g1_points) and g2 = Bytes.create (192 * g2_points) in
+  let vk1 = Bytes.create (96 * vk1_points) and vk2 = Bytes.create (192 * vk2_points) in
+  let want_handle = device_list_length () <= 1 in
+  let h = allocate uint64_t Unsigned.UInt64.zero in
+  check
+    (zk_groth16_pk_specialize (u32 n) (u32 m) (addr l.c) (addr r.c) (addr o.c) (bytes_start mid) (bytes_start srs_g1)
+       (sz (Bytes.length srs_g1 / 96))
+       (bytes_start srs_g2)
+       (sz (Bytes.length srs_g2 / 192))
+       (u32 form) (bytes_start g1) (sz g1_points) (bytes_start g2) (sz g2_points) (bytes_start vk1) (bytes_start vk2)
+       (if want_handle then h else from_voidp uint64_t null));
+  (g1, g2, vk1, vk2, if want_handle then Some !@h else None)
+
 (* ------------------------------------------------------------------ Groth16: groth16.ml:24-34,116-161,235-237 *)
 
 let zk_groth16_pk_upload =

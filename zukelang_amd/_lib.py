@@ -36,6 +36,7 @@ EXPORTS = [
     "zk_groth16_prove_many_compressed", "zk_pinocchio_prove_many_compressed", "zk_selftest_proof_wire",
     "zk_groth16_key_check", "zk_groth16_key_check_lagrange",
     "zk_groth16_pk_contribute", "zk_selftest_g1_scale",
+    "zk_groth16_srs_sizes", "zk_groth16_pk_specialize", "zk_selftest_g1_colsum",
 ]
 
 
@@ -147,6 +148,13 @@ CONTRIBUTE_PROTOTYPES = {
     "zk_groth16_pk_contribute": [C.c_uint64, _P8, _P8, _P8, _P8],
     "zk_selftest_g1_scale": [_P8, C.c_size_t, _P8, C.c_uint32, _P8],
 }
+# a phase-1 string specialised to a circuit, and the hook of its column sums (tests/test_specialize_surface.py holds them to the header)
+SPECIALIZE_PROTOTYPES = {
+    "zk_groth16_srs_sizes": [C.c_uint32, _PH, _PH, _PH],
+    "zk_groth16_pk_specialize": [C.c_uint32, C.c_uint32, _PCSR, _PCSR, _PCSR, _P8, _P8, C.c_size_t, _P8, C.c_size_t, C.c_uint32,
+                                 _P8, C.c_size_t, _P8, C.c_size_t, _P8, _P8, _PH],
+    "zk_selftest_g1_colsum": [_P8, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P8, C.c_uint32, _P8],
+}
 # the bits of zk_groth16_key_check's mask (ZK_KEYCHK_*), in bit order, under the names Groth16.check_key reports
 KEYCHK_BITS = {
     "generators": 1, "tau_g1": 2, "tau_g2": 4, "beta": 8, "delta": 16, "h_bases": 32, "l": 64, "gamma": 128,
@@ -167,7 +175,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(FP29_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()) + list(KEY_CHECK_LAGRANGE_PROTOTYPES.items()) + list(CONTRIBUTE_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(FP29_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()) + list(KEY_CHECK_LAGRANGE_PROTOTYPES.items()) + list(CONTRIBUTE_PROTOTYPES.items()) + list(SPECIALIZE_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

@@ -158,9 +158,9 @@ static uint32_t key_window(uint64_t g1_points, bool in_subgroup) {
 }
 int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
                       const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, bool lagrange, bool shard_of_group,
-                      const void* d_g1, const void* d_g2, bool wire) {
+                      const void* d_g1, const void* d_g2, bool wire, bool device_in_subgroup) {
     // d_g1 / d_g2 (both or neither): the pools as dense affine points in device memory, computed by the library itself (keygen.hip) -- pk_g1 / pk_g2 are
-    // then not read
+    // then not read.  device_in_subgroup = false: they are a linear image of points that came from outside under ZK_KEY_SUBGROUP_CHECK=0 (specialize.hip)
     const bool generated = d_g1 && d_g2;
     if (!mid || (!generated && (!pk_g1 || !pk_g2)) || !L || !R || !O) ZK_FAIL(ZK_ERR_ARG, "pk_upload: null argument");
     if (world == 0 || rank >= world) ZK_FAIL(ZK_ERR_ARG, "pk_upload: bad rank / world");
@@ -196,14 +196,14 @@ int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, 
     // (zk_set_option "key_subgroup_check") skips the subgroup part for keys that were checked before (it is [r] P = O per point: 0.3 s at 2^20
     // constraints, 1.4 s at 2^22).  Read per key (set-up path).  A key uploaded without the check never gets folded windows: msm.cuh.
     const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    const bool chk = generated || !(e_chk && atoi(e_chk) == 0);
+    const bool chk = generated ? device_in_subgroup : !(e_chk && atoi(e_chk) == 0);
     const uint32_t cw = key_window(k.hi1 - k.lo1, chk);
     if (generated) {
         // in_subgroup = true without the [r] P = O test, and so folded windows (msm.cuh: msm_fold): every point of a generated key is [e] G for an
         // exponent the library computed itself, a multiple of the generator of the prime-order group.  ZK_KEY_SUBGROUP_CHECK governs points that come
-        // from outside; there are none here.
-        ZKCHK(msm_bases_from_device_affine(k.g1, CURVE_G1, (const uint8_t*)d_g1 + 96 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, true));
-        ZKCHK(msm_bases_from_device_affine(k.g2, CURVE_G2, (const uint8_t*)d_g2 + 192 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, true));
+        // from outside; there are none here.  A specialised key inherits the verdict on its string (chk = device_in_subgroup).
+        ZKCHK(msm_bases_from_device_affine(k.g1, CURVE_G1, (const uint8_t*)d_g1 + 96 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, chk));
+        ZKCHK(msm_bases_from_device_affine(k.g2, CURVE_G2, (const uint8_t*)d_g2 + 192 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, chk));
     } else if (wire) {          // pk_g1 / pk_g2 hold wire bytes (zk_groth16_pk_upload_compressed): this rank's slice is decoded where its tables are built
         ZKCHK(msm_bases_from_wire(k.g1, CURVE_G1, pk_g1 + 48 * k.lo1, k.hi1 - k.lo1, cw, true, c.stream, chk));
         ZKCHK(msm_bases_from_wire(k.g2, CURVE_G2, pk_g2 + 96 * k.lo2, k.hi2 - k.lo2, cw, true, c.stream, chk));
@@ -235,9 +235,9 @@ static int upload(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, cons
 }
 // a key whose pools the library computed itself (keygen.hip: dense affine points in device memory, pool order) under a handle of its own
 int groth16_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const void* d_g1, size_t g1_points,
-                            const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle) {
+                            const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle, bool in_subgroup) {
     std::unique_ptr<Groth16Key> key;
-    ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, nullptr, g1_points, nullptr, g2_points, 0, 1, lagrange, false, d_g1, d_g2));
+    ZKCHK(groth16_key_build(key, n, m, L, R, O, mid, nullptr, g1_points, nullptr, g2_points, 0, 1, lagrange, false, d_g1, d_g2, false, in_subgroup));
     *handle = g_keys.add(std::move(key));
     return ZK_OK;
 }

@@ -59,10 +59,11 @@ struct Groth16Key {
 // Builds a key (whole: rank 0 of world 1, or rank's shard) on the CURRENT virtual device; nothing is registered under a handle.
 int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid,
                       const uint8_t* pk_g1, size_t pk_g1_points, const uint8_t* pk_g2, size_t pk_g2_points, uint32_t rank, uint32_t world, bool lagrange,
-                      bool shard_of_group = false, const void* d_g1 = nullptr, const void* d_g2 = nullptr, bool wire = false);
-// keygen.hip: a whole key from pools the library generated on the device (dense affine points, pool order), registered under a new handle
+                      bool shard_of_group = false, const void* d_g1 = nullptr, const void* d_g2 = nullptr, bool wire = false, bool device_in_subgroup = true);
+// keygen.hip, specialize.hip: a whole key from pools the library computed on the device (dense affine points, pool order), registered under a new
+// handle.  in_subgroup = false: the pools are a linear image of outside points that were not tested (ZK_KEY_SUBGROUP_CHECK=0), and the handle says so
 int groth16_key_from_device(uint32_t n, uint32_t m, const zk_csr* L, const zk_csr* R, const zk_csr* O, const uint8_t* mid, const void* d_g1, size_t g1_points,
-                            const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle);
+                            const void* d_g2, size_t g2_points, bool lagrange, uint64_t* handle, bool in_subgroup = true);
 int groth16_slot_get(Groth16Key& k, uint32_t idx, Slot** out);
 // host half of a proof's inputs (witness handed over as a host buffer, r, s) into the slot's pinned staging memory; fails when the slot is busy
 int groth16_stage_inputs(Groth16Key& k, Slot& sl, const uint8_t* sol, const uint8_t* r, const uint8_t* s);
@@ -77,6 +78,14 @@ int groth16_derive_lagrange_pools(const FrStage& f, const uint8_t* d_g1, uint64_
 // lagrange_derive.hip: dst[i] <- k[i] * src[i], dense affine points and canonical scalars on the device (dst may be src), through the derivation's three
 // passes k_aff_to_raw, k_g_tabmul, k_raw_to_aff; waits for the stream
 int points_scale_tabmul(Curve curve, void* d_dst, const void* d_src, const void* d_k, uint64_t n, hipStream_t s);
+// keygen.hip: M (n rows, m columns) -> its transpose as CSR over m rows, a counting pass on the host; ZK_ERR_ARG for a malformed M
+int transpose_csr(const zk_csr* M, uint32_t n, uint32_t m, std::vector<uint32_t>& ptr, std::vector<uint32_t>& col, std::vector<uint8_t>& val);
+// lagrange_derive.hip, for zk_groth16_pk_specialize: [l_i]_1, [alpha l_i]_1, [beta l_i]_1 from the three G1 lists of a phase-1 string (dst[q] <- the
+// derivation of src[q], n points each) and tiztd (n - 1 points) from the 2n-1 points at d_tau1 by one correlation with Z's coefficients; waits
+int specialize_g1_bases(const FrStage& f, const uint8_t* const d_src[3], uint8_t* const d_dst[3], const uint8_t* d_tau1, uint8_t* d_tiztd, hipStream_t s);
+// pts[i] <- k[i] * pts[i] on raw XYZZ G1 points (k_g_tabmul in slabs; waits), and raw XYZZ -> dense affine (k_raw_to_aff; enqueues only)
+int g1_raw_tabmul(void* d_raw, const void* d_k, uint64_t total, hipStream_t s);
+int g1_raw_to_affine(void* d_aff, const void* d_raw, uint64_t count, hipStream_t s);
 // contribute.hip: pts[i] <- k * pts[i] in place for n dense affine G1 points (device) and ONE canonical scalar (little-endian words), through
 // points_scale_tabmul over a table of equal scalars, `slab` points per chain of launches (0 = the default); waits for the stream
 int g1_scale_points(void* d_pts, uint64_t n, const uint64_t k[4], uint32_t slab, hipStream_t s);

@@ -139,7 +139,7 @@ static int power_run(void* d_out, const void* d_x, const void* d_scale, uint64_t
 
 // ------------------------------------------------------------------ 3 columns: u_k(x) through the transposed matrices
 // M (n rows, m columns) -> its transpose as CSR over m rows; validates M as the uploads do (the counting pass indexes by its columns)
-static int transpose_csr(const zk_csr* M, uint32_t n, uint32_t m, std::vector<uint32_t>& ptr, std::vector<uint32_t>& col, std::vector<uint8_t>& val) {
+int transpose_csr(const zk_csr* M, uint32_t n, uint32_t m, std::vector<uint32_t>& ptr, std::vector<uint32_t>& col, std::vector<uint8_t>& val) {
     if (!M->row_ptr) ZK_FAIL(ZK_ERR_ARG, "R1CS matrix: null row_ptr");
     for (uint32_t g = 0; g < n; g++)
         if (M->row_ptr[g] > M->row_ptr[g + 1]) ZK_FAIL(ZK_ERR_ARG, "R1CS matrix: row_ptr not monotone");

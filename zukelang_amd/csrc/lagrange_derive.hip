@@ -662,6 +662,91 @@ int derive_shifted_bases_g1(const FrStage& f, const uint8_t* d_si, uint8_t* d_ou
     return derive_set<Fp>(tn, d_si, f.n - 1, d_out, s);
 }
 
+// ---- zk_groth16_pk_specialize (specialize.hip): what the call takes from the derivation
+// src[q]: the n points [tau^i]_1, [alpha tau^i]_1, [beta tau^i]_1 of a phase-1 string (dense affine, device) -> dst[q]: [l_i]_1, [alpha l_i]_1,
+// [beta l_i]_1 -- three runs of derive_set over the SAME tables (offset 0), side by side under the rule of groth16_derive_lagrange_pools.
+// d_tau1: the 2n-1 points [tau^k]_1 -> d_tiztd[i] = sum_j z_j [tau^(i+j)]_1, i < n-1, z the n+1 coefficients of Z = prod_{i<n} (X - i) (f.z): ONE
+// correlation in the exponent, the Conv_alt^T step of a derivation with z in the place of alt.  Cyclic size 2 n2 = f.S: the inputs k = i + j <= 2n-2
+// and the wanted outputs i <= n-2 never meet a wrapped term (a product z_j x_k lands on k - j mod S, and k - j < 0 wraps to >= S - n > n - 2), so the
+// derivation's twiddle heaps serve it and no larger transform is needed.  n = 1: l_0 = 1 and there is no tiztd.  Waits for the stream.
+int specialize_g1_bases(const FrStage& f, const uint8_t* const d_src[3], uint8_t* const d_dst[3], const uint8_t* d_tau1, uint8_t* d_tiztd, hipStream_t s) {
+    const uint32_t n = f.n;
+    if (n == 1) {
+        for (int q = 0; q < 3; q++) HIPCHK(hipMemcpyAsync(d_dst[q], d_src[q], 96, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return ZK_OK;
+    }
+    const char* e_sbs = ::zk::opt("ZK_DERIVE_SIDE_BY_SIDE");
+    const bool side_by_side = e_sbs ? atoi(e_sbs) != 0 : f.log_n2 <= DERIVE_SIDE_BY_SIDE_MAX_LOG;
+    DeriveTables t0;
+    ZKCHK(derive_tables_build(t0, f, 0, s));
+    if (!side_by_side) {
+        ScopedTimer tm("specialize_derive", s);
+        for (int q = 0; q < 3; q++) ZKCHK(derive_set<Fp>(t0, d_src[q], n, d_dst[q], s));
+    } else {
+        DeriveWork wk[3];                          // before the streams, as in groth16_derive_lagrange_pools
+        SideStreams side;
+        for (hipStream_t& x : side.st) HIPCHK(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
+        for (hipEvent_t& e : side.ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ScopedTimer tm("specialize_derive", s);     // closes after the joins below: the span covers all three sets
+        HIPCHK(hipEventRecord(side.ev[0], s));
+        int rc = ZK_OK;
+        uint32_t used = 0;
+        for (int q = 0; q < 3 && rc == ZK_OK; q++) {
+            hipStream_t st = q == 0 ? s : side.st[q - 1];
+            if (q) HIPCHK(hipStreamWaitEvent(st, side.ev[0], 0));
+            rc = derive_set_enqueue<Fp>(wk[q], t0, d_src[q], n, d_dst[q], st);
+            used++;
+        }
+        for (uint32_t k = 1; k < used; k++) {
+            if (hipEventRecord(side.ev[k], side.st[k - 1]) == hipSuccess) (void)hipStreamWaitEvent(s, side.ev[k], 0);
+        }
+        const hipError_t e_sync = hipStreamSynchronize(s);
+        if (rc != ZK_OK) return rc;
+        HIPCHK(e_sync);
+    }
+    constexpr size_t XB = RawLayout<Fp>::XYZZ;
+    const uint32_t S = 2 * t0.n2, lgS = t0.log_n2 + 1;
+    DevBuf zm, zt, sc1, A, scr;
+    ZKCHK(zm.alloc(32 * (size_t)S));
+    ZKCHK(zt.alloc(32 * (size_t)S));
+    ZKCHK(sc1.alloc(32));
+    ZKCHK(A.alloc(XB * S));
+    ZKCHK(scr.alloc((size_t)16 * XB * (S < DERIVE_SLAB ? S : DERIVE_SLAB)));
+    ScopedTimer tm("specialize_correlate", s);
+    // the table: NTT_S of z at the negated frequency, times 1 / S, canonical -- built like DeriveTables::alt
+    HIPCHK(hipMemsetAsync(zm.p, 0, 32 * (size_t)S, s));
+    HIPCHK(hipMemcpyAsync(zm.p, f.z.p, 32 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
+    ZKCHK(ntt_forward(zm.p, S, lgS, s));
+    hipLaunchKernelGGL(k_inv_pow2_mont, dim3(1), dim3(64), 0, s, sc1.as<uint32_t>(), lgS);
+    hipLaunchKernelGGL(k_tab_neg_canon, g1d(S), dim3(256), 0, s, zt.as<uint32_t>(), (const uint32_t*)zm.as<uint32_t>(), lgS, (uint64_t)S, (const uint32_t*)sc1.as<uint32_t>());
+    hipLaunchKernelGGL(k_aff_to_raw<Fp>, g1d((uint64_t)S), dim3(256), 0, s, A.as<uint8_t>(), d_tau1, 2 * (uint64_t)n - 1, (uint64_t)S);
+    ZKCHK(gntt<Fp>(A.as<uint8_t>(), S, lgS, false, t0, scr.as<uint8_t>(), s));
+    ZKCHK(g_tabmul<Fp>(A.as<uint8_t>(), (const uint32_t*)zt.as<uint32_t>(), (uint64_t)S, scr.as<uint8_t>(), s));
+    ZKCHK(gntt<Fp>(A.as<uint8_t>(), S, lgS, true, t0, scr.as<uint8_t>(), s));
+    hipLaunchKernelGGL(k_raw_to_aff<Fp>, g1d((uint64_t)n - 1, 128), dim3(128), 0, s, d_tiztd, (const uint8_t*)A.as<uint8_t>(), (uint64_t)n - 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return ZK_OK;
+}
+// pts[i] <- k[i] * pts[i] for `total` G1 points in the raw XYZZ layout (device), k: canonical scalars on the device: k_g_tabmul in slabs of DERIVE_SLAB
+// with the window-table scratch it needs.  The general entries of the column sums (specialize.hip) are multiplied here, on a gathered copy.  Waits.
+int g1_raw_tabmul(void* d_raw, const void* d_k, uint64_t total, hipStream_t s) {
+    if (!total) return ZK_OK;
+    DevBuf scr;
+    ZKCHK(scr.alloc((size_t)16 * RawLayout<Fp>::XYZZ * (total < DERIVE_SLAB ? total : DERIVE_SLAB)));
+    ZKCHK(g_tabmul<Fp>((uint8_t*)d_raw, (const uint32_t*)d_k, total, scr.as<uint8_t>(), s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZK_OK;
+}
+// `count` raw XYZZ G1 points (device) -> dense affine: k_raw_to_aff, the way out of every working array of this unit.  Enqueues only.
+int g1_raw_to_affine(void* d_aff, const void* d_raw, uint64_t count, hipStream_t s) {
+    if (!count) return ZK_OK;
+    hipLaunchKernelGGL(k_raw_to_aff<Fp>, g1d(count, 128), dim3(128), 0, s, (uint8_t*)d_aff, (const uint8_t*)d_raw, count);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+
 // dst[i] <- k[i] * src[i] for dense affine points (device; dst may be src), k: canonical scalars on the device, through the three passes of a
 // derivation's scaling step: k_aff_to_raw, k_g_tabmul, k_raw_to_aff.  What zk_groth16_pk_contribute multiplies with: d1 and d2 by delta', the tail of
 // the G1 pool by 1 / delta' (contribute.hip).

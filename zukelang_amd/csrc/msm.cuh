@@ -128,6 +128,8 @@ int proof_points_to_bytes_dev(const void* d_g1, uint32_t n1, const uint32_t* off
 // bytes (device copy of host encoding) -> affine Montgomery; *d_flag |= 1 not on curve, |= 2 bad encoding.  The decoder of key lists and MSM bases: zero
 // bytes without the infinity bit are the identity here (msm_points.hip: point_decode)
 int points_bytes_to_affine(Curve curve, void* d_affine, const void* d_bytes, uint64_t n, int* d_flag, hipStream_t s);
+// host bytes -> dense affine on the device with a key upload's checks (encoding, curve, optionally the subgroup) and its verdicts; synchronises
+int points_from_bytes_checked(Curve curve, const uint8_t* host_bytes, uint64_t n, void* d_dense, bool check_subgroup, hipStream_t s);
 int points_affine_to_bytes(Curve curve, void* d_bytes, const void* d_affine, uint64_t n, hipStream_t s);
 // ---- wire form (48 / 96 B per point, to_compressed_bytes): the compressed uploads and read-backs of keys and resident bases
 // host wire bytes -> the dense affine list at d_dense (n points; a rejected point is the identity): one copy up at the compressed stride, THE decompressor

@@ -762,18 +762,18 @@ static void launch_subgroup_check(Curve curve, const void* d_dense, uint64_t n, 
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<F, SUBGROUP_ORDER>), grid, dim3(128), 0, s, (const uint8_t*)d_dense, n, d_flag, d_first);
     });
 }
-int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, uint64_t n, uint32_t c, bool precomp, hipStream_t s, bool check_subgroup) {
-    ZKCHK(bases_setup(b, curve, n, c, precomp, check_subgroup));      // folded digits only for points the [r] P = O test below has passed
-    DevBuf raw, dense, flag;
+// n encoded points (host) -> dense affine (device), checked the way a key upload checks them: encoding, curve, and -- check_subgroup -- [r] P = O.
+// The verdict of the list: ZK_ERR_ARG for an encoding, else ZK_ERR_NOT_ON_CURVE for a point off the curve or outside the subgroup.  Synchronises.
+int points_from_bytes_checked(Curve curve, const uint8_t* host_bytes, uint64_t n, void* d_dense, bool check_subgroup, hipStream_t s) {
+    DevBuf raw, flag;
     ZKCHK(raw.alloc(aff_bytes(curve) * n));
-    ZKCHK(dense.alloc(aff_bytes(curve) * n));
     ZKCHK(flag.alloc(4));
     HIPCHK(hipMemsetAsync(flag.p, 0, 4, s));
     HIPCHK(hipMemcpyAsync(raw.p, host_bytes, aff_bytes(curve) * n, hipMemcpyHostToDevice, s));
-    ZKCHK(points_bytes_to_affine(curve, dense.p, raw.p, n, flag.as<int>(), s));
+    ZKCHK(points_bytes_to_affine(curve, d_dense, raw.p, n, flag.as<int>(), s));
     if (check_subgroup) {
         ScopedTimer t("subgroup_check", s);
-        launch_subgroup_check(curve, dense.p, n, flag.as<int>(), nullptr, s);
+        launch_subgroup_check(curve, d_dense, n, flag.as<int>(), nullptr, s);
     }
     int h = 0;
     HIPCHK(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, s));
@@ -781,6 +781,13 @@ int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, ui
     if (h & 2) ZK_FAIL(ZK_ERR_ARG, "point encoding: compressed flag set or coordinate >= p");
     if (h & 1) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "a base point is not on the curve");
     if (h & 4) ZK_FAIL(ZK_ERR_NOT_ON_CURVE, "a key point is on the curve but outside the prime-order subgroup (of_bytes_exn, curve.ml:199-212)");
+    return ZK_OK;
+}
+int msm_bases_from_bytes(MsmBases& b, Curve curve, const uint8_t* host_bytes, uint64_t n, uint32_t c, bool precomp, hipStream_t s, bool check_subgroup) {
+    ZKCHK(bases_setup(b, curve, n, c, precomp, check_subgroup));      // folded digits only for points the [r] P = O test has passed
+    DevBuf dense;
+    ZKCHK(dense.alloc(aff_bytes(curve) * n));
+    ZKCHK(points_from_bytes_checked(curve, host_bytes, n, dense.p, check_subgroup, s));
     ZKCHK((curve == CURVE_G1 ? bases_finish<Fp>(b, dense.p, s) : bases_finish<Fp2>(b, dense.p, s)));
     HIPCHK(hipStreamSynchronize(s));          // `dense` is released on return: the table build has read it
     return ZK_OK;

@@ -443,6 +443,43 @@ def _prove_many(fn, handle, ws, rnd, count, in_flight, size, return_status):
     return proofs
 
 
+@dataclass
+class SRS:
+    """A phase-1 (powers of tau) string, uncompressed points: tau_g1[i] = [tau^i]_1, alpha_tau_g1[i] = [alpha tau^i]_1, beta_tau_g1[i] =
+    [beta tau^i]_1 (96 B each), beta_g2 = [beta]_2, tau_g2[i] = [tau^i]_2 (192 B each).  What Groth16.specialize turns into a circuit's key."""
+    tau_g1: np.ndarray
+    alpha_tau_g1: np.ndarray
+    beta_tau_g1: np.ndarray
+    beta_g2: bytes
+    tau_g2: np.ndarray
+
+    @staticmethod
+    def sizes(n):
+        """(points of tau_g1, of alpha_tau_g1 and beta_tau_g1 each, of tau_g2) a circuit of n constraints needs: zk_groth16_srs_sizes"""
+        return max(n + 2, 2 * n - 1), n, n + 2
+
+    @classmethod
+    def generate(cls, rng, max_n):
+        """A string for circuits of up to max_n constraints from a trapdoor drawn HERE: alpha, beta, tau in that order from `rng`, every point through
+        G1.of_Fr / G2.of_Fr.  For tests and for hosts that run their own phase 1; a ceremony's string comes from its transcript instead."""
+        P = FR_MODULUS
+        a, b, t = (rng() % P for _ in range(3))
+        n1, nab, n2 = cls.sizes(max_n)
+        pw = [1]
+        for _ in range(max(n1, n2) - 1):
+            pw.append(pw[-1] * t % P)
+        return cls(G1.of_Fr(fr_bytes(pw[:n1])), G1.of_Fr(fr_bytes([a * x % P for x in pw[:nab]])), G1.of_Fr(fr_bytes([b * x % P for x in pw[:nab]])),
+                   bytes(G2.of_Fr(fr_bytes([b]))), G2.of_Fr(fr_bytes(pw[:n2])))
+
+    def cut(self, n):
+        """The exact-size slices of a longer string for a circuit of n constraints; ValueError if the string is too short"""
+        n1, nab, n2 = self.sizes(n)
+        have = (len(self.tau_g1) // 96, len(self.alpha_tau_g1) // 96, len(self.beta_tau_g1) // 96, len(self.tau_g2) // 192)
+        if have[0] < n1 or have[1] < nab or have[2] < nab or have[3] < n2 or len(self.beta_g2) != 192:
+            raise ValueError("SRS.cut: %d constraints need %d / %d / %d / %d points, the string holds %d / %d / %d / %d" % ((n, n1, nab, nab, n2) + have))
+        return SRS(self.tau_g1[:96 * n1], self.alpha_tau_g1[:96 * nab], self.beta_tau_g1[:96 * nab], self.beta_g2, self.tau_g2[:192 * n2])
+
+
 class Groth16:
     @staticmethod
     def keygen(rng, circuit: R1CS, lagrange=False):
@@ -504,6 +541,36 @@ class Groth16:
         h = C.c_uint64()
         _lib.check(_lib.lib().zk_groth16_keygen(n, m, C.byref(L), C.byref(R), C.byref(O), _p(mid), _p(toxic), _lib.KEY_FORMS[form],
                                                 _p(g1), len(g1) // 96, _p(g2), len(g2) // 192, _p(v1), _p(v2), C.byref(h)))
+        self = cls.__new__(cls)
+        self.circuit, self.rank, self.world, self._keep, self.handle = circuit, 0, 1, (circuit,), h
+        self._ab_src = (bytes(g1[:96]), bytes(g2[:192]))
+        vk = VKey(bytes(v1[:96]), v1[96:], bytes(v2[:192]), bytes(v2[192:384]), bytes(v2[384:]),
+                  Pairing.pairing(bytes(g1[:96]), bytes(g2[:192])))        # ab = e(alpha, beta), groth16.ml:103
+        return self, PKey(g1, g2), vk
+
+    @classmethod
+    def specialize(cls, circuit: R1CS, srs: SRS, form="lagrange"):
+        """A phase-1 string specialised to `circuit` on the device (zk_groth16_pk_specialize): returns (prover, pkey, vkey) as `generate` does, for the
+        key with gamma = delta = 1 -- the setup of the trapdoor (alpha, beta, 1, 1, tau) without anybody knowing it.  `srs` holds exactly
+        SRS.sizes(circuit.n) points (SRS.cut of a longer one).  The call trusts the string: run check_key / check_lagrange_key with the returned vkey,
+        then contribute()."""
+        n, m = circuit.n, circuit.m
+        n1, nab, n2 = SRS.sizes(n)
+        lens = (len(srs.tau_g1), len(srs.alpha_tau_g1), len(srs.beta_tau_g1), len(srs.beta_g2), len(srs.tau_g2))
+        if lens != (96 * n1, 96 * nab, 96 * nab, 192, 192 * n2):
+            raise ValueError("specialize: the string must hold exactly SRS.sizes(n) points per list (SRS.cut(n) of a longer one)")
+        s1 = np.ascontiguousarray(np.concatenate([np.frombuffer(bytes(x), dtype=np.uint8) for x in (srs.tau_g1, srs.alpha_tau_g1, srs.beta_tau_g1)]))
+        s2 = np.ascontiguousarray(np.concatenate([np.frombuffer(bytes(x), dtype=np.uint8) for x in (srs.beta_g2, srs.tau_g2)]))
+        mid = np.ascontiguousarray(circuit.mid, dtype=np.uint8)
+        n_mid = int(np.count_nonzero(mid))
+        g1 = np.zeros(96 * (3 + (n + 2) + (n - 1) + n_mid), dtype=np.uint8)
+        g2 = np.zeros(192 * (2 + (n + 2)), dtype=np.uint8)
+        v1 = np.zeros(96 * (1 + m - n_mid), dtype=np.uint8)
+        v2 = np.zeros(192 * 3, dtype=np.uint8)
+        L, R, O = _csr(circuit.L), _csr(circuit.R), _csr(circuit.O)
+        h = C.c_uint64()
+        _lib.check_points(_lib.lib().zk_groth16_pk_specialize(n, m, C.byref(L), C.byref(R), C.byref(O), _p(mid), _p(s1), len(s1) // 96, _p(s2), len(s2) // 192,
+                                                              _lib.KEY_FORMS[form], _p(g1), len(g1) // 96, _p(g2), len(g2) // 192, _p(v1), _p(v2), C.byref(h)))
         self = cls.__new__(cls)
         self.circuit, self.rank, self.world, self._keep, self.handle = circuit, 0, 1, (circuit,), h
         self._ab_src = (bytes(g1[:96]), bytes(g2[:192]))
