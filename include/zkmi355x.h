@@ -424,8 +424,8 @@ int zk_groth16_pk_contribute(uint64_t handle, const uint8_t dmul[32] /* delta', 
  * subgroup part, and the handle remembers it: zk_groth16_key_check refuses it as it refuses such uploads.
  * TRUST: the call cannot know whether the string is well formed and does not try.  Whatever points it is given, the output is the linear map above
  * applied to them.  The contract is: run zk_groth16_key_check (or zk_groth16_key_check_lagrange) with the returned verification key on the result.
- * A string whose lists disagree gives a key that fails it (alpha_tau1 not alpha tau^i: bit L; a wrong high power of tau1: bit H_BASES).  A check of
- * the string itself -- the powers beyond n+1, the alpha and beta lists against tau2 -- is not part of this library.
+ * A string whose lists disagree gives a key that fails it (alpha_tau1 not alpha tau^i: bit L; a wrong high power of tau1: bit H_BASES).  The check of
+ * the string itself -- the powers beyond n+1, the alpha and beta lists against tau2 -- is zk_groth16_srs_check below: run it once on the whole string.
  * Status, in this order, everything before ZK_ERR_HIP without touching the device: ZK_ERR_ARG for a null L / R / O / mid / srs_g1 / srs_g2, an unknown
  * form, n outside [1, 2^24] (the transforms in the exponent run at 2 * 2^ceil(log2 n) <= 2^25 points, the bound of zk_groth16_keygen and of the
  * derivation) or m = 0; ZK_ERR_DOMAIN for any *_points that is not exactly the expected count; ZK_ERR_ARG for a malformed matrix or more than
@@ -437,6 +437,64 @@ int zk_groth16_pk_specialize(uint32_t n, uint32_t m, const zk_csr* L, const zk_c
                              const uint8_t* srs_g1, size_t srs_g1_points, const uint8_t* srs_g2, size_t srs_g2_points, uint32_t form,
                              uint8_t* pk_g1, size_t pk_g1_points, uint8_t* pk_g2, size_t pk_g2_points,
                              uint8_t* vk_g1 /* (1 + n_io) * 96 */, uint8_t* vk_g2 /* 3 * 192 */, uint64_t* handle);
+/* ---- a phase-1 string as a whole: the check and a contribution ------------------------------------------------------------------------------------
+ * The two stations BEFORE zk_groth16_pk_specialize.  A string has the lists and layout of that call -- srs_g1 = tau1[N1] | alpha_tau1[NAB] |
+ * beta_tau1[NAB] (96 B each), srs_g2 = beta2 | tau2[N2] (192 B each), uncompressed -- but its lengths are the caller's, not a circuit's: one long string
+ * is checked once and then cut to many circuits.  N1 >= 2, N2 >= 2, NAB >= 1; NAB <= N1 and N2 <= N1 (BETA and TAU_G2 compare against tau1[i]);
+ * N1 <= 2^25 (what zk_groth16_srs_sizes gives at n = 2^24).
+ *
+ * zk_groth16_srs_check: is this a well-formed string of SOME trapdoor (alpha, beta, tau)?  Each of the four relations is one equation between two
+ * pairing products; the sums run over all its indices with coefficients rho_i expanded from the seed (the generator and the seed contract of
+ * zk_groth16_key_check: 32 bytes drawn AFTER the string's bytes are fixed, unpredictable to whoever made it; NULL: drawn here).  g1, g2 the generators:
+ *   ZK_SRSCHK_GENERATORS  tau1[0] = g1, tau2[0] = g2                                                  byte comparison
+ *   ZK_SRSCHK_TAU_G1      tau1[i+1] = tau tau1[i], i < N1-1, tau the exponent of tau2[1]              e(sum rho_i tau1[i+1], g2) = e(sum rho_i tau1[i], tau2[1])
+ *   ZK_SRSCHK_TAU_G2      tau2[i] holds the exponent of tau1[i], i < N2                               e(sum rho_i tau1[i], g2) = e(g1, sum rho_i tau2[i])
+ *   ZK_SRSCHK_ALPHA       alpha_tau1[i+1] = tau alpha_tau1[i], i < NAB-1                              the form of TAU_G1 over alpha_tau1
+ *   ZK_SRSCHK_BETA        beta_tau1[i] = beta tau1[i], i < NAB, beta the exponent of beta2            e(sum rho_i beta_tau1[i], g2) = e(sum rho_i tau1[i], beta2)
+ *   ZK_SRSCHK_TRIVIAL     tau2[1], alpha_tau1[0] or beta2 is the identity: a component of the trapdoor is 0          identity test
+ * A relation with no index holds (ALPHA at NAB = 1); a sum over fewer than N1 points of tau1 is the long sum with zero coefficients.  A relation that
+ * fails at one index fails the check with probability 1 - 1/r.  A malformed string is a VERDICT: ZK_OK and a non-zero mask.  A bad POINT is a
+ * status: the lists are decoded in the order tau1, alpha_tau1, beta_tau1, beta2 | tau2, the first bad list decides, with the codes of
+ * zk_groth16_pk_specialize (encoding -> ZK_ERR_ARG, off the curve or outside the subgroup -> ZK_ERR_NOT_ON_CURVE).  The subgroup test ALWAYS runs, by
+ * the curves' endomorphisms, whatever ZK_KEY_SUBGROUP_CHECK says: a pairing does not see a cofactor component, so a check that skipped the test would
+ * vouch for points it had not looked at.  Zero bytes are the identity, as in every key list.
+ * Status, in this order, everything before ZK_ERR_HIP without touching the device: ZK_ERR_ARG for a null srs_g1 / srs_g2 / failed or a count below
+ * its minimum; ZK_ERR_DOMAIN for NAB > N1, N2 > N1, N1 > 2^25; ZK_ERR_HIP without a GPU; ZK_ERR_ARG on a device list of several entries; then the
+ * points.  A refused call leaves *failed as it was.  No state outlives the call.  The sums are Pippenger products over base sets built for the call
+ * WITHOUT window tables (a string is multiplied once; DESIGN 2t, profiles/srs_ab.json); the four sums over tau1 share one chain of sort and
+ * accumulate launches, the two over alpha_tau1 another.  Timer family srs_check (stages srs_check:decode, :subgroup, :sums, :pairings).
+ * One MI355X, the string of a circuit of n constraints (profiles/srs.json): 60 ms at n = 2^16, 125 ms at 2^18, 328 ms at 2^20; with tables the call
+ * at 2^18 takes 223 ms instead of 123 ms (profiles/srs_ab.json).
+ *
+ * zk_groth16_srs_contribute: the string times (alpha', beta', tau') on the device -- the step that makes a string trustworthy if ONE contributor
+ * forgets its factors:
+ *   tau1[i] tau'^i     alpha_tau1[i] alpha' tau'^i     beta_tau1[i] beta' tau'^i     beta2 beta'     tau2[i] tau'^i
+ * The identity stays the identity.  The call TRUSTS the string as zk_groth16_pk_specialize does: it applies a linear map and does not repair a
+ * malformed string (check before and after).  The points are checked like those of zk_groth16_pk_specialize; ZK_KEY_SUBGROUP_CHECK=0 is honoured
+ * here.  mul: alpha' | beta' | tau', canonical Fr bytes, the order SRS.generate draws a trapdoor in.  out_g1 / out_g2: the layouts of the inputs; each
+ * may be its input's own memory.  link_g1 = tau1[1] before | after, alpha_tau1[0] before | after, beta_tau1[0] before | after; link_g2 = [tau']_2 |
+ * [alpha']_2 | [beta']_2: three RATIOS, each shown by e(after, g2) = e(before, [x']_2).  The proof of knowledge of the factors and the transcript are
+ * the ceremony's, as for zk_groth16_pk_contribute.
+ * Status, in this order, before the device is touched: ZK_ERR_ARG for a null srs_g1 / srs_g2 / mul / out_g1 / out_g2 or a count below its minimum;
+ * ZK_ERR_DOMAIN for the lengths as above; a factor of 0 -> ZK_ERR_ARG, a factor >= r -> ZK_ERR_SCALAR_RANGE (the first bad factor in mul's order
+ * decides).  Then ZK_ERR_HIP, the device list, the points.  A refused call writes nothing.  The scalars come from the power scan of
+ * zk_groth16_keygen, the multiplications run on the kernels of zk_groth16_pk_contribute (points_scale_tabmul, both curves), [x']_2 on the fixed-base
+ * kernel; the call has no kernel of its own.  Timer family srs_contribute (stages srs_contribute:scalars, :multiply). */
+#define ZK_SRSCHK_GENERATORS 1u   /* tau1[0] is not the G1 generator or tau2[0] is not the G2 generator */
+#define ZK_SRSCHK_TAU_G1     2u   /* some i < N1-1:  tau1[i+1] != tau * tau1[i],  tau the exponent of tau2[1] */
+#define ZK_SRSCHK_TAU_G2     4u   /* some i < N2:    tau2[i] does not hold the exponent of tau1[i] */
+#define ZK_SRSCHK_ALPHA      8u   /* some i < NAB-1: alpha_tau1[i+1] != tau * alpha_tau1[i] */
+#define ZK_SRSCHK_BETA       16u  /* some i < NAB:   beta_tau1[i] != beta * tau1[i],  beta the exponent of beta2 */
+#define ZK_SRSCHK_TRIVIAL    32u  /* tau2[1], alpha_tau1[0] or beta2 is the identity: a component of the trapdoor is 0 */
+int zk_groth16_srs_check(const uint8_t* srs_g1, size_t tau1_points, size_t ab_points,
+                         const uint8_t* srs_g2, size_t tau2_points,
+                         const uint8_t seed[32] /* may be NULL: drawn here */, uint32_t* failed);
+int zk_groth16_srs_contribute(const uint8_t* srs_g1, size_t tau1_points, size_t ab_points,
+                              const uint8_t* srs_g2, size_t tau2_points,
+                              const uint8_t mul[96]  /* alpha' | beta' | tau', canonical Fr: the order SRS.generate draws */,
+                              uint8_t* out_g1, uint8_t* out_g2   /* same layouts; each may alias its input */,
+                              uint8_t link_g1[6 * 96]  /* tau1[1], alpha_tau1[0], beta_tau1[0]: before | after each; may be NULL */,
+                              uint8_t link_g2[3 * 192] /* [tau']_2 | [alpha']_2 | [beta']_2; may be NULL */);
 int zk_groth16_pk_free(uint64_t handle);
 
 /* Groth16.prove rng qap pkey sol with r, s supplied by the caller in the order the reference

@@ -269,6 +269,34 @@ module Make (C : Curve.S) = struct
     | None -> ignore (register vars (l, r, o) n pkey));
     (pkey, vkey)
 
+  (* ---------------------------------------------------------------- srs_check, srs_contribute
+     The two stations before `specialize` (zk_groth16_srs_check, zk_groth16_srs_contribute), on a string of ANY lengths: check a long string once,
+     then cut it to circuits.  srs_check returns the names of the relations that do not hold ([] = well formed); seed as for check_key.
+     srs_contribute multiplies the string by (alpha', beta', tau') on the device and returns the new lists with the link
+     (tau1[1], alpha_tau1[0], beta_tau1[0] before | after each; [tau']_2 | [alpha']_2 | [beta']_2), uncompressed.  It trusts the string: check
+     before and after. *)
+  let srs_bytes ~tau1 ~alpha_tau1 ~beta_tau1 ~beta2 ~tau2 =
+    if List.length alpha_tau1 <> List.length beta_tau1 then invalid_arg "srs: alpha_tau1 and beta_tau1 have one length";
+    (Mi355x.cat [ g1_bytes tau1; g1_bytes alpha_tau1; g1_bytes beta_tau1 ], Mi355x.cat [ G2.to_bytes beta2; g2_bytes tau2 ])
+
+  let srs_check ?(seed : bytes option) ~(tau1 : G1.t list) ~(alpha_tau1 : G1.t list) ~(beta_tau1 : G1.t list) ~(beta2 : G2.t) ~(tau2 : G2.t list) () :
+      string list =
+    let srs_g1, srs_g2 = srs_bytes ~tau1 ~alpha_tau1 ~beta_tau1 ~beta2 ~tau2 in
+    let mask =
+      Mi355x.groth16_srs_check ?seed ~srs_g1 ~tau1_points:(List.length tau1) ~ab_points:(List.length alpha_tau1) ~srs_g2 ~tau2_points:(List.length tau2) ()
+    in
+    List.filter_map (fun (name, bit) -> if mask land bit <> 0 then Some name else None) Mi355x.srschk_names
+
+  let srs_contribute ~(alpha_mul : Fr.t) ~(beta_mul : Fr.t) ~(tau_mul : Fr.t) ~(tau1 : G1.t list) ~(alpha_tau1 : G1.t list) ~(beta_tau1 : G1.t list)
+      ~(beta2 : G2.t) ~(tau2 : G2.t list) : (G1.t list * G1.t list * G1.t list * G2.t * G2.t list) * bytes * bytes =
+    let srs_g1, srs_g2 = srs_bytes ~tau1 ~alpha_tau1 ~beta_tau1 ~beta2 ~tau2 in
+    let n1 = List.length tau1 and nab = List.length alpha_tau1 and n2 = List.length tau2 in
+    let o1, o2, link_g1, link_g2 =
+      Mi355x.groth16_srs_contribute ~srs_g1 ~tau1_points:n1 ~ab_points:nab ~srs_g2 ~tau2_points:n2 ~mul:(fr_bytes [ alpha_mul; beta_mul; tau_mul ])
+    in
+    let take b at off count = List.init count (fun i -> at b (off + i)) in
+    ((take o1 g1_at 0 n1, take o1 g1_at n1 nab, take o1 g1_at (n1 + nab) nab, g2_at o2 0, take o2 g2_at 1 n2), link_g1, link_g2)
+
   (* ---------------------------------------------------------------- prove *)
 
   let prove rng (qap : qap) (pkey : pkey) (sol : f Var.Map.t) : proof =

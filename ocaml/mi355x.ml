@@ -551,6 +551,36 @@ let groth16_pk_contribute (h : Unsigned.UInt64.t) ~(dmul : bytes) : bytes * byte
   let out a = Bytes.init 192 (fun i -> CArray.get a i) in
   (out link, out dg2, out vkd)
 
+(* A phase-1 string as a whole (include/zkmi355x.h, "a phase-1 string as a whole"): srs_g1 = tau1[N1] | alpha_tau1[NAB] | beta_tau1[NAB], srs_g2 =
+   beta2 | tau2[N2], uncompressed, of the caller's lengths.  The check gives a mask (0: well formed); seed as for key_check_call.  The contribution
+   multiplies the string by mul = alpha' | beta' | tau' (96 canonical bytes) and returns (srs_g1, srs_g2, link_g1, link_g2). *)
+let zk_groth16_srs_check =
+  fn "zk_groth16_srs_check" (ptr char @-> size_t @-> size_t @-> ptr char @-> size_t @-> ptr char @-> ptr uint32_t @-> returning int)
+
+let zk_groth16_srs_contribute =
+  fn "zk_groth16_srs_contribute"
+    (ptr char @-> size_t @-> size_t @-> ptr char @-> size_t @-> ptr char @-> ptr char @-> ptr char @-> ptr char @-> ptr char @-> returning int)
+
+(* the bits of the check's mask under their names, in bit order (name first: the pairs of keychk_names above are the key check's alone) *)
+let srschk_names = [ ("generators", 1); ("tau_g1", 2); ("tau_g2", 4); ("alpha", 8); ("beta", 16); ("trivial", 32) ]
+
+let groth16_srs_check ?seed ~(srs_g1 : bytes) ~tau1_points ~ab_points ~(srs_g2 : bytes) ~tau2_points () : int =
+  let failed = allocate uint32_t Unsigned.UInt32.zero in
+  let s1 = carray_of_bytes srs_g1 and s2 = carray_of_bytes srs_g2 and sd = Option.map carray_of_bytes seed in
+  let start = function Some a -> CArray.start a | None -> null_bytes in
+  check (zk_groth16_srs_check (CArray.start s1) (sz tau1_points) (sz ab_points) (CArray.start s2) (sz tau2_points) (start sd) failed);
+  Unsigned.UInt32.to_int !@failed
+
+let groth16_srs_contribute ~(srs_g1 : bytes) ~tau1_points ~ab_points ~(srs_g2 : bytes) ~tau2_points ~(mul : bytes) : bytes * bytes * bytes * bytes =
+  let s1 = carray_of_bytes srs_g1 and s2 = carray_of_bytes srs_g2 and k = carray_of_bytes mul in
+  let n1 = Bytes.length srs_g1 and n2 = Bytes.length srs_g2 in
+  let o1 = CArray.make char n1 and o2 = CArray.make char n2 and l1 = CArray.make char (6 * 96) and l2 = CArray.make char (3 * 192) in
+  check
+    (zk_groth16_srs_contribute (CArray.start s1) (sz tau1_points) (sz ab_points) (CArray.start s2) (sz tau2_points) (CArray.start k) (CArray.start o1)
+       (CArray.start o2) (CArray.start l1) (CArray.start l2));
+  let out a len = Bytes.init len (fun i -> CArray.get a i) in
+  (out o1 n1, out o2 n2, out l1 (6 * 96), out l2 (3 * 192))
+
 let pinocchio_upload ~n ~m (l : matrix) (r : matrix) (o : matrix) ~(mid : bytes) ~(g1 : bytes) ~(g2 : bytes) : Unsigned.UInt64.t =
   let h = allocate uint64_t Unsigned.UInt64.zero in
   check

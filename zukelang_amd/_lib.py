@@ -37,6 +37,7 @@ EXPORTS = [
     "zk_groth16_key_check", "zk_groth16_key_check_lagrange",
     "zk_groth16_pk_contribute", "zk_selftest_g1_scale",
     "zk_groth16_srs_sizes", "zk_groth16_pk_specialize", "zk_selftest_g1_colsum",
+    "zk_groth16_srs_check", "zk_groth16_srs_contribute",
 ]
 
 
@@ -155,6 +156,16 @@ SPECIALIZE_PROTOTYPES = {
                                  _P8, C.c_size_t, _P8, C.c_size_t, _P8, _P8, _PH],
     "zk_selftest_g1_colsum": [_P8, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P8, C.c_uint32, _P8],
 }
+# a phase-1 string checked as a whole and contributed to (tests/test_srs_surface.py holds them to the header).  A table of their own:
+# tests/test_specialize_surface.py holds SPECIALIZE_PROTOTYPES to exactly its three entries.
+SRS_PROTOTYPES = {
+    "zk_groth16_srs_check": [_P8, C.c_size_t, C.c_size_t, _P8, C.c_size_t, _P8, C.POINTER(C.c_uint32)],
+    "zk_groth16_srs_contribute": [_P8, C.c_size_t, C.c_size_t, _P8, C.c_size_t, _P8, _P8, _P8, _P8, _P8],
+}
+# the bits of zk_groth16_srs_check's mask (ZK_SRSCHK_*), in bit order, under the names SRS.check reports
+SRSCHK_BITS = {
+    "generators": 1, "tau_g1": 2, "tau_g2": 4, "alpha": 8, "beta": 16, "trivial": 32,
+}
 # the bits of zk_groth16_key_check's mask (ZK_KEYCHK_*), in bit order, under the names Groth16.check_key reports
 KEYCHK_BITS = {
     "generators": 1, "tau_g1": 2, "tau_g2": 4, "beta": 8, "delta": 16, "h_bases": 32, "l": 64, "gamma": 128,
@@ -175,7 +186,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.zk_strerror.restype = C.c_char_p
         _lib.zk_last_error.restype = C.c_char_p
-        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(FP29_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()) + list(KEY_CHECK_LAGRANGE_PROTOTYPES.items()) + list(CONTRIBUTE_PROTOTYPES.items()) + list(SPECIALIZE_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(VK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + list(PIN_FOLD_PROTOTYPES.items()) + list(COMPRESSED_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + list(FP_PAIR_PROTOTYPES.items()) + list(FR_PROTOTYPES.items()) + list(FP29_PROTOTYPES.items()) + list(KEY_WIRE_PROTOTYPES.items()) + list(PROVE_MANY_PROTOTYPES.items()) + list(KEY_CHECK_PROTOTYPES.items()) + list(KEY_CHECK_LAGRANGE_PROTOTYPES.items()) + list(CONTRIBUTE_PROTOTYPES.items()) + list(SPECIALIZE_PROTOTYPES.items()) + list(SRS_PROTOTYPES.items()):
             fn = getattr(_lib, name, None)          # absent from the host-only sanitizer build (ZK_LIBZKMI355X_PATH); calling a missing entry still raises
             if fn is not None:
                 fn.argtypes, fn.restype = args, C.c_int

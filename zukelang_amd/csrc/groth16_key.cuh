@@ -6,6 +6,7 @@
 #include "msm.cuh"
 
 #include <memory>
+#include <vector>
 
 namespace zk {
 
@@ -80,6 +81,8 @@ int groth16_derive_lagrange_pools(const FrStage& f, const uint8_t* d_g1, uint64_
 int points_scale_tabmul(Curve curve, void* d_dst, const void* d_src, const void* d_k, uint64_t n, hipStream_t s);
 // keygen.hip: M (n rows, m columns) -> its transpose as CSR over m rows, a counting pass on the host; ZK_ERR_ARG for a malformed M
 int transpose_csr(const zk_csr* M, uint32_t n, uint32_t m, std::vector<uint32_t>& ptr, std::vector<uint32_t>& col, std::vector<uint8_t>& val);
+// keygen.hip: out[i] = scale * x^i for i < cnt (k_power_run; x, scale and out in Montgomery form on the device, scale == nullptr: 1); enqueues only
+int power_run(void* d_out, const void* d_x, const void* d_scale, uint64_t cnt, hipStream_t s, const char* family = "keygen_powers");
 // lagrange_derive.hip, for zk_groth16_pk_specialize: [l_i]_1, [alpha l_i]_1, [beta l_i]_1 from the three G1 lists of a phase-1 string (dst[q] <- the
 // derivation of src[q], n points each) and tiztd (n - 1 points) from the 2n-1 points at d_tau1 by one correlation with Z's coefficients; waits
 int specialize_g1_bases(const FrStage& f, const uint8_t* const d_src[3], uint8_t* const d_dst[3], const uint8_t* d_tau1, uint8_t* d_tiztd, hipStream_t s);
@@ -94,6 +97,9 @@ int g1_scale_points(void* d_pts, uint64_t n, const uint64_t k[4], uint32_t slab,
 int groth16_key_check(Groth16Key& k, const uint8_t* vk_g1, size_t n_io, const uint8_t* vk_g2, const uint8_t* seed, uint32_t* failed);
 // the same for zk_groth16_key_check_lagrange: a Lagrange-form key held whole on one device
 int groth16_key_check_lagrange(Groth16Key& k, const uint8_t* vk_g1, size_t n_io, const uint8_t* vk_g2, const uint8_t* seed, uint32_t* failed);
+// key_check.hip: product q = the pairs lens[0] + .. + lens[q-1] onwards, lens[q] of them, of P (96 B each) and Q (192 B each), host bytes of points the
+// caller has checked or summed itself -> gt: 576 B per product (pairing_products_device); waits.  The key checks and zk_groth16_srs_check compare them.
+int keychk_pairing_products(const std::vector<uint8_t>& P, const std::vector<uint8_t>& Q, const std::vector<uint64_t>& lens, std::vector<uint8_t>& gt, hipStream_t s);
 void groth16_shard_range(uint64_t points, uint64_t heavy, uint32_t rank, uint32_t world, uint64_t* lo, uint64_t* hi);
 
 // ---- multi-device keys (groth16_multi.hip): one shard per entry of the device list behind ONE handle

@@ -11,9 +11,9 @@
 // zk_groth16_key_check_lagrange, the same for a Lagrange-form handle, follows it below: other relations, the same shape.
 #include "ec.cuh"
 #include "groth16_key.cuh"
+#include "seed_expand.cuh"
 #include "verdict_order.h"
 
-#include <random>
 #include <string.h>
 #include <vector>
 
@@ -21,24 +21,12 @@ namespace zk {
 
 static inline dim3 g1d(uint64_t n, unsigned t = 256) { return dim3((unsigned)((n + t - 1) / t)); }
 
-struct KeychkSeed { uint64_t w[4]; };
-// out[i]: pseudo-random canonical scalars below 2^254.  Limb q (64 bits) of every scalar is a splitmix64 stream of its own, keyed by bytes 8q .. 8q+7 of
-// the seed: all 256 bits of the seed reach the scalars.  Elements from mu_first on are the per-variable coefficients mu_k; with zero_io those of the
-// variables outside mids are 0 (no verification key: their points are not in the proving key).
+// out[i]: the seed's expansion (seed_expand.cuh: pseudo-random canonical scalars below 2^254).  Elements from mu_first on are the per-variable
+// coefficients mu_k; with zero_io those of the variables outside mids are 0 (no verification key: their points are not in the proving key).
 __global__ void k_keychk_expand(uint32_t* __restrict__ out, uint64_t count, uint64_t mu_first, const uint8_t* __restrict__ is_mid, int zero_io, KeychkSeed seed) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    Fr r;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        uint64_t x = seed.w[q] + (i + 1) * 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        x ^= x >> 31;
-        r.v[2 * q] = (uint32_t)x;
-        r.v[2 * q + 1] = (uint32_t)(x >> 32);
-    }
-    r.v[7] &= 0x3fffffffu;
+    Fr r = seed_expand_at(seed, i);
     if (zero_io && i >= mu_first && !is_mid[i - mu_first]) r = fe_zero<FrParams>();
     fe_store<FrParams>(out + 8 * i, r);
 }
@@ -102,7 +90,7 @@ static inline bool is_identity_bytes(const uint8_t* p) { return (p[0] & 0x40) !=
 // Product q = the pairs lens[0] + .. + lens[q-1] onwards, lens[q] of them, of P (96 B each) and Q (192 B each) -> gt: 576 B per product; waits.
 // The products of zk_pairing_product_many without its point checks: every point here is a key point the upload checked (in_subgroup), a point of the
 // verification key the caller checked, or a sum of such points -- [r] P = O on sixteen pairs would cost more than all the Miller loops.
-static int keychk_pairing_products(const std::vector<uint8_t>& P, const std::vector<uint8_t>& Q, const std::vector<uint64_t>& lens, std::vector<uint8_t>& gt, hipStream_t s) {
+int keychk_pairing_products(const std::vector<uint8_t>& P, const std::vector<uint8_t>& Q, const std::vector<uint64_t>& lens, std::vector<uint8_t>& gt, hipStream_t s) {
     const uint32_t count = (uint32_t)lens.size();
     gt.resize(576 * (size_t)count);
     std::vector<uint32_t> off(count + 1, 0);
@@ -128,7 +116,7 @@ static int keychk_pairing_products(const std::vector<uint8_t>& P, const std::vec
     HIPCHK(hipMemcpyAsync(&hf, flag.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(gt.data(), dgt.p, gt.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (hf) ZK_FAIL(ZK_ERR_HIP, "zk_groth16_key_check: a point of the check's own making does not decode");
+    if (hf) ZK_FAIL(ZK_ERR_HIP, "a point of the check's own making does not decode");
     return ZK_OK;
 }
 
@@ -140,12 +128,7 @@ int groth16_key_check(Groth16Key& k, const uint8_t* vk_g1, size_t n_io, const ui
     Ctx& c = ctx();
     hipStream_t s = c.stream;
     HIPCHK(hipGetLastError());
-    KeychkSeed sd;
-    if (seed) memcpy(sd.w, seed, 32);
-    else {
-        std::random_device rd;
-        for (int q = 0; q < 4; q++) sd.w[q] = ((uint64_t)rd() << 32) | (uint64_t)rd();
-    }
+    const KeychkSeed sd = seed_take(seed);
     // which variable has its point where: mids in the key's ltd_mid (mid_idx), the others in the verification key's ltgm_io, both in variable order
     std::vector<uint32_t> mids(n_mid ? n_mid : 1), io_idx;
     if (n_mid) HIPCHK(hipMemcpy(mids.data(), k.mid_idx.p, 4 * (size_t)n_mid, hipMemcpyDeviceToHost));
@@ -371,12 +354,7 @@ int groth16_key_check_lagrange(Groth16Key& k, const uint8_t* vk_g1, size_t n_io,
     Ctx& c = ctx();
     hipStream_t s = c.stream;
     HIPCHK(hipGetLastError());
-    KeychkSeed sd;
-    if (seed) memcpy(sd.w, seed, 32);
-    else {
-        std::random_device rd;
-        for (int q = 0; q < 4; q++) sd.w[q] = ((uint64_t)rd() << 32) | (uint64_t)rd();
-    }
+    const KeychkSeed sd = seed_take(seed);
     // which variable has its point where: mids in the key's ltd_mid (mid_idx), the others in the verification key's ltgm_io, both in variable order
     std::vector<uint32_t> mids(n_mid ? n_mid : 1), io_idx;
     if (n_mid) HIPCHK(hipMemcpy(mids.data(), k.mid_idx.p, 4 * (size_t)n_mid, hipMemcpyDeviceToHost));

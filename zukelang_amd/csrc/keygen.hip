@@ -129,9 +129,9 @@ __global__ void k_power_run(uint32_t* __restrict__ out, const uint32_t* __restri
         acc = fe_mul(acc, xs);
     }
 }
-static int power_run(void* d_out, const void* d_x, const void* d_scale, uint64_t cnt, hipStream_t s) {
+int power_run(void* d_out, const void* d_x, const void* d_scale, uint64_t cnt, hipStream_t s, const char* family) {
     if (!cnt) return ZK_OK;
-    ScopedTimer t("keygen_powers", s);
+    ScopedTimer t(family, s);
     hipLaunchKernelGGL(k_power_run, g1d((cnt + KCH - 1) / KCH, 64), dim3(64), 0, s, (uint32_t*)d_out, (const uint32_t*)d_x, (const uint32_t*)d_scale, cnt);
     HIPCHK(hipGetLastError());
     return ZK_OK;

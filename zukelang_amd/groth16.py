@@ -479,6 +479,119 @@ class SRS:
             raise ValueError("SRS.cut: %d constraints need %d / %d / %d / %d points, the string holds %d / %d / %d / %d" % ((n, n1, nab, nab, n2) + have))
         return SRS(self.tau_g1[:96 * n1], self.alpha_tau_g1[:96 * nab], self.beta_tau_g1[:96 * nab], self.beta_g2, self.tau_g2[:192 * n2])
 
+    def _lists(self, what):
+        """(srs_g1, N1, NAB, srs_g2, N2) as the C calls take a string; ValueError for lists that are no whole points or of unequal alpha / beta lengths"""
+        t1, a1, b1, t2 = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (self.tau_g1, self.alpha_tau_g1, self.beta_tau_g1, self.tau_g2))
+        b2 = np.frombuffer(bytes(self.beta_g2), dtype=np.uint8)
+        if len(t1) % 96 or len(a1) % 96 or len(a1) != len(b1) or len(b2) != 192 or len(t2) % 192:
+            raise ValueError("%s: the lists are whole uncompressed points, alpha_tau_g1 and beta_tau_g1 of one length, beta_g2 one G2 point" % what)
+        return np.ascontiguousarray(np.concatenate([t1, a1, b1])), len(t1) // 96, len(a1) // 96, np.ascontiguousarray(np.concatenate([b2, t2])), len(t2) // 192
+
+    def check(self, seed=None):
+        """Is this a well-formed string of SOME trapdoor, over all its points (zk_groth16_srs_check: one random combination per relation on the device)?
+        Returns an SRSCheck: .ok, .failed (the mask) and .names.  A malformed string is a verdict, not an exception; a point that does not decode, is
+        off the curve or outside the subgroup raises ValueError.  seed: 32 bytes; None draws them from os.urandom here, after the string's bytes are
+        fixed -- a caller that passes its own takes over that contract.  Check a long string once, then cut() it to circuits."""
+        import os
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("SRS.check: the seed is 32 bytes")
+        s1, n1, nab, s2, n2 = self._lists("SRS.check")
+        failed = C.c_uint32(0)
+        _lib.check_points(_lib.lib().zk_groth16_srs_check(_p(s1), n1, nab, _p(s2), n2, _p(np.frombuffer(seed, dtype=np.uint8)), C.byref(failed)))
+        return SRSCheck(failed.value)
+
+    def contribute(self, mul=None):
+        """A phase-1 contribution on the device (zk_groth16_srs_contribute): the string of the trapdoor (alpha alpha', beta beta', tau tau').  mul =
+        (alpha', beta', tau'), each 0 < x < r; None draws them from os.urandom here and FORGETS them on return -- a string is sound when one
+        contributor did.  Returns (SRS, SRSContribution).  The call trusts the string: check() before and after."""
+        import os
+        if mul is None:
+            mul = []
+            while len(mul) < 3:
+                x = int.from_bytes(os.urandom(64), "little") % FR_MODULUS
+                if x:
+                    mul.append(x)
+        mul = [int(x) for x in mul]
+        if len(mul) != 3 or any(x < 0 or x >= 1 << 256 for x in mul):
+            raise ValueError("SRS.contribute: mul is three elements of Fr: alpha', beta', tau'")
+        s1, n1, nab, s2, n2 = self._lists("SRS.contribute")
+        k = np.frombuffer(b"".join(x.to_bytes(32, "little") for x in mul), dtype=np.uint8)
+        o1, o2 = np.zeros(len(s1), dtype=np.uint8), np.zeros(len(s2), dtype=np.uint8)
+        l1, l2 = np.zeros(6 * 96, dtype=np.uint8), np.zeros(3 * 192, dtype=np.uint8)
+        _lib.check_points(_lib.lib().zk_groth16_srs_contribute(_p(s1), n1, nab, _p(s2), n2, _p(k), _p(o1), _p(o2), _p(l1), _p(l2)))
+        out = SRS(o1[:96 * n1], o1[96 * n1:96 * (n1 + nab)], o1[96 * (n1 + nab):], bytes(o2[:192]), o2[192:])
+        pt = lambda j: bytes(l1[96 * j:96 * j + 96])
+        q = lambda j: bytes(l2[192 * j:192 * j + 192])
+        return out, SRSContribution(pt(0), pt(1), pt(2), pt(3), pt(4), pt(5), q(0), q(1), q(2))
+
+    def link_points(self):
+        """(tau_g1[1], alpha_tau_g1[0], beta_tau_g1[0]): the three points a chain of SRSContribution links starts from and ends at"""
+        return bytes(self.tau_g1[96:192]), bytes(self.alpha_tau_g1[:96]), bytes(self.beta_tau_g1[:96])
+
+
+class SRSCheck:
+    """The verdict of SRS.check: .failed is zk_groth16_srs_check's mask, .names the relations that do not hold, in bit order, .ok whether there is none."""
+
+    def __init__(self, failed):
+        self.failed = int(failed)
+        self.names = [name for name, bit in _lib.SRSCHK_BITS.items() if self.failed & bit]
+        self.ok = self.failed == 0
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "SRSCheck(ok)" if self.ok else "SRSCheck(failed=%s)" % "|".join(self.names)
+
+
+@dataclass
+class SRSContribution:
+    """What SRS.contribute returns beside the new string (uncompressed points): tau_g1[1], alpha_tau_g1[0] and beta_tau_g1[0] before and after, and
+    [tau']_2, [alpha']_2, [beta']_2.  A link of verify_srs_contributions."""
+    tau_before: bytes
+    tau_after: bytes
+    alpha_before: bytes
+    alpha_after: bytes
+    beta_before: bytes
+    beta_after: bytes
+    tau_g2: bytes
+    alpha_g2: bytes
+    beta_g2: bytes
+
+
+def verify_srs_contributions(first, links, last):
+    """Do these links lead from the string `first` to the string `last`?  first / last: an SRS or its link_points(); links: one SRSContribution per
+    contribution, in order.  True when, for each of tau_g1[1], alpha_tau_g1[0] and beta_tau_g1[0], every link satisfies e(after, g2) = e(before,
+    [x']_2) (zk_pairing_check on the host: three checks of two pairings per link; it also refuses points off the curve or outside the subgroup), the
+    first link starts at `first`, each link starts where the one before it ended, the last ends at `last`, and no point is the identity.  An empty
+    chain holds when the points of first and last are equal.
+
+    As for verify_contributions: a link shows three RATIOS.  It does not show that the contributor knew its factors, that the chain is the one a
+    ceremony agreed on, nor that either string is well formed (SRS.check does that).  Those are the caller's protocol."""
+    cur = tuple(bytes(x) for x in (first.link_points() if isinstance(first, SRS) else first))
+    end = tuple(bytes(x) for x in (last.link_points() if isinstance(last, SRS) else last))
+    if len(cur) != 3 or len(end) != 3 or any(len(x) != 96 for x in cur + end) or any(_is_identity(x) for x in cur):
+        return False
+    for link in links:
+        before = (bytes(link.tau_before), bytes(link.alpha_before), bytes(link.beta_before))
+        after = (bytes(link.tau_after), bytes(link.alpha_after), bytes(link.beta_after))
+        g2 = (bytes(link.tau_g2), bytes(link.alpha_g2), bytes(link.beta_g2))
+        if any(len(x) != 96 for x in before + after) or any(len(x) != 192 for x in g2):
+            return False
+        if before != cur or any(_is_identity(x) for x in after + g2):
+            return False
+        for b, a, x2 in zip(before, after, g2):
+            one = C.c_int(0)
+            try:
+                _lib.check(_lib.lib().zk_pairing_check(a + _g1_negate(b), _G2_ONE + x2, C.c_size_t(2), C.byref(one)))
+            except _lib.ZkError:
+                return False
+            if not one.value:
+                return False
+        cur = after
+    return cur == end
+
 
 class Groth16:
     @staticmethod
