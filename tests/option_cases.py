@@ -1,20 +1,43 @@
-"""The public options of libzkmi355x (csrc/zk_api.hip: PUBLIC_OPTIONS) and how the suite holds each of them to the oracle -- TEST INFRASTRUCTURE ONLY.
+"""The public options of libzkmi355x (the PUBLIC rows of csrc/zk_options.h) and how the suite holds each of them to the oracle -- TEST INFRASTRUCTURE ONLY.
 
 include/zkmi355x.h (zk_set_option) promises that no public knob changes a result.  CASES has one row per public name: the values to exercise (every
 branch its parse site tells apart), where the library reads it, and the companion settings a value needs to reach its branch.  tests/test_option_cases.py
-(CPU) keeps the table equal to PUBLIC_OPTIONS and the `read` column equal to the read sites; tests/test_gpu_options.py (GPU) runs it.  ROUTES, further
-down, has one row per way to make a handle: tests/test_gpu_options_routes.py (GPU) runs CASES through every one of them.
+(CPU) keeps the table equal to the PUBLIC rows of csrc/zk_options.h (option_table below reads them) and the `read` column true to each row's kind;
+tests/test_gpu_options.py (GPU) runs it.  ROUTES, further down, has one row per way to make a handle: tests/test_gpu_options_routes.py (GPU) runs CASES
+through every one of them.
 
-read:
-  "cached" -- a function-local static (ZK_ENV, or `static const ... = ::zk::opt(...)`): fixed at first use, so only a fresh process reaches another value
-              (CACHED_GROUPS below, one child process per group).
-  "setup"  -- read when a key is uploaded, a slot's workspaces are allocated or a key is derived: set before the upload, live in one process.
-  "call"   -- read per call (ZK_FORM_ENV under ZK_TEST_FORMS=1, which tests/conftest.py sets, or a plain ::zk::opt on a per-call path).
+read:    from the row's kind in csrc/zk_options.h
+  "cached" -- a CACHED row: fixed at its first read, so only a fresh process reaches another value (CACHED_GROUPS below, one child process per group).
+  "setup"  -- a LIVE row read when a key is uploaded, a slot's workspaces are allocated or a key is derived: set before the upload, live in one process.
+  "call"   -- read per call: a FORM row (under ZK_TEST_FORMS=1, which tests/conftest.py sets), or a LIVE row on a per-call path.
 size:    "small" -- Groth16 at 2^12, Pinocchio at n = 1000;  "ba" -- both at 2^14, where the automatic batch-affine rounds start.
 multi:   also run on the device lists [0, 0] and [0, 0, 0] (the one card listed several times, as tests/test_gpu_multidevice.py does).
 special: "msm_api" -- reached through zk_msm_g1 / zk_msm_g2 against the oracle's naive fold instead of through a proof.
 """
+import os
+import re
 from collections import namedtuple
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zukelang_amd", "csrc")
+OPTIONS_UNIT = "zk_options.h"
+# every way a unit of the library touches an option (csrc/zk_options.h): any opt_*( call, whatever its argument, or one of the three named readers.
+# Groups: the opt_* function, the row's id where the argument is a literal one, the named reader.
+OPTION_READ = re.compile(r"\b(?:(opt_\w+)\s*\(\s*(?:OPT_([A-Z0-9_]+))?|(key_subgroup_check|trace_on|forms_live)\s*\()")
+OptionRow = namedtuple("OptionRow", "id name kind visibility")
+
+
+def option_table():
+    """the rows of csrc/zk_options.h, in order"""
+    text = open(os.path.join(CSRC, OPTIONS_UNIT)).read()
+    rows = [OptionRow(*m) for m in re.findall(r'^\s*ZK_OPTION\(\s*(\w+)\s*,\s*"(ZK_[A-Z0-9_]+)"\s*,\s*(\w+)\s*,\s*(\w+)\s*\)', text, flags=re.M)]
+    assert rows and all(r.name == "ZK_" + r.id and r.kind in ("CACHED", "LIVE", "FORM") and r.visibility in ("PUBLIC", "INTERNAL", "ENV_ONLY") for r in rows)
+    assert len({r.name for r in rows}) == len(rows), "a name listed twice in zk_options.h"
+    return rows
+
+
+def public_options():
+    return [r.name for r in option_table() if r.visibility == "PUBLIC"]
+
 
 Case = namedtuple("Case", "values read with_ size multi special")
 

@@ -4,7 +4,7 @@ point patterns against the oracle's naive fold, Groth16 proofs of random sizes a
 (power-form and Lagrange-form keys).  Test infrastructure (it uses the oracle); not collected by pytest.
 Usage: python tests/soak_parity.py [seconds] [seed]"""
 import os, random, sys, time
-os.environ.setdefault("ZK_TEST_FORMS", "1")      # before the library loads: kernel-form switches (ZK_FR_RNS ...) are read per call, not cached (csrc/zk_common.h)
+os.environ.setdefault("ZK_TEST_FORMS", "1")      # before the library loads: kernel-form switches (ZK_FR_RNS ...) are read per call, not cached (csrc/zk_options.h: FORM rows)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))      # ROOT = repo root (this file lives in tests/)
 import numpy as np

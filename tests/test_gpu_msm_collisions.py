@@ -65,7 +65,7 @@ def test_the_restated_plan_is_the_librarys():
                  "FIXUP_SERIAL_MAX = %d;" % FIXUP_SERIAL_MAX, "DW_POINTS = %d;" % DW_POINTS):
         assert line in tail, line
     msm = open(os.path.join(ROOT, "zukelang_amd", "csrc", "msm.hip")).read()
-    assert re.search(r'chunk_min = ::zk::opt\("ZK_MSM_CHUNK_MIN"\) \? [^;]* : %d;' % CHUNK, msm) and "ZK_MSM_CHUNK_MIN" not in os.environ
+    assert "chunk_min = (uint32_t)opt_int(OPT_MSM_CHUNK_MIN, %d);" % CHUNK in msm and "ZK_MSM_CHUNK_MIN" not in os.environ
     assert "const bool wide = dp.nd0 > DW_POINTS;" in msm
     red = open(os.path.join(ROOT, "zukelang_amd", "csrc", "msm_red.hip")).read()
     tl = open(os.path.join(ROOT, "zukelang_amd", "csrc", "msm_tail.hip")).read()

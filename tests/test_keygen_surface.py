@@ -8,6 +8,7 @@ import re
 
 import numpy as np
 
+import option_cases
 from zukelang_amd import _lib
 from zukelang_amd import r1cs as RC
 from zukelang_amd.groth16 import _csr, _p
@@ -237,9 +238,7 @@ def test_h_lagrange_fixture_is_first_principles_and_the_header_is_the_json():
 
 
 def test_no_new_public_option():
-    api = open(os.path.join(ROOT, "zukelang_amd", "csrc", "zk_api.hip")).read()
-    table = api[api.index("PUBLIC_OPTIONS[] = {"):]
-    names = re.findall(r'"(ZK_[A-Z0-9_]+)"', table[:table.index("};")])
+    names = option_cases.public_options()
     assert len(names) == 28 and not any("KEYGEN" in n or "KEY_FORM" in n for n in names)
     src = open(os.path.join(ROOT, "zukelang_amd", "csrc", "keygen.hip")).read()
-    assert "ZK_ENV(" not in src and "getenv" not in src and "opt(" not in src          # ZK_PIN_COMPACT_H / ZK_PIN_SHARED_SORT through pinocchio.hip's helpers
+    assert not option_cases.OPTION_READ.search(src) and "getenv" not in src          # ZK_PIN_COMPACT_H / ZK_PIN_SHARED_SORT through pinocchio.hip's helpers

@@ -1,4 +1,4 @@
-"""CPU guard of the option table (tests/option_cases.py): one row per public option of csrc/zk_api.hip, the `read` column true to the C sources,
+"""CPU guard of the option table (tests/option_cases.py): one row per PUBLIC row of csrc/zk_options.h, the `read` column true to each row's kind,
 and every name accepted by zk_set_option.  A knob added without a parity case, a row deleted, or a knob newly cached fails here, without a GPU.
 The same for the route table (ROUTES): every entry point of include/zkmi355x.h that makes, fills or uses a handle has a row or a reason, the
 verifiers' lack of one is true to their sources, and the key-check route's batch-affine rows reach their rounds."""
@@ -8,11 +8,10 @@ import re
 
 from zukelang_amd import _lib
 
-from option_cases import (CACHED_GROUPS, CASES, EXEMPT, FLIPS, KEY_CHECK_POOLS, PROVE_ROUTE, ROUTED_WORDS, ROUTES, VERIFIER_SOURCES, live_runs,
-                          route_settings)
+from option_cases import (CACHED_GROUPS, CASES, CSRC, EXEMPT, FLIPS, KEY_CHECK_POOLS, OPTION_READ, OPTIONS_UNIT, PROVE_ROUTE, ROUTED_WORDS, ROUTES,
+                          VERIFIER_SOURCES, live_runs, option_table, public_options, route_settings)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zukelang_amd", "csrc")
 
 
 def _strip_comments(text):
@@ -20,28 +19,20 @@ def _strip_comments(text):
     return re.sub(r"//[^\n]*", "", text)
 
 
-def public_options():
-    text = open(os.path.join(CSRC, "zk_api.hip")).read()
-    m = re.search(r"PUBLIC_OPTIONS\[\]\s*=\s*\{(.*?)\};", text, flags=re.S)
-    assert m, "PUBLIC_OPTIONS not found in zk_api.hip"
-    names = re.findall(r'"([A-Z0-9_]+)"', _strip_comments(m.group(1)))
-    assert len(names) == len(set(names)), "a name listed twice in PUBLIC_OPTIONS"
-    return names
-
-
 def read_sites():
-    """name -> set of read kinds found in the sources: "cached" (ZK_ENV, or a function-local static initialised from ::zk::opt), "form" (ZK_FORM_ENV)"""
+    """name -> the units of csrc/ outside the options unit that read it, by the row's id or through one of the named readers of csrc/zk_options.h"""
+    named = {"key_subgroup_check": ["ZK_KEY_SUBGROUP_CHECK"], "trace_on": ["ZK_TRACE"], "forms_live": ["ZK_TEST_FORMS"],
+             "opt_form_fingerprint": [r.name for r in option_table() if r.kind == "FORM" and r.name != "ZK_GRAPH"]}
     sites = {}
-    files = glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cuh"))
-    for f in files:
-        code = _strip_comments(open(f).read())
-        for name in re.findall(r'(?<![A-Za-z0-9_])ZK_ENV\(\s*"(ZK_[A-Z0-9_]+)"\s*\)', code):
-            sites.setdefault(name, set()).add("cached")
-        for stmt in re.findall(r"\bstatic\s+const\b[^;{}]*?=[^;]*;", code):
-            for name in re.findall(r'::zk::opt\(\s*"(ZK_[A-Z0-9_]+)"\s*\)', stmt):
-                sites.setdefault(name, set()).add("cached")
-        for name in re.findall(r'\bZK_FORM_ENV\(\s*"(ZK_[A-Z0-9_]+)"\s*\)', code):
-            sites.setdefault(name, set()).add("form")
+    for f in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cuh")) + glob.glob(os.path.join(CSRC, "*.h"))):
+        if os.path.basename(f) == OPTIONS_UNIT:
+            continue
+        for fn, by_id, reader in OPTION_READ.findall(_strip_comments(open(f).read())):
+            if fn == "opt_set":
+                continue                                                 # zk_set_option itself (zk_api.hip): a write, by name
+            assert by_id or reader or fn in named, "%s: %s( is handed something other than a row's literal id" % (os.path.basename(f), fn)
+            for name in (["ZK_" + by_id] if by_id else named[reader or fn]):
+                sites.setdefault(name, set()).add(os.path.basename(f))
     return sites
 
 
@@ -58,21 +49,38 @@ def test_the_table_has_one_row_per_public_option():
 
 
 def test_every_cached_read_is_marked_cached():
+    rows = {r.name: r for r in option_table()}
     sites = read_sites()
-    public = set(public_options())
     # the scan itself must find the known sites (a regex that matches nothing would pass everything below)
-    assert "cached" in sites.get("ZK_SLOT_STREAMS", ()) and "cached" in sites.get("ZK_SORT_SCALAR_MAJOR", ())
-    assert "cached" in sites.get("ZK_MSM_TARGET_THREADS", ()) and "form" in sites.get("ZK_TAIL_SLOTS", ())
-    for name, kinds in sorted(sites.items()):
-        if name not in public:
-            continue                                                 # test-only and experiment switches have no row
-        if "cached" in kinds:
-            assert CASES[name].read == "cached", "%s is read once per process (ZK_ENV / static): mark it cached and give it a child-process group" % name
-        elif "form" in kinds:
-            assert CASES[name].read == "call", "%s is a kernel-form switch (ZK_FORM_ENV): read per call under ZK_TEST_FORMS=1" % name
+    assert {"groth16.hip", "pinocchio.hip"} <= sites["ZK_SERIAL_STREAMS"] and sites["ZK_SLOT_STREAMS"] == {"groth16.hip"} and sites["ZK_SORT_SCALAR_MAJOR"] == {"msm_sort.hip"}
+    assert sites["ZK_MSM_TARGET_THREADS"] == {"msm.hip"} and {"msm.hip", "groth16.hip"} <= sites["ZK_TAIL_SLOTS"] and sites["ZK_GRAPH"] == {"groth16.hip"}
+    assert len(sites["ZK_KEY_SUBGROUP_CHECK"]) == 5 and sites["ZK_TRACE"] == {"zk_api.hip", "ctx_tables.h", "groth16_multi.hip"}
+    assert rows["ZK_SLOT_STREAMS"].kind == "CACHED" and rows["ZK_TAIL_SLOTS"].kind == "FORM" and rows["ZK_MSM_WINDOW"].kind == "LIVE"
     for name, c in CASES.items():
-        if c.read == "cached":
-            assert "cached" in sites.get(name, ()), "%s is marked cached but no cached read site was found" % name
+        kind = rows[name].kind
+        assert (kind == "CACHED") == (c.read == "cached"), "%s is %s in zk_options.h: a row read once per process is marked cached and has a child-process group, no other is" % (name, kind)
+        if kind == "FORM":
+            assert c.read == "call", "%s is a kernel-form switch: read per call under ZK_TEST_FORMS=1" % name
+        if kind == "LIVE":
+            assert c.read in ("setup", "call"), name
+    for r in rows.values():
+        assert sites.get(r.name), "%s has a row in zk_options.h and no unit reads it" % r.name
+    assert set(sites) <= set(rows), "read by an id that is no row: %s" % sorted(set(sites) - set(rows))
+
+
+def test_only_the_options_unit_reads_by_name():
+    """no getenv and no "ZK_..." literal handed to a reader outside csrc/zk_options.h; names inside error texts ("... must be ZK_KEY_FORM_...") are not reads"""
+    seen = 0
+    for f in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cuh")) + glob.glob(os.path.join(CSRC, "*.h")):
+        code = _strip_comments(open(f).read())
+        seen += len(re.findall(r'"ZK_[A-Z0-9_]+"', code))
+        if os.path.basename(f) == OPTIONS_UNIT:
+            assert "getenv(" in code                                     # the scan does find what is there
+            continue
+        assert not re.search(r"\bgetenv\s*\(", code), "%s calls getenv: options are read through csrc/zk_options.h" % os.path.basename(f)
+        hits = re.findall(r'\b\w+\s*\(\s*"ZK_[A-Z0-9_]+"\s*[,)]', code)
+        assert not hits, "%s hands an option's name to %s: read it by its id (csrc/zk_options.h)" % (os.path.basename(f), hits)
+    assert seen >= 34
 
 
 def test_every_cached_value_runs_in_a_child_process():
@@ -131,9 +139,9 @@ def test_the_verifiers_read_no_option():
     """why they have no route; if one of them ever reads a knob, they get one"""
     for name in VERIFIER_SOURCES:
         code = _strip_comments(open(os.path.join(CSRC, name)).read())
-        for word in ("::zk::opt", "ZK_ENV", "ZK_FORM_ENV"):
-            assert word not in code, "%s reads an option (%s): the verifiers need a row in option_cases.ROUTES" % (name, word)
-    assert "::zk::opt" in _strip_comments(open(os.path.join(CSRC, "msm.hip")).read())          # the scan does find what is there
+        m = OPTION_READ.search(code)
+        assert not m and '#include "zk_options.h"' not in code, "%s reads an option (%s): the verifiers need a row in option_cases.ROUTES" % (name, m and m.group(0))
+    assert OPTION_READ.search(_strip_comments(open(os.path.join(CSRC, "msm.hip")).read()))          # the scan does find what is there
 
 
 def test_the_key_check_route_reaches_the_automatic_batch_affine_rounds():

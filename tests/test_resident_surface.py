@@ -4,12 +4,12 @@ import inspect
 import os
 import re
 
+import option_cases
 from zukelang_amd import _lib, curve
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "zkmi355x.h")).read()
 SEAM = open(os.path.join(ROOT, "ocaml", "bls12_381_mi355x.ml")).read()
-API = open(os.path.join(ROOT, "zukelang_amd", "csrc", "zk_api.hip")).read()
 
 PROTOS = {
     "zk_bases_upload": "int zk_bases_upload(int group, const uint8_t* points, size_t n, uint64_t* handle);",
@@ -71,11 +71,9 @@ def test_ocaml_seam_memoises_physically_and_calls_the_resident_product():
 
 
 def test_no_new_public_option():
-    table = API[API.index("PUBLIC_OPTIONS[] = {"):]
-    table = table[:table.index("};")]
-    names = re.findall(r'"(ZK_[A-Z0-9_]+)"', table)
+    names = option_cases.public_options()
     assert len(names) == 28
     assert not any("RESIDENT" in n or "SHORT" in n for n in names)
     src = open(os.path.join(ROOT, "zukelang_amd", "csrc", "msm_resident.hip")).read()
-    assert "ZK_ENV(" not in src and "getenv" not in src
-    assert re.findall(r'opt\("([A-Z0-9_]+)"\)', src) == ["ZK_KEY_SUBGROUP_CHECK"]
+    assert "getenv" not in src
+    assert [m.group(0) for m in option_cases.OPTION_READ.finditer(src)] == ["key_subgroup_check("]

@@ -232,7 +232,7 @@ def test_the_new_kernels_live_in_their_own_unit_and_the_derivation_is_unchanged(
         assert fn in text, fn
     derive = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "lagrange_derive.hip")).read())
     body = derive[derive.index("int specialize_g1_bases("):derive.index("int g1_raw_tabmul(")]
-    for k in ("derive_set<Fp>", "derive_set_enqueue<Fp>", "gntt<Fp>", "g_tabmul<Fp>", "k_tab_neg_canon", "ZK_DERIVE_SIDE_BY_SIDE"):
+    for k in ("derive_set<Fp>", "derive_set_enqueue<Fp>", "gntt<Fp>", "g_tabmul<Fp>", "k_tab_neg_canon", "OPT_DERIVE_SIDE_BY_SIDE"):
         assert k in body, k
 
 

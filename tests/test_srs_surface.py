@@ -212,8 +212,8 @@ def test_the_new_unit_reuses_the_existing_kernels():
     # the check's subgroup test does not read the option; the contribution's does
     chk = text[text.index("static int srs_check_run("):text.index("static constexpr uint64_t SRS_SCALE_SLAB")]
     con = text[text.index("static int srs_contribute_run("):]
-    assert "ZK_KEY_SUBGROUP_CHECK" not in chk and 'srs_decode(srs_g1, srs_g2, n1, nab, n2, true, "srs_check"' in chk
-    assert "ZK_KEY_SUBGROUP_CHECK" in con
+    assert "key_subgroup_check()" not in chk and "OPT_" not in chk and 'srs_decode(srs_g1, srs_g2, n1, nab, n2, true, "srs_check"' in chk
+    assert "key_subgroup_check()" in con
 
 
 def test_the_documents_point_to_the_calls():

@@ -1,6 +1,6 @@
 """The batched verifiers' surface without a GPU: include/zkmi355x.h, _lib.EXPORTS, the ctypes prototypes and the OCaml stubs name the same calls with
 the same argument lists; argument checks come before the device (a null pointer is ZK_ERR_ARG, count = 0 is ZK_OK and touches nothing); without a
-GPU every call is ZK_ERR_HIP (there is no CPU fallback); the Python functions exist and refuse lists that do not match; PUBLIC_OPTIONS is untouched.
+GPU every call is ZK_ERR_HIP (there is no CPU fallback); the Python functions exist and refuse lists that do not match; the public options are untouched.
 What the calls compute is held to the host verifiers on the GPU: tests/test_gpu_pairing.py, tests/test_gpu_verify_many.py."""
 import ctypes as C
 import os
@@ -160,9 +160,8 @@ def test_python_functions_exist_and_refuse_mismatched_lengths():
 
 
 def test_public_options_are_unchanged():
-    text = open(os.path.join(ROOT, "zukelang_amd", "csrc", "zk_api.hip")).read()
-    names = re.findall(r'"(ZK_[A-Z0-9_]+)"', re.search(r"PUBLIC_OPTIONS\[\]\s*=\s*\{(.*?)\};", text, flags=re.S).group(1))
+    names = option_cases.public_options()
     assert len(names) == 28 and sorted(names) == sorted(option_cases.CASES)
     assert not [n for n in names if "VERIFY" in n or "PAIRING" in n]
     dev = open(os.path.join(ROOT, "zukelang_amd", "csrc", "pairing_dev.hip")).read() + open(os.path.join(ROOT, "zukelang_amd", "csrc", "pairing_tower.cuh")).read()
-    assert "ZK_ENV(" not in dev and "opt(" not in dev          # the batched verifiers read no knob
+    assert not option_cases.OPTION_READ.search(dev)          # the batched verifiers read no knob

@@ -1,6 +1,6 @@
 """The resident verification keys' surface without a GPU: include/zkmi355x.h, _lib.EXPORTS, _lib.VK_PROTOTYPES and the OCaml stubs name the same seven
 calls with the same argument lists; argument checks come before the device; without a GPU every upload is ZK_ERR_HIP (no CPU fallback, so no handle
-can exist) and a handle of 0 is ZK_ERR_HANDLE; the Python objects exist and refuse lists that do not match; PUBLIC_OPTIONS is untouched.
+can exist) and a handle of 0 is ZK_ERR_HANDLE; the Python objects exist and refuse lists that do not match; the public options are untouched.
 What the calls compute is held to the batched and the host verifiers on the GPU: tests/test_gpu_verify_resident.py, tests/test_gpu_subgroup_endo.py."""
 import ctypes as C
 import os
@@ -194,8 +194,7 @@ def test_python_objects_exist_and_refuse_mismatched_lengths():
 
 
 def test_public_options_are_unchanged():
-    text = open(os.path.join(ROOT, "zukelang_amd", "csrc", "zk_api.hip")).read()
-    names = re.findall(r'"(ZK_[A-Z0-9_]+)"', re.search(r"PUBLIC_OPTIONS\[\]\s*=\s*\{(.*?)\};", text, flags=re.S).group(1))
+    names = option_cases.public_options()
     assert len(names) == 28 and sorted(names) == sorted(option_cases.CASES)
     new = open(os.path.join(ROOT, "zukelang_amd", "csrc", "verify_resident.hip")).read()
-    assert "ZK_ENV(" not in new and "opt(" not in new          # the resident path reads no knob
+    assert not option_cases.OPTION_READ.search(new)          # the resident path reads no knob

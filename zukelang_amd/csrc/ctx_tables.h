@@ -15,6 +15,8 @@
 #include <stdlib.h>
 #include <vector>
 
+#include "zk_options.h"
+
 namespace zk {
 
 // The capacity a request is served with: the table's floor, or the request itself.
@@ -23,8 +25,7 @@ static inline uint32_t ctx_table_log_cap(uint32_t want_log, uint32_t floor_log) 
 // ZK_TRACE=1 (diagnostics, environment only): one line on stderr per growth, "[zk tables] <what>: 2^<from> -> 2^<to>, <n> retired" (from 0: the first
 // table).  tests/test_gpu_live_together.py reads the lines of its child processes: a scenario that is meant to move a table shows that it did.
 static inline void ctx_table_trace(const char* what, uint32_t from_log, uint32_t to_log, size_t retired) {
-    static const bool on = getenv("ZK_TRACE") != nullptr;
-    if (on) {
+    if (trace_on()) {
         fprintf(stderr, "[zk tables] %s: 2^%u -> 2^%u, %zu retired\n", what, from_log, to_log, retired);
         fflush(stderr);
     }

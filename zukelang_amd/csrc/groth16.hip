@@ -124,9 +124,8 @@ int groth16_slot_get(Groth16Key& k, uint32_t idx, Slot** out) {
         // Slot 0 -- the slot of the synchronous zk_groth16_prove -- keeps two more streams and forks onto them while it is the ONLY
         // proof in flight: the G2 product's latency-bound reduction chain then runs beside the G1 products instead of in front of
         // them (single-proof latency; with other proofs in flight it stays on one stream like every other slot).
-        const char* ss = ZK_ENV("ZK_SLOT_STREAMS");
-        const bool want3 = !k.one_stream_slots && (ss ? atoi(ss) >= 3 : idx == 0);
-        if (ZK_ENV("ZK_SERIAL_STREAMS") || !want3) {
+        const bool want3 = !k.one_stream_slots && (opt_is_set(OPT_SLOT_STREAMS) ? opt_int(OPT_SLOT_STREAMS, 0) >= 3 : idx == 0);
+        if (opt_is_set(OPT_SERIAL_STREAMS) || !want3) {
             sl->s1 = sl->s2 = sl->s0;
             sl->serial = true;
         } else {
@@ -151,7 +150,7 @@ int groth16_slot_get(Groth16Key& k, uint32_t idx, Slot** out) {
 // proof, at 2^16 -6 %: both stay at 16 (profiles/r04_window_17_ab.txt).
 // Without the subgroup check there are no folded digits (msm.cuh: msm_fold), and 17 bits without them are 16 windows over twice the buckets of 16 bits.
 static uint32_t key_window(uint64_t g1_points, bool in_subgroup) {
-    if (::zk::opt("ZK_MSM_WINDOW")) return 0;          // bases_setup reads it
+    if (opt_is_set(OPT_MSM_WINDOW)) return 0;          // bases_setup reads it
     if (g1_points >= ((uint64_t)1 << 21)) return 20;
     if (g1_points >= ((uint64_t)1 << 20)) return in_subgroup ? 17 : 16;
     return msm_auto_window(g1_points, true);
@@ -192,11 +191,8 @@ int groth16_key_build(std::unique_ptr<Groth16Key>& out, uint32_t n, uint32_t m, 
     // in this rank's G1 pool (n >= ~2^19.6 on one GPU) 20-bit windows: 13 instead of 16 digits per scalar pay for the 16x
     // bucket count and the two-level sort (measured, profiles/r02_window_sweep_*.json: +7.5 % at 2^20, +12 % at 2^22, -2 % at
     // 2^19, -16 % at 2^18); round 4: 17-bit windows, fifteen of them, from 2^20 points (key_window above).  ZK_MSM_WINDOW overrides (config 3's sweep).
-    // key points are checked like the reference checks them on the way in (of_bytes_exn: encoding, curve, prime-order subgroup); ZK_KEY_SUBGROUP_CHECK=0
-    // (zk_set_option "key_subgroup_check") skips the subgroup part for keys that were checked before (it is [r] P = O per point: 0.3 s at 2^20
-    // constraints, 1.4 s at 2^22).  Read per key (set-up path).  A key uploaded without the check never gets folded windows: msm.cuh.
-    const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    const bool chk = generated ? device_in_subgroup : !(e_chk && atoi(e_chk) == 0);
+    // key points from outside are checked on the way in unless ZK_KEY_SUBGROUP_CHECK=0 (zk_options.h: key_subgroup_check)
+    const bool chk = generated ? device_in_subgroup : key_subgroup_check();
     const uint32_t cw = key_window(k.hi1 - k.lo1, chk);
     if (generated) {
         // in_subgroup = true without the [r] P = O test, and so folded windows (msm.cuh: msm_fold): every point of a generated key is [e] G for an
@@ -289,7 +285,7 @@ int groth16_scalars_enqueue(Groth16Key& k, Slot& sl, const uint8_t* sol, const u
 static bool runs_serial(Groth16Key& k, Slot& sl) {
     bool serial = sl.serial;
     if (ctx().profiling >= 2) serial = true;      // the per-family event timers want un-overlapped launches (bench.py's one-proof-in-flight pass)
-    if (!serial && !ZK_ENV("ZK_SLOT_STREAMS"))
+    if (!serial && !opt_is_set(OPT_SLOT_STREAMS))
         for (uint32_t i = 0; i < MAX_SLOTS; i++)
             if (k.slots[i] && k.slots[i].get() != &sl && k.slots[i]->busy) serial = true;
     return serial;
@@ -341,18 +337,12 @@ int groth16_msms_enqueue(Groth16Key& k, Slot& sl, const void* dA, const void* dC
 }
 // Enqueues one whole proof on the slot's streams and returns without waiting.
 static int prove_enqueue(Groth16Key& k, Slot& sl, const uint8_t* sol, const uint8_t* r, const uint8_t* s, bool raw) {
-    const char* eg = ZK_FORM_ENV("ZK_GRAPH");              // cached; per proof only under ZK_TEST_FORMS=1 (tests switch it inside one process)
-    const bool graphs = eg && atoi(eg) != 0;
+    const bool graphs = opt_on(OPT_GRAPH, false);          // cached; per proof only under ZK_TEST_FORMS=1 (tests switch it inside one process)
     if (graphs && !ctx().profiling) {
         // The captured launches freeze the kernel forms that were selected at capture time.  Outside test mode the form switches cannot change (they are
         // cached); under ZK_TEST_FORMS=1 a slot's graphs are dropped whenever the switches differ from the ones they were captured under.
         if (forms_live()) {
-            uint64_t h = 1469598103934665603ull;
-            for (const char* name : {"ZK_TAIL_SLOTS", "ZK_TAIL_FIXUP_SLOTS", "ZK_FIXUP_BY_CHUNK", "ZK_ACC_G1_GLDS", "ZK_ACC_G1_MMADD", "ZK_ACC_G2_INLINE", "ZK_RED_WAVES", "ZK_SORT_FINE_STAGED", "ZK_SORT_COARSE_STAGED", "ZK_DS_WIDE_GROUP", "ZK_FR_RNS"}) {
-                const char* v = ::zk::opt(name);
-                for (const char* q = v ? v : "\x01"; *q; q++) h = (h ^ (uint8_t)*q) * 1099511628211ull;
-                h = (h ^ 0xff) * 1099511628211ull;
-            }
+            const uint64_t h = opt_form_fingerprint();
             if (h != sl.graph_forms) {
                 for (hipGraphExec_t& g : sl.graph)
                     if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -447,8 +437,7 @@ int zk_groth16_pk_upload_compressed(uint32_t n, uint32_t m, const zk_csr* L, con
     if (form != ZK_KEY_FORM_TAU_POWERS && form != ZK_KEY_FORM_LAGRANGE) ZK_FAIL(ZK_ERR_ARG, "zk_groth16_pk_upload_compressed: form must be ZK_KEY_FORM_TAU_POWERS or ZK_KEY_FORM_LAGRANGE");
     const int rc = upload(n, m, L, R, O, mid, pk_g1, pk_g1_points, pk_g2, pk_g2_points, 0, 1, handle, form == ZK_KEY_FORM_LAGRANGE, true, true);
     if (rc != ZK_ERR_ARG && rc != ZK_ERR_NOT_ON_CURVE) return rc;
-    const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    const bool chk = !(e_chk && atoi(e_chk) == 0);
+    const bool chk = key_subgroup_check();
     DeviceScope ds(0);
     int first = points_wire_check(CURVE_G1, pk_g1, pk_g1_points, chk, ctx().stream);
     if (first == ZK_OK) first = points_wire_check(CURVE_G2, pk_g2, pk_g2_points, chk, ctx().stream);

@@ -103,8 +103,7 @@ template <class F> static int on_every_device(size_t count, F f) {
 }
 
 static void trace(const char* what) {
-    static const bool on = getenv("ZK_TRACE") != nullptr;          // diagnostics: environment only
-    if (on) {
+    if (trace_on()) {          // diagnostics: environment only
         fprintf(stderr, "[zk multi] %s\n", what);
         fflush(stderr);
     }

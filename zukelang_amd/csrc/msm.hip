@@ -78,10 +78,10 @@ static uint32_t ba_rounds_for(const MsmBases& b, uint32_t nbuckets) {
     // (bit 0: G1, bit 1: G2).  Default: none -- measured on MI355X: the rounds re-read what they add from HBM, ~1 KB
     // per G1 addition in round 0 (two random 128-byte-line gathers of each table entry), and lose to the register-resident XYZZ
     // accumulate for G1; for G2 they break even.  Read per workspace, not cached: tests switch it.
-    const int forced = ::zk::opt("ZK_MSM_BA_ROUNDS") ? atoi(::zk::opt("ZK_MSM_BA_ROUNDS")) : -1;
+    const int forced = opt_int(OPT_MSM_BA_ROUNDS, -1);
     if (forced == 0) return 0;
     if (forced > 0) return forced > 24 ? 24 : (uint32_t)forced;
-    const int curves = ::zk::opt("ZK_MSM_BA_CURVES") ? atoi(::zk::opt("ZK_MSM_BA_CURVES")) : 0;
+    const int curves = opt_int(OPT_MSM_BA_CURVES, 0);
     if (!(curves & (b.curve == CURVE_G1 ? 1 : 2))) return 0;
     const uint64_t mean = b.n * b.nw / nbuckets;
     uint32_t r = 0;
@@ -96,9 +96,9 @@ int msm_workspace_alloc(MsmWorkspace& w, const MsmBases& b, uint64_t max_nonzero
     // >= 2 waves per SIMD when there is enough work; chunks of at least 16 entries (with a dozen proofs in flight the
     // chip is full anyway, and every chunk boundary costs a partial sum to store and to fix up: 8 -> 16 is +2.5 % proofs/s
     // at 2^16, 16..24 measure the same, 32 and up lose to the tail of the longest chunk)
-    static const uint64_t target_threads = ::zk::opt("ZK_MSM_TARGET_THREADS") ? (uint64_t)atoll(::zk::opt("ZK_MSM_TARGET_THREADS")) : 256 * 1024;   // tuning knob
+    const uint64_t target_threads = opt_u64(OPT_MSM_TARGET_THREADS, 256 * 1024);   // tuning knob
     uint32_t chunk = (uint32_t)((maxN + target_threads - 1) / target_threads);
-    static const uint32_t chunk_min = ::zk::opt("ZK_MSM_CHUNK_MIN") ? (uint32_t)atoi(::zk::opt("ZK_MSM_CHUNK_MIN")) : 16;   // tuning knob
+    const uint32_t chunk_min = (uint32_t)opt_int(OPT_MSM_CHUNK_MIN, 16);   // tuning knob
     if (launch_entries && chunk >= 64) {            // short chunks (small keys) already fill whole rounds: at 2^16, 2 rounds of 16-entry chunks beat 1 round of 32; 48 instead of 64 (the G2 product of a 2^20 key: one round of 208 instead of four of 52) measures the same
         // The caller knows how many sorted entries ONE accumulate launch carries (several products over these bases, e.g. Groth16's A and C):
         // cut it into a WHOLE number of rounds of the chip's resident lanes (256 CUs x 4 SIMDs x ACC_WAVES_G1 = ACC_WAVES_G2 = 2 waves x 64 lanes, half as many
@@ -125,8 +125,8 @@ int msm_workspace_alloc(MsmWorkspace& w, const MsmBases& b, uint64_t max_nonzero
     // single-level sort below), but its 128 KiB per workgroup evict the accumulate workgroups of the other proofs in flight from every compute unit
     // the sort runs on: two levels (2 KiB + 20 KiB of LDS) measure +1.6 % proofs/s at 2^16, +1.9 % at 2^18 with the same single-proof latency.
     // ZK_SORT_TWO_LEVEL=0: never (A/B; above 2^15 buckets that is the global-atomic sort); ZK_SORT_TWO_LEVEL_MIN: log2 of the pair threshold.
-    const int two_level = ::zk::opt("ZK_SORT_TWO_LEVEL") ? atoi(::zk::opt("ZK_SORT_TWO_LEVEL")) : 1;
-    const int two_level_min = ::zk::opt("ZK_SORT_TWO_LEVEL_MIN") ? atoi(::zk::opt("ZK_SORT_TWO_LEVEL_MIN")) : (w.nbuckets > 2 * SORT_MAX_BUCKETS ? 22 : 20);          // 2^16 buckets (c = 17) sort in two levels from 2^20 pairs like 2^15
+    const int two_level = opt_int(OPT_SORT_TWO_LEVEL, 1);
+    const int two_level_min = opt_int(OPT_SORT_TWO_LEVEL_MIN, w.nbuckets > 2 * SORT_MAX_BUCKETS ? 22 : 20);          // 2^16 buckets (c = 17) sort in two levels from 2^20 pairs like 2^15
     if (b.precomp && w.nbuckets >= SORT_MAX_BUCKETS && w.nbuckets / COARSE_BINS <= SORT_MAX_FINE && maxN >= ((uint64_t)1 << two_level_min) && two_level != 0) {
         w.sort_fine_bits = ceil_log2(w.nbuckets / COARSE_BINS);
         uint64_t wgs = maxN / (4 * (uint64_t)COARSE_BINS);
@@ -141,7 +141,7 @@ int msm_workspace_alloc(MsmWorkspace& w, const MsmBases& b, uint64_t max_nonzero
         // tuning knob.  With scalar-major passes 8 workgroups already beat the global atomics (2^16: 37.3 -> 38.7-39.4 M constraints/s, the
         // sort 0.61 -> 0.45 ms per proof; below 8 -- pools of 2^14 constraints -- the global path wins: 23.6 M against 22.3-22.6); it was 64
         // with window-major passes
-        static const uint64_t min_wgs = ::zk::opt("ZK_SORT_MIN_WGS") ? (uint64_t)atoll(::zk::opt("ZK_SORT_MIN_WGS")) : 8;
+        const uint64_t min_wgs = opt_u64(OPT_SORT_MIN_WGS, 8);
         if (wgs >= min_wgs) {                               // below that too few workgroups: the global-atomic path is cheaper
             w.sort_wgs = (uint32_t)wgs;
             ZKCHK(w.wgcount.alloc(4 * (size_t)w.nbuckets * wgs));
@@ -286,24 +286,20 @@ int msm_reduce_mixed(const MsmBases* b1, MsmWorkspace* const* ws1, void* const* 
     // (msm_tail.cuh).  ZK_TAIL_SLOTS = 0 / 1 forces one form of the digit sums, ZK_TAIL_FIXUP_SLOTS = 1 puts the fix-up on slots (A/B runs, latency-first
     // deployments).  Digit sums -> product: always msm_tail.hip.
     // (cached; read per call only under ZK_TEST_FORMS=1, where the GPU suite flips them inside one process to hold every form to the oracle)
-    const char* e_sums = ZK_FORM_ENV("ZK_TAIL_SLOTS");
-    const char* e_fix = ZK_FORM_ENV("ZK_TAIL_FIXUP_SLOTS");
-    const char* e_chunk = ZK_FORM_ENV("ZK_FIXUP_BY_CHUNK");
-    const int force = e_sums ? atoi(e_sums) : -1, force_fixup = e_fix ? atoi(e_fix) : -1;
+    const int force = opt_int(OPT_TAIL_SLOTS, -1), force_fixup = opt_int(OPT_TAIL_FIXUP_SLOTS, -1);
+    const bool by_chunk_ok = opt_on(OPT_FIXUP_BY_CHUNK, true);      // A/B switch
     const bool sums_on_slots = force < 0 ? !wide : force != 0;
     if (force_fixup > 0) {                                 // default: lanes at every width (fewer instructions: +1.5 % proofs/s at 2^16, +0.8 % at 2^18; slots: -0.3 ms of a lone 2^18 proof)
         ZKCHK(msm_tail_fixup_slots(jobs, count, n2, max_nb, s));
     } else {
         ScopedTimer t1("msm_reduce:fixup", s);
         // one worker per bucket, or per chunk border where those are fewer (msm_red.hip: k_msm_fixup)
-        const bool by_chunk_ok = !(e_chunk && atoi(e_chunk) == 0);      // A/B switch
         ZKCHK(msm_red_fixup_launch(jobs, count, n2, by_chunk_ok && max_chunks < max_nb, by_chunk_ok && max_chunks < max_nb ? max_chunks : max_nb, max_nb, s));
     }
     if (sums_on_slots) {
         ZKCHK(msm_tail_digit_sums_slots(jobs, count, n2, nwin, b.c, s));
     } else {
-        const char* e_wg = ZK_FORM_ENV("ZK_DS_WIDE_GROUP");          // a kernel-form switch like the ones above
-        const uint32_t wg_env = e_wg ? (uint32_t)atoi(e_wg) : 0;
+        const uint32_t wg_env = (uint32_t)opt_int(OPT_DS_WIDE_GROUP, 0);          // a kernel-form switch like the ones above
         ScopedTimer t2("msm_reduce:digit_sums", s);
         ZKCHK(msm_red_digit_sums_launch(jobs, count, n2, nwin, dp, wide, wg_env, s));
     }
@@ -353,7 +349,7 @@ static int msm_api(Curve curve, const uint8_t* bases, size_t nbases, const uint8
     MsmWorkspace w;
     // ZK_MSM_API_PRECOMP=1 runs this entry point through the resident-key machinery (window tables, one bucket set, batch-affine
     // rounds): how the tests reach those kernels with adversarial base sets (duplicates, negations, the identity)
-    const bool precomp = ::zk::opt("ZK_MSM_API_PRECOMP") && atoi(::zk::opt("ZK_MSM_API_PRECOMP")) != 0;
+    const bool precomp = opt_on(OPT_MSM_API_PRECOMP, false);
     ZKCHK(msm_bases_from_bytes(b, curve, bases, nscalars, window_bits, precomp, c.stream));
     ZKCHK(msm_workspace_alloc(w, b));
     DevBuf sc, res, flag;

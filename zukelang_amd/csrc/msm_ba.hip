@@ -5,11 +5,6 @@
 
 namespace zk {
 
-static uint64_t env_u64(const char* name, uint64_t dflt) {
-    const char* e = ::zk::opt(name);
-    return e ? (uint64_t)atoll(e) : dflt;
-}
-
 int msm_batch_affine_rounds(const MsmBases& b, MsmWorkspace* const* ws, uint32_t count, uint32_t rounds, hipStream_t s) {
     if (!rounds) return ZK_OK;
     const uint32_t nb = ws[0]->nbuckets;
@@ -25,8 +20,8 @@ int msm_batch_affine_rounds(const MsmBases& b, MsmWorkspace* const* ws, uint32_t
     hipLaunchKernelGGL(k_ba_plan, dim3(rounds, count), dim3(1024), 0, s, pj, nb);
     // lanes per round: L additions per lane share one inversion; few lanes when a single proof owns the chip would leave it
     // empty, many lanes make the inversion expensive per addition -- both knobs are measured defaults
-    static const uint64_t target_lanes = env_u64("ZK_BA_TARGET_LANES", 16384);
-    static const uint64_t lmin = env_u64("ZK_BA_LMIN", 16), lmax = env_u64("ZK_BA_LMAX", 128);
+    const uint64_t target_lanes = opt_u64(OPT_BA_TARGET_LANES, 16384);
+    const uint64_t lmin = opt_u64(OPT_BA_LMIN, 16), lmax = opt_u64(OPT_BA_LMAX, 128);
     for (uint32_t r = 0; r < rounds; r++) {
         BaJobs j{};
         for (uint32_t i = 0; i < count; i++) {

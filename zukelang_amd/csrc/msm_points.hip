@@ -637,8 +637,7 @@ int msm_bases_dense(const MsmBases& b, uint64_t lo, uint64_t count, void* d_dens
 static int bases_setup(MsmBases& b, Curve curve, uint64_t n, uint32_t c, bool precomp, bool in_subgroup) {
     if (n == 0) ZK_FAIL(ZK_ERR_ARG, "msm: empty base set");
     if (c == 0) {
-        const char* e = ::zk::opt("ZK_MSM_WINDOW");         // window-size sweeps (BASELINE config 3); key set-up, not a per-proof path
-        c = e ? (uint32_t)atoi(e) : msm_auto_window(n, precomp);
+        c = (uint32_t)opt_int(OPT_MSM_WINDOW, (int)msm_auto_window(n, precomp));         // window-size sweeps (BASELINE config 3); key set-up, not a per-proof path
     }
     if (c < 2 || c > 22) ZK_FAIL(ZK_ERR_ARG, "msm: window_bits must be in [2, 22]");
     b.curve = curve; b.n = n; b.c = c; b.precomp = precomp; b.in_subgroup = in_subgroup; b.fold = msm_fold(c, precomp, in_subgroup); b.nw = msm_windows(c, b.fold);

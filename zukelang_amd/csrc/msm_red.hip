@@ -184,9 +184,8 @@ template <int WG, int WAVES> __global__ __launch_bounds__(DS_THREADS, WAVES) voi
     else digit_sums_body<Fp2H, DS_THREADS, WG>(jobs.j[blockIdx.z], p, lds);
 }
 
-static uint32_t red_waves() {          // a kernel-FORM switch: cached, read per call only under ZK_TEST_FORMS=1 (zk_common.h)
-    const char* e = ZK_FORM_ENV("ZK_RED_WAVES");
-    const uint32_t w = e ? (uint32_t)atoi(e) : RED_WAVES_DEFAULT;
+static uint32_t red_waves() {          // a kernel-form switch: cached, read per call only under ZK_TEST_FORMS=1 (zk_options.h)
+    const uint32_t w = (uint32_t)opt_int(OPT_RED_WAVES, RED_WAVES_DEFAULT);
     return w == 1 || w == 2 ? w : RED_WAVES_DEFAULT;
 }
 int msm_red_fixup_launch(const TailJobs& jobs, uint32_t count, uint32_t n2, bool by_chunk, uint64_t workers, uint32_t max_nb, hipStream_t s) {

@@ -223,8 +223,7 @@ static int res_upload(int group, const uint8_t* points, size_t n, uint64_t* hand
     r.n = n;
     // the key uploads' checks (groth16.hip, pinocchio.hip): encoding, curve, [r] P = O unless ZK_KEY_SUBGROUP_CHECK=0 -- read here, once: the
     // handle keeps this verdict (without it no table folds)
-    const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    const bool chk = !(e_chk && atoi(e_chk) == 0);
+    const bool chk = key_subgroup_check();
     if (wire) ZKCHK(msm_bases_from_wire(r.b, r.curve, points, n, msm_auto_window(n, true), true, s, chk));
     else ZKCHK(msm_bases_from_bytes(r.b, r.curve, points, n, msm_auto_window(n, true), true, s, chk));
     r.short_max = r.curve == CURVE_G1 ? RESIDENT_SHORT_MAX_G1 : RESIDENT_SHORT_MAX_G2;

@@ -532,10 +532,10 @@ int msm_sort_launch(const MsmBases& b, MsmWorkspace* const* ws, const void* cons
     const uint32_t nbw = 1u << (b.c - 1);
     // scalar-major LDS sorts need ONE bucket set (resident keys: every window files into the same 2^(c-1) buckets); ZK_SORT_SCALAR_MAJOR=0 restores
     // the window-major ranges
-    static const bool want_sm = !(::zk::opt("ZK_SORT_SCALAR_MAJOR") && atoi(::zk::opt("ZK_SORT_SCALAR_MAJOR")) == 0);
+    const bool want_sm = opt_on(OPT_SORT_SCALAR_MAJOR, true);
     const bool sm = want_sm && b.precomp && w.sort_wgs != 0;
 #ifdef ZK_EXPERIMENTS
-    static const uint32_t alias = (::zk::opt("ZK_EXPERIMENT_TABLE_ALIAS") && atoi(::zk::opt("ZK_EXPERIMENT_TABLE_ALIAS"))) ? 1u : 0u;
+    const uint32_t alias = opt_on(OPT_EXPERIMENT_TABLE_ALIAS, false) ? 1u : 0u;
 #else
     const uint32_t alias = 0u;
 #endif
@@ -561,14 +561,13 @@ int msm_sort_launch(const MsmBases& b, MsmWorkspace* const* ws, const void* cons
             gc.y = count;
             hipLaunchKernelGGL(k_sort_colscan, gc, dim3(256), 0, s, l1, bins, w.sort_wgs);
             hipLaunchKernelGGL(k_scan, dim3(count), dim3(1024), 0, s, l1, bins);
-            const char* e_cs = ZK_FORM_ENV("ZK_SORT_COARSE_STAGED");          // a kernel-form switch (zk_common.h)
-            const bool coarse_staged = sm && (e_cs ? atoi(e_cs) != 0 : SORT_COARSE_STAGED_DEFAULT);
+            const bool want_cs = opt_on(OPT_SORT_COARSE_STAGED, SORT_COARSE_STAGED_DEFAULT);          // a kernel-form switch (zk_options.h), read whatever sm says
+            const bool coarse_staged = sm && want_cs;
             if (coarse_staged) hipLaunchKernelGGL(k_sort_scatter_staged, dim3(w.sort_wgs, count), dim3(SORT_THREADS), 0, s, l1, d1, per_wg, bins);
             else hipLaunchKernelGGL(k_sort_scatter_lds<SORT_FEW_BINS>, dim3(w.sort_wgs, count), dim3(SORT_THREADS), 0, s, l1, d1, per_wg, bins);
             SortJobs l2 = sj;
             for (uint32_t i = 0; i < count; i++) l2.cursor[i] = l1.offsets[i];          // the coarse offsets (k_scan wrote offsets = cursor; the scatter advanced neither: it ranks in LDS)
-            const char* e_st = ZK_FORM_ENV("ZK_SORT_FINE_STAGED");          // a kernel-form switch (zk_common.h)
-            bool staged = e_st ? atoi(e_st) != 0 : b.n * b.nw / bins >= SORT_FINE_STAGED_MIN;
+            bool staged = opt_on(OPT_SORT_FINE_STAGED, b.n * b.nw / bins >= SORT_FINE_STAGED_MIN);          // a kernel-form switch (zk_options.h)
             // its static LDS (part + the two staging tiles) plus 8 bytes per fine bucket must fit the device's per-workgroup limit (84 KB at c = 22; the
             // MI355X allows 160 KB): asked once per device, the plain form serves wherever it does not fit
             if (staged) {

@@ -62,12 +62,6 @@ struct PinSlot {
     }
 };
 static constexpr uint32_t PIN_MAX_SLOTS = 15;
-// key points are checked like the reference checks them on the way in (of_bytes_exn, curve.ml:199-212: encoding, curve, prime-order subgroup);
-// ZK_KEY_SUBGROUP_CHECK=0 skips the subgroup part (see groth16.hip)
-static bool key_subgroup_check() {          // read per key (set-up path); without the check a pool never gets folded windows (msm.cuh)
-    const char* e = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    return !(e && atoi(e) == 0);
-}
 struct PinKey {
     uint32_t n = 0, m = 0, n_mid = 0;
     // A whole key is shard 0 of 1.  A shard of a multi-device key (PinGroup below) holds the points [lo, hi) of every pool -- the pools are cut in `world`
@@ -179,10 +173,7 @@ __global__ void k_pinocchio_scalars(PinScalPtrs out, PinHArgs ha, const uint32_t
 }
 
 // ---- the compact h pool's precondition: v_all / w_all are the images of the key's own powers si (header comment)
-static bool pin_compact_wanted() {          // read per key (set-up path)
-    const char* e = ::zk::opt("ZK_PIN_COMPACT_H");
-    return !(e && atoi(e) == 0);
-}
+static bool pin_compact_wanted() { return opt_on(OPT_PIN_COMPACT_H, true); }          // read per key (set-up path)
 // The seed of rho.  The check is a random linear combination, and it is worth its 2^-254 only if rho cannot be known before the key's bytes are fixed:
 // with a seed anybody can compute (rounds 1-5: a constant mixed with n and m) a key with v_all[i] += [a] G, v_all[j] -= [a rho_i / rho_j] G passes, is
 // proved from si, and the proof differs from what ZKCompute.f computes from that key.  So the seed is a digest of the very bytes that are checked
@@ -283,8 +274,7 @@ static inline void pin_slice(uint64_t full, uint32_t rank, uint32_t world, uint6
 
 // which products read another product's sort (PinKey::share1 / share2), decided per key once its base sets exist
 static int pin_decide_shared_sort(PinKey& k, hipStream_t s) {
-    const char* e = ::zk::opt("ZK_PIN_SHARED_SORT");          // 0: every product sorts for itself (A/B, tests)
-    if (e && atoi(e) == 0) return ZK_OK;
+    if (!opt_on(OPT_PIN_SHARED_SORT, true)) return ZK_OK;          // 0: every product sorts for itself (A/B, tests)
     auto try_share = [&](const MsmBases& a, const MsmBases& b, int* slot, int from) -> int {
         if (!a.n || !b.n) return ZK_OK;
         bool same = false;
@@ -541,7 +531,7 @@ static int pin_slot_get(PinKey& k, uint32_t idx, PinSlot** out) {
         ZKCHK(sl->out_dev.alloc(960));
         HIPCHK(hipStreamCreateWithFlags(&sl->st, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&sl->done, hipEventDisableTiming));
-        if (idx == 0 && k.world == 1 && !::zk::opt("ZK_SERIAL_STREAMS")) {
+        if (idx == 0 && k.world == 1 && !opt_is_set(OPT_SERIAL_STREAMS)) {
             // the slot of the synchronous zk_pinocchio_prove: two more streams, used only while no other proof is in flight (groth16.hip, slot 0)
             HIPCHK(hipStreamCreateWithFlags(&sl->s1, hipStreamNonBlocking));
             HIPCHK(hipStreamCreateWithFlags(&sl->s2, hipStreamNonBlocking));

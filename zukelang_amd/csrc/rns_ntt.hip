@@ -290,10 +290,7 @@ __global__ void k_rns_table_scale(uint32_t* __restrict__ res, uint64_t total, ui
 }
 
 // ------------------------------------------------------------------ host side
-bool rns_enabled() {
-    const char* e = ZK_FORM_ENV("ZK_FR_RNS");
-    return e ? atoi(e) != 0 : RNS_DEFAULT_ON;
-}
+bool rns_enabled() { return opt_on(OPT_FR_RNS, RNS_DEFAULT_ON); }
 static inline dim3 g1d(uint64_t n, unsigned t = 256) { return dim3((unsigned)((n + t - 1) / t)); }
 static int check_shape(uint64_t total, uint32_t log_len) {
     if (log_len == 0 || log_len > RNS_MAX_LOG || total == 0 || (total & (total - 1)) || ((uint64_t)1 << log_len) > total) ZK_FAIL(ZK_ERR_ARG, "rns: bad transform shape");

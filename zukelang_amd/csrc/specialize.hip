@@ -220,8 +220,7 @@ int zk_groth16_pk_specialize(uint32_t n, uint32_t m, const zk_csr* L, const zk_c
     Ctx& c = ctx();
     hipStream_t s = c.stream;
     // ---- the string: five lists from outside, checked like the points of an uploaded key, the first bad list deciding
-    const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    const bool chk = !(e_chk && atoi(e_chk) == 0);
+    const bool chk = key_subgroup_check();
     DevBuf s1, s2;
     ZKCHK(s1.alloc(96 * (T + 2 * (uint64_t)n)));
     ZKCHK(s2.alloc(192 * ((uint64_t)n + 3)));

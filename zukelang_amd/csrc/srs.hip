@@ -211,8 +211,7 @@ static int srs_contribute_run(uint64_t n1, uint64_t nab, uint64_t n2, const uint
     Ctx& c = ctx();
     hipStream_t s = c.stream;
     HIPCHK(hipGetLastError());
-    const char* e_chk = ::zk::opt("ZK_KEY_SUBGROUP_CHECK");
-    const bool chk = !(e_chk && atoi(e_chk) == 0);
+    const bool chk = key_subgroup_check();
     DevBuf s1, s2;
     ZKCHK(srs_decode(srs_g1, srs_g2, n1, nab, n2, chk, "srs_contribute", s1, s2, s));
     uint8_t *d_tau1 = s1.as<uint8_t>(), *d_at1 = d_tau1 + 96 * n1, *d_bt1 = d_at1 + 96 * nab, *d_b2 = s2.as<uint8_t>(), *d_tau2 = d_b2 + 192;
